@@ -2,9 +2,11 @@
 """Headline benchmark: depth-maps/sec of the DPT path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W                          # BASELINE configs[2]: DA-V2 ViT-L, 518x518 (-> 504), batch 32, bf16
+    python bench.py --gpus N --steps K --warmup W --full                   # + roofline, CPU baseline, other modes, other configurations
     python bench.py --precision bf16x3 --steps 20                          # the same workload in the mode that meets the 1e-3 tolerance
     python bench.py --size 1036 --batch 8                                  # the other north-star size (1036x1036, 5477 tokens)
     python bench.py --model beitl   (or swinl)                             # BASELINE configs[4]: MiDaS v3.1 BEiT-L / SwinV2-L, 384x384, batch 16
+    python bench.py ... --dump-outputs DIR                                 # + DIR/depth.npy: the depth maps of the last timed step (float32)
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...)
 
 One "step" = one pass of the hot path (mdpt_forward through the C ABI) over one batch of synthetic images per GPU,
@@ -12,6 +14,10 @@ followed (N>1) by the RCCL all-gather of the depth maps. Default workload = BASE
 ViT-L, "518x518" images (= 504x504 model tensor, the reference's own size snapping), bf16 MFMA with fp32 accumulate,
 batch 32 per GPU (weak scaling: global batch 32*N), seeded synthetic weights and inputs already resident in HBM.
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; everything else it can measure or check
+(per-kernel profile passes and roofline, the H2D-inclusive rate, the CPU baseline and error, the other arithmetic modes, the other
+BASELINE configurations under `secondary`, the N-rank gather self-check) runs only with --full, after the timed region.
 """
 from __future__ import annotations
 
@@ -39,6 +45,7 @@ PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 # what a loop of nothing but bf16 MFMAs on random operands sustains on this part (power limit: 1.93 GHz of the 2.4 GHz the nominal peak is
 # quoted at; tools/probes/mfma_power.hip, profiles/r03_mfma_power_probe.txt). Context for `roofline.frac`, never its denominator.
 SUSTAINED_BF16_TFLOPS = 2030.0
+DUMP_BYTES = 64 << 20  # --dump-outputs cap
 FAMILY = {"vitl": "Depth-Anything-V2 ViT-L", "vits": "Depth-Anything-V2 ViT-S", "vitb": "Depth-Anything-V2 ViT-B",
           "beitl": "MiDaS v3.1 BEiT-L-384", "swinl": "MiDaS v3.1 SwinV2-L-384"}
 SYNTH_NAME = {"beitl": "beit_large_384", "swinl": "swin2_large_384"}
@@ -371,6 +378,21 @@ def secondary_legs(args, dev, lib, vitl_model):
     return out
 
 
+def dump_outputs(out_dir: str, y: torch.Tensor) -> None:
+    """DIR/depth.npy = what a caller of the timed path receives (the [B,H,W] depth maps of the last step; N>1: the gathered global batch)
+    as float32. Above DUMP_BYTES: the maps at a fixed seeded choice of batch indices, in index order, as many as fit."""
+    import numpy as np
+    y = y.detach().float()
+    keep = DUMP_BYTES // (y[0].numel() * 4)
+    if keep == 0:
+        raise SystemExit(f"--dump-outputs: one depth map {tuple(y.shape[1:])} is larger than {DUMP_BYTES >> 20} MB")
+    if keep < y.shape[0]:
+        idx = torch.randperm(y.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        y = y[idx.to(y.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "depth.npy"), y.cpu().numpy())
+
+
 def rccl_version() -> str | None:
     try:
         v = torch.cuda.nccl.version()
@@ -390,13 +412,20 @@ def main():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "bf16x3", "fp16", "fp16x3", "mixed"],
                     help="MFMA operand arithmetic (include/mdpt.h MDPT_PREC_*); bf16 / fp16 run a 16-bit model, the others a float32 model")
     ap.add_argument("--tile", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-launch HIP-event passes behind the timed region (no roofline object)")
+    ap.add_argument("--full", action="store_true", help="behind the timed region also run the per-kernel profile passes (roofline), the H2D-inclusive "
+                    "rate, the CPU baseline and the other arithmetic modes, the other BASELINE configurations (`secondary`, default workload) and the "
+                    "N-rank gather self-check; a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the depth maps the timed path returned in its last step to DIR/depth.npy (float32; "
+                    f"above {DUMP_BYTES >> 20} MB a fixed, seeded sample of whole maps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the other arithmetic modes")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the per-launch HIP-event passes behind the timed region (no roofline object)")
     ap.add_argument("--no-split", action="store_true", help="nothing on the library's side stream: no two-stream half-batch split inside mdpt_forward, reassembly branches behind the encoder (every kernel alone on the GPU)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configurations the default run reports under `secondary`")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the other BASELINE configurations the default run reports under `secondary`")
     ap.add_argument("--fake-model", action="store_true", help="test hook (tests/test_parallel.py): run the N-rank control flow - barriers, timed region, "
                     "max-over-ranks reduction, rank-0 JSON line - on CPU tensors with a stand-in model and the gloo backend; measures nothing")
     args = ap.parse_args()
+    if not args.full:
+        args.no_profile = args.no_cpu_baseline = args.no_secondary = True
     midas = args.model in SYNTH_NAME
     default_run = args.model == "vitl" and not args.size and not args.batch and args.precision == "bf16" and not args.tile and not args.no_split
     if not args.size:
@@ -473,10 +502,13 @@ def main():
         per_rank_elapsed = [float(v) for v in every.tolist()]
         elapsed = max(per_rank_elapsed)
         n_ranks_seen = dist.get_world_size()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y)
+    if world > 1:
         # Self-check of the gathered tensor ("gathered result == concatenation of single-GPU results bit-for-bit"):
         # rank 0 recomputes the LAST rank's shard locally (same seed rule, 1 + rank) and compares it bitwise with its slice of what the
         # all-gather delivered; its own slice must equal its own local forward. Collective-free, after the timed region.
-        if rank == 0:
+        if rank == 0 and args.full:
             with torch.inference_mode():
                 last = world - 1
                 x_last = torch.randn(args.batch, 3, args.size, args.size, generator=torch.Generator().manual_seed(1 + last)).to(dev).to(dtype)
@@ -520,7 +552,7 @@ def main():
             "per_rank_maps_per_s": {"min": round(args.batch * args.steps / max(per_rank_elapsed), 3),
                                     "max": round(args.batch * args.steps / min(per_rank_elapsed), 3)},
         }
-        if world == 1 and dev.type == "cuda":
+        if world == 1 and dev.type == "cuda" and args.full:
             # the rate with the H2D copy of each batch inside the loop (SURVEY §8(d) "report both"; the C ABI takes device pointers, only
             # DPTModel.inference starts from a host image): pinned host batch in the model dtype, one extra pass, never `value`
             x_host = x_cpu.to(dtype).pin_memory()

@@ -1,4 +1,4 @@
-"""bench.py's output contract (one JSON line; metric/config of BASELINE.json; roofline and cpu_baseline objects). `pytest -m gpu`."""
+"""bench.py's output contract (one JSON line; metric/config of BASELINE.json; with --full the roofline and cpu_baseline objects). `pytest -m gpu`."""
 import json
 import os
 import subprocess
@@ -11,7 +11,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -37,3 +37,21 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert d["fp16_mode"]["error_vs_cpu_fp32"]["rel_to_max"] <= 3e-3 and d["fp16_mode"]["value"] > d["mixed_mode"]["value"]
     assert abs(roof["path_frac"] - d["path_frac_of_mfma_peak"]) < 1e-9
     assert 0 < d["value_incl_h2d"] <= d["value"] * 1.02
+
+
+def test_plain_bench_times_only_the_steps_and_dumps_the_last_step(tmp_path):
+    """Without --full: the headline fields, nothing measured behind the timed region, and --dump-outputs writes the [32, 504, 504] depth maps
+    of the last timed step as float32."""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "depth-maps/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["value"] - 32 * 4 / (d["ms_per_step"] * 4 / 1e3)) / d["value"] < 1e-3
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "secondary" not in d and "value_incl_h2d" not in d and "mixed_mode" not in d
+    import numpy as np
+    assert sorted(os.listdir(tmp_path)) == ["depth.npy"]
+    y = np.load(tmp_path / "depth.npy")
+    assert y.dtype == np.float32 and y.shape == (32, 504, 504) and np.isfinite(y).all() and y.std() > 0

@@ -72,7 +72,7 @@ def test_bench_control_flow_at_world_size_2_on_gloo():
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--fake-model"],
+                        "--master-port", str(port), os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--fake-model", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=repo, env={**os.environ, "OMP_NUM_THREADS": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -87,3 +87,22 @@ def test_bench_control_flow_at_world_size_2_on_gloo():
     assert d["gather_bitwise_ok"] is True
     assert 0 < d["per_rank_maps_per_s"]["min"] <= d["per_rank_maps_per_s"]["max"]
     assert abs(d["per_rank_maps_per_s"]["min"] * 2 - d["value"]) / d["value"] < 1e-3
+
+
+def test_plain_bench_at_world_size_2_dumps_the_gathered_last_step(tmp_path):
+    """Without --full the N-rank run skips the gather self-check, and --dump-outputs writes what rank 0 received in the last timed step:
+    the gathered global batch, the concatenation of every rank's maps of its own seeded images (seed 1 + rank)."""
+    import json, subprocess
+    import numpy as np
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+                        "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--fake-model", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=REPO, env={**os.environ, "OMP_NUM_THREADS": "1"})
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["gather_bitwise_ok"] is None and d["cpu_baseline"] is None and d["roofline"] is None
+    y = np.load(tmp_path / "depth.npy")
+    want = torch.cat([torch.randn(2, 3, 16, 16, generator=torch.Generator().manual_seed(1 + rank)).mean(dim=1) for rank in range(2)])
+    assert y.dtype == np.float32 and np.array_equal(y, want.numpy())

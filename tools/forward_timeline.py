@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One forward pass as a launch-by-launch timeline, from a rocprofv3 --kernel-trace CSV.
 
-    rocprofv3 --kernel-trace --output-format csv -d DIR -- python bench.py --no-split --steps 2 --warmup 1 --no-cpu-baseline --no-profile
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python bench.py --no-split --steps 2 --warmup 1
     python tools/forward_timeline.py DIR out.md
 
 The last forward in the trace (from its patchify launch on) is printed in launch order: duration, gap to the previous launch, grid in

@@ -6,7 +6,7 @@ import subprocess
 import sys
 
 root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-secondary", "--no-cpu-baseline", *sys.argv[1:]],
+out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-secondary", "--no-cpu-baseline", *sys.argv[1:]],
                      capture_output=True, text=True, cwd=root)
 line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
 if not line:
