@@ -280,6 +280,15 @@ int mdpt_prepare_image(const void* bgr_u8_hwc, int32_t in_h, int32_t in_w, void*
 int mdpt_forward_bgr(mdpt_handle* h, const void* bgr_u8_hwc, int32_t in_h, int32_t in_w, int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3],
                      const float rgb_std[3], int32_t interpolation, void* depth_hw, int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* mdpt_forward_bgr for B frames of one size (DPTModel.inference_batch; additive to ABI v6): uint8 [B,in_h,in_w,3] BGR, packed, on the device -> depth
+ * [B,H,W]. The im2col kernel takes the frame index as its grid's y dimension, so all B frames are resized, normalised and patchified in one launch.
+ * Image b's map equals mdpt_prepare_image(frame b), stacked, then mdpt_forward of the batch, bit for bit, in every family, dtype and arithmetic mode
+ * (latency mode included); a batch at or above the split size (mdpt_set_batch_split) runs as two halves exactly as mdpt_forward does. B = 1 is
+ * mdpt_forward_bgr. Workspace as for mdpt_forward(B). */
+int mdpt_forward_bgr_batch(mdpt_handle* h, const void* bgr_u8_bhwc, int32_t B, int32_t in_h, int32_t in_w, int32_t image_dtype, int32_t H, int32_t W,
+                           const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw, int32_t depth_dtype, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* Depth post-processing on the device (reference muggled_dpt/demo_helpers/postprocess.py and
  * run_3dviewer.py:576-590). All buffers are device pointers; `minmax` is a 2-float device buffer {min, max} and
  * `scratch8` 8 bytes of device scratch - nothing is read back to the host, nothing synchronises.
@@ -298,6 +307,33 @@ int mdpt_post_minmax(const void* in_f32, size_t count, void* minmax_out, void* s
 int mdpt_post_scale_prediction(const void* in_bhw_f32, int32_t B, int32_t in_h, int32_t in_w, void* out_bhw_f32, int32_t out_h,
                                int32_t out_w, void* minmax_out, void* scratch8, void* stream);
 int mdpt_post_normalize(const void* in_f32, size_t count, const void* minmax, void* out, int32_t mode, int32_t lossy, void* stream);
+
+/* Per-image display tail (additive to ABI v6): the per-frame loop of the reference's video demo (run_video.py:348-361: scale_prediction ->
+ * convert_to_uint8 -> optional 255 - x -> histogram_equalization -> colormap LUT) over a batch, every image with its own min/max, histogram and
+ * LUT, nothing read back to the host. Image b's result equals the per-frame composition on image b alone, bit for bit; a NaN map gives that image
+ * what MDPT_POST_U8 gives it (all 0 before the reverse) and touches no other image. Buffers (device):
+ *   parts  [B, MDPT_POST_SEG_PARTS, 2] uint32, the per-image min/max partials mdpt_post_minmax_seg leaves for mdpt_post_u8_hist_seg
+ *   hist   [B, 256] uint32 counts, ACCUMULATED into (zero it first, e.g. through mdpt_post_minmax_seg's hist_clear)
+ *   lut    [B, 256] uint8 equalization LUTs; cmap_bgr [256, 3] uint8 BGR (a 1x256x3 colormap LUT)
+ *   mdpt_post_minmax_seg ...... out_bhw_f32 == NULL: per-image min/max of in_bhw ([B,in_h,in_w], dtype in_dtype = MDPT_DTYPE_*);
+ *                               else mdpt_post_scale_prediction's bilinear resize of each image to out_h x out_w, rounded to in_dtype (the map
+ *                               scale_prediction returns), stored as fp32, and the per-image min/max of that. hist_clear != NULL: zeroes [B,256]
+ *   mdpt_post_u8_hist_seg ..... (255 * normalize_01(image b)).byte() per image (MDPT_POST_U8 arithmetic, image b's min/max), reverse != 0: 255 - x,
+ *                               -> out_u8 [B,count]; hist != NULL also counts the result into hist (LDS-private bins, integer atomics)
+ *   mdpt_post_histogram ....... 256-bin histogram per image of a uint8 [B,count] batch, accumulated into hist
+ *   mdpt_post_equalize_lut .... the equalization LUT of every image (demo_helpers/postprocess.py:107-145). bin_of_value == NULL: cv2.equalizeHist
+ *                               (fp32, round half to even). Otherwise the thresholded branch: bin_of_value = 256 int32 on the device, the bin
+ *                               np.histogram(x, 1 + max - min, range=(min, max)) puts value v in (-1: outside), LUT built in fp64 as numpy does
+ *   mdpt_post_colorize ........ out = cmap_bgr[eq_lut[b][x]] as [B,count,3] BGR (channels 3), or eq_lut[b][x] as [B,count] (channels 1);
+ *                               eq_lut == NULL: identity, cmap_bgr == NULL: gray (cv2.cvtColor GRAY2BGR) */
+#define MDPT_POST_SEG_PARTS 64
+int mdpt_post_minmax_seg(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t in_h, int32_t in_w, void* out_bhw_f32, int32_t out_h, int32_t out_w,
+                         void* parts, void* hist_clear, void* stream);
+int mdpt_post_u8_hist_seg(const void* in_bhw, int32_t in_dtype, int32_t B, size_t count, const void* parts, int32_t reverse, void* out_u8, void* hist,
+                          void* stream);
+int mdpt_post_histogram(const void* in_u8, int32_t B, size_t count, void* hist, void* stream);
+int mdpt_post_equalize_lut(const void* hist, int32_t B, const void* bin_of_value, int32_t min_value, int32_t max_value, void* lut_out, void* stream);
+int mdpt_post_colorize(const void* in_u8, int32_t B, size_t count, const void* eq_lut, const void* cmap_bgr, int32_t channels, void* out, void* stream);
 
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */

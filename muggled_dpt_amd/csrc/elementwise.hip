@@ -681,17 +681,19 @@ __global__ __launch_bounds__(256) void prepare_image_kernel(const unsigned char*
 // of the model tensor, computed from the uint8 image as above, rounded to the dtype the stand-alone kernel would have written it in (img_dt: the
 // values - and so every bit behind them - equal mdpt_prepare_image + patchify_kernel) and stored straight into its three places of the patch
 // embedding's im2col rows (k = c P^2 + ky P + kx). The normalised image never exists in memory. The first pixel of a patch also zeroes its
-// row's padding columns [3 P^2, Kp).
+// row's padding columns [3 P^2, Kp). Batched (mdpt_forward_bgr_batch): blockIdx.y = image b reads frame b of the packed [B,ih,iw,3] source and
+// writes rows b gh gw + py gw + px, the row layout of patchify_kernel.
 template <int INTERP>
 __global__ __launch_bounds__(256) void prepare_patchify_kernel(const unsigned char* __restrict__ bgr, int img_dt, op_t* out_hi, op_t* out_lo, int ih, int iw,
                                                                int H, int W, int P, int Kp, float m0, float m1, float m2, float s0, float s1, float s2) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
+    const int b = blockIdx.y;
     const int ox = idx % W, oy = idx / W;
     float v[3];
-    aa_pixel_rgb<INTERP>(bgr, ih, iw, H, W, oy, ox, m0, m1, m2, s0, s1, s2, v[0], v[1], v[2]);
+    aa_pixel_rgb<INTERP>(bgr + (size_t)b * ih * iw * 3, ih, iw, H, W, oy, ox, m0, m1, m2, s0, s1, s2, v[0], v[1], v[2]);
     const int py = oy / P, ky = oy - py * P, px = ox / P, kx = ox - px * P;
-    const size_t row = ((size_t)py * (W / P) + px) * Kp;
+    const size_t row = ((size_t)b * (H / P) * (W / P) + (size_t)py * (W / P) + px) * Kp;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float r = img_dt == MDPT_DT_BF16 ? (float)(__bf16)v[c] : (img_dt == MDPT_DT_F16 ? (float)(_Float16)v[c] : v[c]);
@@ -1135,16 +1137,17 @@ int MDPT_FN(mdpt_launch_prepare_image)(const unsigned char* bgr, void* out, int 
     LAUNCH_RET();
 }
 
-int MDPT_FN(mdpt_launch_prepare_patchify)(const unsigned char* bgr, int img_dtype, op_t* out_hi, op_t* out_lo, int ih, int iw, int H, int W, int P, int Kp,
+int MDPT_FN(mdpt_launch_prepare_patchify)(const unsigned char* bgr, int img_dtype, op_t* out_hi, op_t* out_lo, int B, int ih, int iw, int H, int W, int P, int Kp,
                                          const float mean[3], const float inv_std[3], int interp, hipStream_t stream) {
-    if (ih <= 0 || iw <= 0 || H <= 0 || W <= 0 || P <= 0 || (H % P) || (W % P) || Kp < 3 * P * P || (interp != 0 && interp != 1) || img_dtype < MDPT_DT_F32 || img_dtype > MDPT_DT_F16)
+    if (B <= 0 || B > 65535 || ih <= 0 || iw <= 0 || H <= 0 || W <= 0 || P <= 0 || (H % P) || (W % P) || Kp < 3 * P * P || (interp != 0 && interp != 1) ||
+        img_dtype < MDPT_DT_F32 || img_dtype > MDPT_DT_F16)
         return (int)hipErrorInvalidValue;
     MdptProfScope prof("prepare_patchify_kernel", 0.0, stream);
     if (interp == 0)
-        hipLaunchKernelGGL(prepare_patchify_kernel<0>, dim3((H * W + 255) / 256), dim3(256), 0, stream, bgr, img_dtype, out_hi, out_lo, ih, iw, H, W, P, Kp, mean[0], mean[1],
+        hipLaunchKernelGGL(prepare_patchify_kernel<0>, dim3((H * W + 255) / 256, B), dim3(256), 0, stream, bgr, img_dtype, out_hi, out_lo, ih, iw, H, W, P, Kp, mean[0], mean[1],
                            mean[2], inv_std[0], inv_std[1], inv_std[2]);
     else
-        hipLaunchKernelGGL(prepare_patchify_kernel<1>, dim3((H * W + 255) / 256), dim3(256), 0, stream, bgr, img_dtype, out_hi, out_lo, ih, iw, H, W, P, Kp, mean[0], mean[1],
+        hipLaunchKernelGGL(prepare_patchify_kernel<1>, dim3((H * W + 255) / 256, B), dim3(256), 0, stream, bgr, img_dtype, out_hi, out_lo, ih, iw, H, W, P, Kp, mean[0], mean[1],
                            mean[2], inv_std[0], inv_std[1], inv_std[2]);
     LAUNCH_RET();
 }

@@ -429,11 +429,10 @@ static int ensure_side_stream(mdpt_handle* h, hipStream_t s0, void* scratch) {
 
 static inline size_t dtype_bytes(int dt) { return dt == MDPT_DTYPE_F32 ? 4 : 2; }
 
-int mdpt_forward(mdpt_handle* h, const void* image_bchw, int32_t image_dtype, int32_t B, int32_t H, int32_t W, void* depth_bhw,
-                 int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h || !image_bchw || !depth_bhw) return fail(MDPT_E_INVALID, "null argument");
-    for (int dt : {image_dtype, depth_dtype})
-        if (dt != MDPT_DTYPE_F32 && dt != MDPT_DTYPE_BF16 && dt != MDPT_DTYPE_F16) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
+// mdpt_forward and mdpt_forward_bgr_batch: the source is either an image tensor (image_bchw) or, when bgr != NULL, B packed uint8 frames the
+// im2col kernel reads itself (image_bchw is NULL then; the split's second half starts B0 frames into them, as it starts B0 images into the tensor)
+static int forward_batch(mdpt_handle* h, const void* image_bchw, const Ctx::BgrSource* bgr, int32_t image_dtype, int32_t B, int32_t H, int32_t W,
+                         void* depth_bhw, int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
     if (h->split_min > 0 && B >= h->split_min && B >= 2 && h->dbg_block < 0) {
         // two half batches, one on the caller's stream, one on the side stream; joined before returning to the caller's stream
         const int B0 = B / 2, B1 = B - B0;
@@ -454,11 +453,16 @@ int mdpt_forward(mdpt_handle* h, const void* image_bchw, int32_t image_dtype, in
         c1.consts_cached = h->cache_hit(c1.ws, B1, H, W);
         h->cache_clear();
         const size_t in_stride = (size_t)3 * H * W * dtype_bytes(image_dtype), out_stride = (size_t)H * W * dtype_bytes(depth_dtype);
+        if (bgr) {
+            c0.bgr = *bgr;
+            c1.bgr = *bgr;
+            c1.bgr.ptr += (size_t)B0 * bgr->ih * bgr->iw * 3;
+        }
         // Whatever happens after the fork, the side stream is joined back into the caller's stream before returning: kernels already
         // queued there keep using the second half of the workspace and the caller's tensors, which the caller may free or reuse on its
         // own stream as soon as this call returns (also on the error path).
         int rc = forward_one(h, c0, image_bchw, image_dtype, depth_bhw, depth_dtype);
-        if (rc == 0) rc = forward_one(h, c1, (const char*)image_bchw + in_stride * B0, image_dtype, (char*)depth_bhw + out_stride * B0, depth_dtype);
+        if (rc == 0) rc = forward_one(h, c1, bgr ? nullptr : (const char*)image_bchw + in_stride * B0, image_dtype, (char*)depth_bhw + out_stride * B0, depth_dtype);
         const hipError_t ej = hipEventRecord(h->ev_join, h->side_stream);
         const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(s0, h->ev_join, 0) : ej;
         if (ew != hipSuccess) hipStreamSynchronize(h->side_stream);  // last resort: never leave the side stream running un-joined
@@ -472,29 +476,42 @@ int mdpt_forward(mdpt_handle* h, const void* image_bchw, int32_t image_dtype, in
     Ctx c;
     CHK(make_ctx(h, B, H, W, workspace, workspace_bytes, stream, &c));
     c.consts_cached = hit;
+    if (bgr) c.bgr = *bgr;
     CHK(forward_one(h, c, image_bchw, image_dtype, depth_bhw, depth_dtype));
     if (h->grid_cache && h->dbg_block < 0) h->cache_store(0, workspace, B, H, W);
     return 0;
 }
 
-// ---- DPTModel.inference's device half (reference dpt_model.py:87-109: prepare_image_bgr -> forward), SURVEY 8(f) row 1 "fused with patchify"
-int mdpt_forward_bgr(mdpt_handle* h, const void* bgr_u8_hwc, int32_t in_h, int32_t in_w, int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3],
-                     const float rgb_std[3], int32_t interpolation, void* depth_hw, int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h || !bgr_u8_hwc || !depth_hw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
+int mdpt_forward(mdpt_handle* h, const void* image_bchw, int32_t image_dtype, int32_t B, int32_t H, int32_t W, void* depth_bhw,
+                 int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !image_bchw || !depth_bhw) return fail(MDPT_E_INVALID, "null argument");
+    for (int dt : {image_dtype, depth_dtype})
+        if (dt != MDPT_DTYPE_F32 && dt != MDPT_DTYPE_BF16 && dt != MDPT_DTYPE_F16) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
+    return forward_batch(h, image_bchw, nullptr, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
+}
+
+// ---- DPTModel.inference's device half (reference dpt_model.py:87-109: prepare_image_bgr -> forward), SURVEY 8(f) row 1 "fused with patchify",
+// for B packed frames of one size (DPTModel.inference_batch); image b's map equals mdpt_prepare_image(frame b), stacked, then mdpt_forward
+int mdpt_forward_bgr_batch(mdpt_handle* h, const void* bgr_u8_bhwc, int32_t B, int32_t in_h, int32_t in_w, int32_t image_dtype, int32_t H, int32_t W,
+                           const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw, int32_t depth_dtype, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    if (!h || !bgr_u8_bhwc || !depth_bhw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
     for (int dt : {image_dtype, depth_dtype})
         if (dt != MDPT_DTYPE_F32 && dt != MDPT_DTYPE_BF16 && dt != MDPT_DTYPE_F16) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
     if (interpolation != MDPT_INTERP_BILINEAR && interpolation != MDPT_INTERP_BICUBIC)
         return fail(MDPT_E_UNSUPPORTED, "interpolation %d: antialiased resize exists for bilinear and bicubic only (as in torch)", interpolation);
     if (in_h <= 0 || in_w <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d", in_h, in_w);
-    const bool hit = h->cache_hit(workspace, 1, H, W);
-    Ctx c;
-    CHK(make_ctx(h, 1, H, W, workspace, workspace_bytes, stream, &c));
-    c.consts_cached = hit;
-    c.bgr.ptr = (const unsigned char*)bgr_u8_hwc; c.bgr.ih = in_h; c.bgr.iw = in_w; c.bgr.round_dtype = image_dtype; c.bgr.interp = interpolation;
-    for (int i = 0; i < 3; ++i) { c.bgr.mean[i] = rgb_mean[i]; c.bgr.inv_std[i] = 1.0f / rgb_std[i]; }  // patch_embed.py:38-39,62
-    CHK(forward_one(h, c, nullptr, image_dtype, depth_hw, depth_dtype));
-    if (h->grid_cache && h->dbg_block < 0) h->cache_store(0, workspace, 1, H, W);
-    return 0;
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);  // (the im2col kernel's grid y is the frame index)
+    Ctx::BgrSource src;
+    src.ptr = (const unsigned char*)bgr_u8_bhwc; src.ih = in_h; src.iw = in_w; src.round_dtype = image_dtype; src.interp = interpolation;
+    for (int i = 0; i < 3; ++i) { src.mean[i] = rgb_mean[i]; src.inv_std[i] = 1.0f / rgb_std[i]; }  // patch_embed.py:38-39,62
+    return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
+}
+
+int mdpt_forward_bgr(mdpt_handle* h, const void* bgr_u8_hwc, int32_t in_h, int32_t in_w, int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3],
+                     const float rgb_std[3], int32_t interpolation, void* depth_hw, int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    return mdpt_forward_bgr_batch(h, bgr_u8_hwc, 1, in_h, in_w, image_dtype, H, W, rgb_mean, rgb_std, interpolation, depth_hw, depth_dtype, workspace,
+                                  workspace_bytes, stream);
 }
 
 static int forward_body(mdpt_handle* h, const Ctx& c, const void* image_bchw, int image_dtype, void* depth_bhw, int depth_dtype);
@@ -503,7 +520,7 @@ static int forward_body(mdpt_handle* h, const Ctx& c, const void* image_bchw, in
 // pixel into an all-NaN depth map - the value reaches every token through the first attention and torch's ReLU keeps it. Here the saturating fp16
 // operand converts (v_med3) and the v_max ReLUs would return a finite, plausible map instead. The im2col kernel, which reads every pixel anyway,
 // flags such images in B words of the plan and one small launch behind the head writes their maps as NaN: two stream-ordered operations per
-// forward (graph-capturable, nothing on the host). uint8 sources (mdpt_forward_bgr) cannot hold a non-finite value and skip both.
+// forward (graph-capturable, nothing on the host). uint8 sources (mdpt_forward_bgr[_batch]) cannot hold a non-finite value and skip both.
 static int forward_one(mdpt_handle* h, const Ctx& c0, const void* image_bchw, int image_dtype, void* depth_bhw, int depth_dtype) {
     if (!h->nonfinite_prop || !image_bchw || h->dbg_block >= 0) return forward_body(h, c0, image_bchw, image_dtype, depth_bhw, depth_dtype);
     Ctx c = c0;
@@ -891,6 +908,55 @@ int mdpt_post_normalize(const void* in_f32, size_t count, const void* minmax, vo
     if (!in_f32 || !out || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
     if (mode < MDPT_POST_F32 || mode > MDPT_POST_U24) return fail(MDPT_E_INVALID, "unknown post-processing mode %d", mode);
     CHK(mdpt_launch_post_normalize((const float*)in_f32, (const float*)minmax, out, count, mode, lossy, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- per-image display tail (run_video.py:348-361 per frame, over a batch; demo_helpers/postprocess.py:107-145, toadui/colormaps.py:237-259)
+static bool post_dtype_ok(int dt) { return dt == MDPT_DTYPE_F32 || dt == MDPT_DTYPE_BF16 || dt == MDPT_DTYPE_F16; }
+
+int mdpt_post_minmax_seg(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t in_h, int32_t in_w, void* out_bhw_f32, int32_t out_h, int32_t out_w,
+                         void* parts, void* hist_clear, void* stream) {
+    if (!in_bhw || !parts) return fail(MDPT_E_INVALID, "null argument");
+    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
+    if (B <= 0 || B > 65535 || in_h <= 0 || in_w <= 0 || (out_bhw_f32 && (out_h <= 0 || out_w <= 0)))
+        return fail(MDPT_E_INVALID, "bad size %dx%dx%d -> %dx%d", B, in_h, in_w, out_h, out_w);
+    CHK(mdpt_launch_post_seg_minmax(in_bhw, in_dtype, B, in_h, in_w, (float*)out_bhw_f32, out_h, out_w, (unsigned*)parts, (unsigned*)hist_clear,
+                                    (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_u8_hist_seg(const void* in_bhw, int32_t in_dtype, int32_t B, size_t count, const void* parts, int32_t reverse, void* out_u8, void* hist,
+                          void* stream) {
+    if (!in_bhw || !parts || !out_u8 || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
+    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    CHK(mdpt_launch_post_seg_u8(in_bhw, in_dtype, B, count, (const unsigned*)parts, reverse != 0, (unsigned char*)out_u8, (unsigned*)hist,
+                                (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_histogram(const void* in_u8, int32_t B, size_t count, void* hist, void* stream) {
+    if (!in_u8 || !hist || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    CHK(mdpt_launch_post_hist((const unsigned char*)in_u8, B, count, (unsigned*)hist, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_equalize_lut(const void* hist, int32_t B, const void* bin_of_value, int32_t min_value, int32_t max_value, void* lut_out, void* stream) {
+    if (!hist || !lut_out) return fail(MDPT_E_INVALID, "null argument");
+    if (B <= 0) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    if (bin_of_value && (min_value < 0 || max_value > 255 || max_value <= min_value))
+        return fail(MDPT_E_INVALID, "bad equalization range [%d, %d]", min_value, max_value);
+    CHK(mdpt_launch_post_eq_lut((const unsigned*)hist, B, (const int*)bin_of_value, min_value, max_value, (unsigned char*)lut_out, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_colorize(const void* in_u8, int32_t B, size_t count, const void* eq_lut, const void* cmap_bgr, int32_t channels, void* out, void* stream) {
+    if (!in_u8 || !out || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    if (channels != 1 && channels != 3) return fail(MDPT_E_INVALID, "channels must be 1 or 3, got %d", channels);
+    CHK(mdpt_launch_post_colorize((const unsigned char*)in_u8, B, count, (const unsigned char*)eq_lut, (const unsigned char*)cmap_bgr, channels,
+                                  (unsigned char*)out, (hipStream_t)stream));
     return 0;
 }
 

@@ -192,6 +192,15 @@ int mdpt_launch_post_scale(const float* in, float* out, int B, int ih, int iw, i
                            unsigned* scratch2, hipStream_t stream);
 int mdpt_launch_post_normalize(const float* in, const float* minmax, void* out, size_t n, int mode, int lossy,
                                hipStream_t stream);
+// per-image display tail: parts = [B, MDPT_POST_SEG_PARTS, 2] ordered {min, max} partials, hist / hist_clear = [B, 256] counts, lut = [B, 256]
+int mdpt_launch_post_seg_minmax(const void* in, int in_dt, int B, int ih, int iw, float* out, int oh, int ow, unsigned* parts, unsigned* hist_clear,
+                                hipStream_t stream);
+int mdpt_launch_post_seg_u8(const void* in, int in_dt, int B, size_t n, const unsigned* parts, int reverse, unsigned char* out, unsigned* hist,
+                            hipStream_t stream);
+int mdpt_launch_post_hist(const unsigned char* in, int B, size_t n, unsigned* hist, hipStream_t stream);
+int mdpt_launch_post_eq_lut(const unsigned* hist, int B, const int* bin_of, int vmin, int vmax, unsigned char* lut, hipStream_t stream);
+int mdpt_launch_post_colorize(const unsigned char* in, int B, size_t n, const unsigned char* eq, const unsigned char* cmap, int channels, unsigned char* out,
+                              hipStream_t stream);
 
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);

@@ -43,11 +43,11 @@ int run_pos(const Ctx& c) {
                                 h->cfg.base_patch_grid_w, c.p.gh, c.p.gw, h->F, c.s);
 }
 
-// im2col rows of the patch embedding: from an image tensor, or (mdpt_forward_bgr) straight from the caller's uint8 BGR image
+// im2col rows of the patch embedding: from an image tensor, or (mdpt_forward_bgr[_batch]) straight from the caller's uint8 BGR frames
 int run_patchify(const Ctx& c, const void* image, int image_dtype, const Planes& im, int H, int W) {
     const mdpt_handle* h = c.h;
     if (c.bgr.ptr)
-        return OPLC(mdpt_launch_prepare_patchify, c.bgr.ptr, c.bgr.round_dtype, im.hi, im.lo, c.bgr.ih, c.bgr.iw, H, W, h->P, h->Kpatch, c.bgr.mean, c.bgr.inv_std, c.bgr.interp, c.s);
+        return OPLC(mdpt_launch_prepare_patchify, c.bgr.ptr, c.bgr.round_dtype, im.hi, im.lo, c.p.B, c.bgr.ih, c.bgr.iw, H, W, h->P, h->Kpatch, c.bgr.mean, c.bgr.inv_std, c.bgr.interp, c.s);
     return OPLC(mdpt_launch_patchify, image, image_dtype, im.hi, im.lo, c.p.B, H, W, h->P, h->Kpatch, c.s, c.poison);
 }
 

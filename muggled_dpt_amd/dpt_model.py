@@ -174,15 +174,18 @@ class PatchEmbed(_Stage):
         eng.call("mdpt_patch_embed", x, b, h, w, out, size_hw=(-(-h // tile) * tile, -(-w // tile) * tile), batch=b)
         return eng.as_output(out), (gh, gw)
 
-    def _prepare_plan(self, image_bgr: np.ndarray, max_side_length: int | None, use_square_sizing: bool, interpolation_mode: str):
-        """Size rule and argument checks of prepare_image (patch_embed.py:103-130): -> (model tensor (H, W), MDPT_INTERP_*, parameter, image dtype)."""
+    def _scaled_hw(self, img_h: int, img_w: int, max_side_length: int | None, use_square_sizing: bool) -> list[int]:
+        """The reference's size rule (patch_embed.py:112-127): model tensor sides, multiples of the tiling size."""
         if max_side_length is None:
             max_side_length = self._default_size_px
-        img_h, img_w = image_bgr.shape[0:2]
         largest_side = max(img_h, img_w)
         scale = max_side_length / largest_side
         targ_hw = (largest_side, largest_side) if use_square_sizing else (img_h, img_w)
-        scaled_hw = [max(1, round(side * scale / self._tiling_size)) * self._tiling_size for side in targ_hw]
+        return [max(1, round(side * scale / self._tiling_size)) * self._tiling_size for side in targ_hw]
+
+    def _prepare_plan(self, image_bgr: np.ndarray, max_side_length: int | None, use_square_sizing: bool, interpolation_mode: str):
+        """Size rule and argument checks of prepare_image (patch_embed.py:103-130): -> (model tensor (H, W), MDPT_INTERP_*, parameter, image dtype)."""
+        scaled_hw = self._scaled_hw(image_bgr.shape[0], image_bgr.shape[1], max_side_length, use_square_sizing)
         p = next(self.parameters())
         # one HIP kernel (antialiased resize + BGR->RGB + normalisation), mdpt_prepare_image. No torch fallback: what the kernel does not
         # cover raises, exactly where torch's own F.interpolate(antialias=True) would (it supports bilinear and bicubic only).
@@ -202,9 +205,14 @@ class PatchEmbed(_Stage):
         Sides snap to multiples of 2*patch (so a 518x518 image is processed at 504x504)."""
         scaled_hw, interp, p, out_dtype = self._prepare_plan(image_bgr, max_side_length, use_square_sizing, interpolation_mode)
         img_h, img_w = image_bgr.shape[0:2]
-        lib = native.load()
         with torch.cuda.device(p.device):
             src = self._stage_host_image(image_bgr, p.device)
+            return self._prepare_device(src, img_h, img_w, scaled_hw, interp, p, out_dtype)
+
+    def _prepare_device(self, src: Tensor, img_h: int, img_w: int, scaled_hw, interp: int, p, out_dtype) -> Tensor:
+        """mdpt_prepare_image on one uint8 HxWx3 frame already on the device -> [1,3,H',W'] in the model dtype."""
+        lib = native.load()
+        with torch.cuda.device(p.device):
             out = torch.empty((1, 3, scaled_hw[0], scaled_hw[1]), device=p.device, dtype=out_dtype)
             stream = torch.cuda.current_stream(p.device).cuda_stream
             mean3, std3 = self._norm_constants()
@@ -219,11 +227,14 @@ class PatchEmbed(_Stage):
             c = self.__dict__["_norm_c"] = ((ctypes.c_float * 3)(*self.rgb_offset), (ctypes.c_float * 3)(*self.rgb_stdev))
         return c
 
-    def _stage_host_image(self, image_bgr: np.ndarray, device: torch.device) -> Tensor:
+    def _stage_host_image(self, image_bgr, device: torch.device) -> Tensor:
         """uint8 host image -> device through a reusable PINNED staging buffer (an asynchronous copy from pageable memory is a synchronous
         one in disguise): numpy -> pinned (host memcpy) -> device (non-blocking on the current stream). One (pinned, device) pair per
-        PatchEmbed, grown on demand; the pinned buffer is rewritten only after the previous call's copy has drained (event)."""
-        n = int(image_bgr.size)
+        PatchEmbed, grown on demand; the pinned buffer is rewritten only after the previous call's copy has drained (event).
+        A list / tuple of equally shaped frames is copied frame by frame into consecutive slices of the pinned buffer (packed [B,H,W,3],
+        no stacked temporary)."""
+        frames = image_bgr if isinstance(image_bgr, (list, tuple)) else (image_bgr,)
+        n = sum(int(f.size) for f in frames)
         stages = self.__dict__.setdefault("_host_stage", {})
         key = (str(device), torch.cuda.current_stream(device).cuda_stream)  # per stream: the device buffer is reused in stream order
         st = stages.get(key)
@@ -237,7 +248,10 @@ class PatchEmbed(_Stage):
         if st["event"] is not None:
             st["event"].synchronize()
         pinned = st["pinned"][:n]
-        pinned.view(image_bgr.shape).numpy()[...] = image_bgr  # (handles non-contiguous views: numpy does the strided copy)
+        at = 0
+        for f in frames:
+            pinned[at:at + f.size].view(f.shape).numpy()[...] = f  # (handles non-contiguous views: numpy does the strided copy)
+            at += f.size
         dev = st["dev"][:n]
         dev.copy_(pinned, non_blocking=True)
         ev = torch.cuda.Event()
@@ -410,6 +424,37 @@ def native_config(cfg: dict, family: str, precision: int) -> "native.MdptConfig"
     c.precision = precision
     c.family = {"v2": native.FAMILY_DAV2, "v1": native.FAMILY_DAV1, "beit": native.FAMILY_BEIT, "swinv2": native.FAMILY_SWINV2}[family]
     return c
+
+
+def _check_frames(images_bgr):
+    """Argument checks of DPTModel.inference_batch (host-side only, nothing touches a GPU) -> (frames, on_device, (H, W)): frames is the
+    ndarray / list as given, or a contiguous [B,H,W,3] CUDA tensor."""
+    if isinstance(images_bgr, torch.Tensor):
+        if images_bgr.dtype != torch.uint8 or images_bgr.dim() != 4 or images_bgr.shape[3] != 3:
+            raise TypeError(f"inference_batch expects uint8 BxHxWx3 BGR frames, got a {images_bgr.dtype} tensor of shape {tuple(images_bgr.shape)}")
+        if images_bgr.shape[0] == 0:
+            raise ValueError("inference_batch got no frames")
+        if images_bgr.device.type != "cuda":
+            images_bgr = images_bgr.numpy()
+        else:
+            return images_bgr.contiguous(), True, tuple(images_bgr.shape[1:3])
+    if isinstance(images_bgr, np.ndarray):
+        if images_bgr.dtype != np.uint8 or images_bgr.ndim != 4 or images_bgr.shape[3] != 3:
+            raise TypeError(f"inference_batch expects uint8 BxHxWx3 BGR frames, got a {images_bgr.dtype} array of shape {images_bgr.shape}")
+        if images_bgr.shape[0] == 0:
+            raise ValueError("inference_batch got no frames")
+        return images_bgr, False, images_bgr.shape[1:3]
+    if not isinstance(images_bgr, (list, tuple)):
+        raise TypeError(f"inference_batch expects a uint8 [B,H,W,3] ndarray / CUDA tensor or a list of HxWx3 uint8 arrays, got {type(images_bgr)}")
+    if len(images_bgr) == 0:
+        raise ValueError("inference_batch got no frames")
+    for f in images_bgr:
+        if not (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3):
+            raise TypeError("inference_batch expects OpenCV-style uint8 HxWx3 BGR frames (cv2.imread output)")
+    shapes = {f.shape for f in images_bgr}
+    if len(shapes) != 1:
+        raise ValueError(f"inference_batch needs frames of one size, got {sorted(shapes)}")
+    return list(images_bgr), False, images_bgr[0].shape[0:2]
 
 
 class _Engine:
@@ -773,6 +818,43 @@ class DPTModel(nn.Module):
                 mean3, std3 = pe._norm_constants()
                 eng.call_checked("mdpt_forward_bgr", src, image_bgr.shape[0], image_bgr.shape[1], native.dtype_code(img_dtype), h, w, mean3, std3, interp,
                                  out, native.dtype_code(out.dtype), size_hw=(h, w), batch=1)
+            return out
+
+    def inference_batch(self, images_bgr, max_side_length: int | None = None, use_square_sizing: bool = True) -> Tensor:
+        """inference() for B frames of one size -> [B,H',W'] in the model dtype (not in the reference; its demos loop over frames). Takes a uint8
+        ndarray [B,H,W,3], a list / tuple of HxWx3 uint8 arrays of one shape, or a uint8 CUDA tensor [B,H,W,3] on the model's device (frames that
+        already live there skip the host staging). Same size rule, resize and inference_mode as inference(); row b equals
+        model(torch.cat([prepare_image_bgr(frame) for frame in frames]))[b] bit for bit, through one mdpt_forward_bgr_batch call."""
+        frames, on_device, (img_h, img_w) = _check_frames(images_bgr)
+        if img_h == 0 or img_w == 0:
+            raise ValueError(f"inference_batch got empty frames ({img_h}x{img_w})")
+        pe = self.patch_embed
+        p = next(self.parameters())
+        if p.device.type != "cuda":
+            raise RuntimeError("inference_batch runs on the GPU only (no CPU fallback): move the model to a cuda device first")
+        if on_device and frames.device != p.device:
+            raise RuntimeError(f"Expected all tensors to be on the same device, model is on {p.device} but the frames are on {frames.device}")
+        scaled_hw = pe._scaled_hw(img_h, img_w, max_side_length, use_square_sizing)
+        b = len(frames)
+        with torch.inference_mode():
+            probes = self.imgencoder.__dict__.get("_softmax_probes") or []
+            blocks = self.imgencoder.__dict__.get("_block_probes") or []
+            img_dtype = p.dtype if p.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
+            if img_dtype != p.dtype or any(len(pr._forward_hooks) > 0 for pr in probes) or any(len(node._forward_hooks) > 0 for node, _ in blocks):
+                # hooks listening: the stage-by-stage route of forward(), on the tensor prepare_image_bgr gives per frame
+                if on_device:
+                    x = torch.cat([pe._prepare_device(frames[i], img_h, img_w, scaled_hw, native.INTERP_BILINEAR, p, img_dtype) for i in range(b)])
+                else:
+                    x = torch.cat([pe.prepare_image(f, max_side_length, use_square_sizing) for f in frames])
+                return self(x)
+            eng = self._get_engine()
+            h, w = scaled_hw
+            with torch.cuda.device(p.device):
+                src = frames if on_device else pe._stage_host_image(frames, p.device)
+                out = torch.empty((b, h, w), device=p.device, dtype=eng.dtype)
+                mean3, std3 = pe._norm_constants()
+                eng.call_checked("mdpt_forward_bgr_batch", src, b, img_h, img_w, native.dtype_code(img_dtype), h, w, mean3, std3, native.INTERP_BILINEAR,
+                                 out, native.dtype_code(out.dtype), size_hw=(h, w), batch=b)
             return out
 
     def prepare_image_bgr(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True,

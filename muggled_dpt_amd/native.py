@@ -46,6 +46,7 @@ FAMILY_BEIT = 2
 FAMILY_SWINV2 = 3
 E_GRID = -7
 POST_F32, POST_U8, POST_U24 = 0, 1, 2
+POST_SEG_PARTS = 64  # MDPT_POST_SEG_PARTS
 INTERP_BILINEAR, INTERP_BICUBIC = 0, 1
 
 
@@ -188,9 +189,16 @@ SYMBOLS = {
     "mdpt_head": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_prepare_image": (ctypes.c_int, [_VP, _I, _I, _VP, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _I, _VP]),
     "mdpt_forward_bgr": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _I, _VP, _I, _VP, _SZ, _VP]),
+    "mdpt_forward_bgr_batch": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _I, _VP, _I, _VP, _SZ,
+                                              _VP]),
     "mdpt_post_minmax": (ctypes.c_int, [_VP, _SZ, _VP, _VP, _VP]),
     "mdpt_post_scale_prediction": (ctypes.c_int, [_VP, _I, _I, _I, _VP, _I, _I, _VP, _VP, _VP]),
     "mdpt_post_normalize": (ctypes.c_int, [_VP, _SZ, _VP, _VP, _I, _I, _VP]),
+    "mdpt_post_minmax_seg": (ctypes.c_int, [_VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _VP, _VP]),
+    "mdpt_post_u8_hist_seg": (ctypes.c_int, [_VP, _I, _I, _SZ, _VP, _I, _VP, _VP, _VP]),
+    "mdpt_post_histogram": (ctypes.c_int, [_VP, _I, _SZ, _VP, _VP]),
+    "mdpt_post_equalize_lut": (ctypes.c_int, [_VP, _I, _VP, _I, _I, _VP, _VP]),
+    "mdpt_post_colorize": (ctypes.c_int, [_VP, _I, _SZ, _VP, _VP, _I, _VP, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

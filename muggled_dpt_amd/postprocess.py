@@ -1,5 +1,7 @@
 """Depth post-processing on the GPU: drop-in for the tensor helpers of the reference's muggled_dpt/demo_helpers/postprocess.py
-(scale_prediction :22-29, normalize_01 :63-74, convert_to_uint8 :79-91) plus the 24-bit packing step of run_3dviewer.py:576-590.
+(scale_prediction :22-29, normalize_01 :63-74, convert_to_uint8 :79-91) plus the 24-bit packing step of run_3dviewer.py:576-590, and the
+display tail of its video / image demos per image (histogram_equalization :107-145, the colormap LUT of toadui/colormaps.py:237-259, and
+depth_to_color, the whole per-frame loop of run_video.py:348-361 over a batch).
 
 Every function takes the CUDA tensor the model returned and launches HIP kernels (libmdpt: mdpt_post_*) on the current torch
 stream; results stay on the device (the reference's convert_to_uint8 does the same, postprocess.py:85-87). min / max never visit
@@ -8,6 +10,9 @@ the host. There is no CPU implementation here: host arrays raise (numpy callers 
 
 from __future__ import annotations
 
+import functools
+
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -99,3 +104,130 @@ def remove_inf_tensor(data: Tensor, inf_replacement_value: float = 0.0, in_place
     data = data if in_place else data.clone()
     data[data.isinf()] = inf_replacement_value
     return data
+
+
+# ---- per-image display tail
+
+
+def _dev_u8(t, what: str) -> Tensor:
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise RuntimeError(f"{what}: expected a CUDA tensor (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+    if t.dtype != torch.uint8 or t.dim() not in (2, 3) or t.numel() == 0:
+        raise TypeError(f"{what}: expected a uint8 HxW or BxHxW tensor, got {t.dtype} {tuple(t.shape)}")
+    return t.detach().contiguous()
+
+
+def equalization_range(min_pct: float = 0.0, max_pct: float = 1.0) -> tuple[int, int]:
+    """The reference's (min_value, max_value) of histogram_equalization (postprocess.py:124-126); (0, 255) is the cv2.equalizeHist branch."""
+    min_value, max_value = [int(round(255 * value)) for value in sorted((min_pct, max_pct))]
+    max_value = max(max_value, min_value + 1)
+    if min_value < 0 or max_value > 255:  # (the reference's np.zeros / np.full fail on these)
+        raise ValueError(f"histogram_equalization range {min_pct}, {max_pct} gives values [{min_value}, {max_value}] outside 0..255")
+    return min_value, max_value
+
+
+@functools.lru_cache(maxsize=64)
+def threshold_bin_table(min_value: int, max_value: int) -> np.ndarray:
+    """value -> bin of np.histogram(x, 1 + max_value - min_value, range=(min_value, max_value)) for the 256 uint8 values (-1: not counted).
+    The bins are not unit wide, so the table is taken from numpy itself, one value at a time, and handed to the LUT kernel."""
+    nbins = 1 + max_value - min_value
+    table = np.full(256, -1, dtype=np.int32)
+    for v in range(256):
+        counts, _ = np.histogram(np.array([v], dtype=np.uint8), nbins, range=(min_value, max_value))
+        hit = np.flatnonzero(counts)
+        if hit.size:
+            table[v] = hit[0]
+    table.setflags(write=False)
+    return table
+
+
+def _equalize_lut(x3: Tensor, min_pct: float, max_pct: float) -> Tensor:
+    """[B,256] equalization LUTs of a uint8 [B,H,W] batch, one per image."""
+    vmin, vmax = equalization_range(min_pct, max_pct)
+    b = x3.shape[0]
+    hist = torch.zeros((b, 256), device=x3.device, dtype=torch.int32)
+    _launch(x3.device, "mdpt_post_histogram", x3.data_ptr(), b, x3[0].numel(), hist.data_ptr())
+    table = None
+    if (vmin, vmax) != (0, 255):
+        table = torch.from_numpy(threshold_bin_table(vmin, vmax).copy()).to(x3.device)
+    lut = torch.empty((b, 256), device=x3.device, dtype=torch.uint8)
+    _launch(x3.device, "mdpt_post_equalize_lut", hist.data_ptr(), b, None if table is None else table.data_ptr(), vmin, vmax, lut.data_ptr())
+    return lut
+
+
+def histogram_equalization(depth_uint8: Tensor, min_pct: float = 0.0, max_pct: float = 1.0) -> Tensor:
+    """uint8 [H,W] or [B,H,W] on the device -> same shape, every image equalized on its own (postprocess.py:107-145): cv2.equalizeHist for the
+    full range, the np.histogram branch otherwise. One histogram pass, one LUT launch, one apply pass; nothing visits the host."""
+    x = _dev_u8(depth_uint8, "histogram_equalization")
+    x3 = x if x.dim() == 3 else x[None]
+    lut = _equalize_lut(x3, min_pct, max_pct)
+    out = torch.empty_like(x3)
+    _launch(x.device, "mdpt_post_colorize", x3.data_ptr(), x3.shape[0], x3[0].numel(), lut.data_ptr(), None, 1, out.data_ptr())
+    return out.view(x.shape)
+
+
+def _cmap_tensor(lut, device) -> Tensor | None:
+    if lut is None:
+        return None
+    if isinstance(lut, np.ndarray):
+        if lut.dtype != np.uint8 or lut.size != 256 * 3:
+            raise TypeError(f"colormap LUT must be a uint8 1x256x3 array, got {lut.dtype} {lut.shape}")
+        return torch.from_numpy(np.ascontiguousarray(lut).reshape(256, 3)).to(device)
+    if isinstance(lut, torch.Tensor):
+        if lut.dtype != torch.uint8 or lut.numel() != 256 * 3:
+            raise TypeError(f"colormap LUT must be a uint8 1x256x3 tensor, got {lut.dtype} {tuple(lut.shape)}")
+        return lut.detach().to(device).contiguous().reshape(256, 3)
+    raise TypeError(f"Error applying colormap, unrecognized colormap type: {type(lut)}")
+
+
+def apply_colormap(depth_uint8: Tensor, lut=None) -> Tensor:
+    """uint8 [H,W] or [B,H,W] -> uint8 [...,H,W,3] BGR through a 1x256x3 BGR LUT (ndarray or tensor), or gray when lut is None:
+    cv2.LUT(cv2.cvtColor(x, GRAY2BGR), lut) (toadui/colormaps.py:237-259)."""
+    x = _dev_u8(depth_uint8, "apply_colormap")
+    cmap = _cmap_tensor(lut, x.device)
+    x3 = x if x.dim() == 3 else x[None]
+    out = torch.empty((*x.shape, 3), device=x.device, dtype=torch.uint8)
+    _launch(x.device, "mdpt_post_colorize", x3.data_ptr(), x3.shape[0], x3[0].numel(), None, None if cmap is None else cmap.data_ptr(), 3, out.data_ptr())
+    return out
+
+
+def depth_to_color(prediction: Tensor, target_wh: tuple[int, int] | None = None, reverse: bool = False, high_contrast: bool = False,
+                   lut=None) -> Tensor:
+    """[B,h,w] depth prediction -> uint8 [B,H,W,3] BGR display frames, the per-frame loop of run_video.py:348-361 for every image at once:
+    scale_prediction (target_wh given) -> convert_to_uint8 -> 255 - x (reverse) -> histogram_equalization (high_contrast) -> colormap (lut; gray
+    when None). Image b's frame equals that composition on prediction[b:b+1] bit for bit (its own min / max and histogram). Four launches at
+    most: resize + per-image min/max (also clears the histogram), uint8 + histogram, LUT, equalize-and-colormap as one lookup."""
+    if not isinstance(prediction, torch.Tensor) or prediction.device.type != "cuda":
+        raise RuntimeError("depth_to_color: expected a CUDA tensor (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+    x = prediction.detach()
+    if x.dim() == 2:
+        x = x[None]
+    if x.dim() != 3 or x.numel() == 0:
+        raise RuntimeError(f"depth_to_color expects BxHxW, got {tuple(prediction.shape)}")
+    if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        x = x.to(torch.float32)
+    x = x.contiguous()
+    dev = x.device
+    cmap = _cmap_tensor(lut, dev)
+    b, h, w = x.shape
+    dt = native.dtype_code(x.dtype)
+    scaled = None
+    oh, ow = h, w
+    if target_wh is not None:
+        oh, ow = int(target_wh[1]), int(target_wh[0])
+        scaled = torch.empty((b, oh, ow), device=dev, dtype=torch.float32)
+    parts = torch.empty((b, native.POST_SEG_PARTS, 2), device=dev, dtype=torch.int32)
+    hist = torch.empty((b, 256), device=dev, dtype=torch.int32) if high_contrast else None
+    hist_ptr = None if hist is None else hist.data_ptr()
+    _launch(dev, "mdpt_post_minmax_seg", x.data_ptr(), dt, b, h, w, None if scaled is None else scaled.data_ptr(), oh, ow, parts.data_ptr(), hist_ptr)
+    n = oh * ow
+    u8 = torch.empty((b, oh, ow), device=dev, dtype=torch.uint8)
+    src, src_dt = (x, dt) if scaled is None else (scaled, native.DTYPE_F32)
+    _launch(dev, "mdpt_post_u8_hist_seg", src.data_ptr(), src_dt, b, n, parts.data_ptr(), int(bool(reverse)), u8.data_ptr(), hist_ptr)
+    eq = None
+    if high_contrast:
+        eq = torch.empty((b, 256), device=dev, dtype=torch.uint8)
+        _launch(dev, "mdpt_post_equalize_lut", hist.data_ptr(), b, None, 0, 255, eq.data_ptr())
+    out = torch.empty((b, oh, ow, 3), device=dev, dtype=torch.uint8)
+    _launch(dev, "mdpt_post_colorize", u8.data_ptr(), b, n, None if eq is None else eq.data_ptr(), None if cmap is None else cmap.data_ptr(), 3, out.data_ptr())
+    return out
