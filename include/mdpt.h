@@ -289,6 +289,16 @@ int mdpt_forward_bgr_batch(mdpt_handle* h, const void* bgr_u8_bhwc, int32_t B, i
                            const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw, int32_t depth_dtype, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* mdpt_forward_bgr_batch for B frames of ANY sizes (DPTModel.inference_images; additive to ABI v6): frame b is uint8 [frames_hw[2b],
+ * frames_hw[2b+1], 3] BGR at device pointer frames_u8_hwc[b]; every frame is resized to the one model tensor size H x W -> depth [B,H,W]. The
+ * host arrays are read during the call only. The im2col kernel takes its frame table by value (64 frames per launch): nothing is
+ * allocated or copied to the device, the call never synchronises and stays graph-capturable. Image b's map equals mdpt_prepare_image(frame b),
+ * stacked, then mdpt_forward of the batch, bit for bit, in every family, dtype and arithmetic mode; a batch at or above the split size runs as
+ * two halves, the second from table entry B0. Errors as mdpt_forward_bgr_batch. Workspace as for mdpt_forward(B). */
+int mdpt_forward_bgr_frames(mdpt_handle* h, const void* const* frames_u8_hwc, const int32_t* frames_hw, int32_t B, int32_t image_dtype, int32_t H, int32_t W,
+                            const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw, int32_t depth_dtype, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* Depth post-processing on the device (reference muggled_dpt/demo_helpers/postprocess.py and
  * run_3dviewer.py:576-590). All buffers are device pointers; `minmax` is a 2-float device buffer {min, max} and
  * `scratch8` 8 bytes of device scratch - nothing is read back to the host, nothing synchronises.
@@ -334,6 +344,21 @@ int mdpt_post_u8_hist_seg(const void* in_bhw, int32_t in_dtype, int32_t B, size_
 int mdpt_post_histogram(const void* in_u8, int32_t B, size_t count, void* hist, void* stream);
 int mdpt_post_equalize_lut(const void* hist, int32_t B, const void* bin_of_value, int32_t min_value, int32_t max_value, void* lut_out, void* stream);
 int mdpt_post_colorize(const void* in_u8, int32_t B, size_t count, const void* eq_lut, const void* cmap_bgr, int32_t channels, void* out, void* stream);
+
+/* The same display tail for B images of DIFFERENT sizes (postprocess.scale_prediction_images / depth_to_color_images; additive to ABI v6).
+ * Image i is in[i] (device pointer) of hw[2i] x hw[2i+1] elements; outputs are packed in image order (image i's output starts where image
+ * i-1's ends). parts / hist / eq_lut are [B, ...] as above. The host arrays are read during the call only; every kernel takes its image table
+ * by value, so each of the three is one launch per 32 images, and image i's result equals the uniform entry point on image i
+ * alone, bit for bit:
+ *   mdpt_post_minmax_images .... mdpt_post_minmax_seg per image; out_f32 != NULL: image i resized to out_hw[2i] x out_hw[2i+1] into out_f32
+ *   mdpt_post_u8_hist_images ... mdpt_post_u8_hist_seg per image (in[i]: the map mdpt_post_minmax_images measured, hw its size)
+ *   mdpt_post_colorize_images .. mdpt_post_colorize per image of a packed uint8 input (in_u8), hw the images' sizes */
+int mdpt_post_minmax_images(const void* const* in, const int32_t* in_hw, int32_t in_dtype, int32_t B, void* out_f32, const int32_t* out_hw, void* parts,
+                            void* hist_clear, void* stream);
+int mdpt_post_u8_hist_images(const void* const* in, const int32_t* hw, int32_t in_dtype, int32_t B, const void* parts, int32_t reverse, void* out_u8,
+                             void* hist, void* stream);
+int mdpt_post_colorize_images(const void* in_u8, const int32_t* hw, int32_t B, const void* eq_lut, const void* cmap_bgr, int32_t channels, void* out,
+                              void* stream);
 
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */

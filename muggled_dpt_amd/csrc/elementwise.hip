@@ -681,17 +681,21 @@ __global__ __launch_bounds__(256) void prepare_image_kernel(const unsigned char*
 // of the model tensor, computed from the uint8 image as above, rounded to the dtype the stand-alone kernel would have written it in (img_dt: the
 // values - and so every bit behind them - equal mdpt_prepare_image + patchify_kernel) and stored straight into its three places of the patch
 // embedding's im2col rows (k = c P^2 + ky P + kx). The normalised image never exists in memory. The first pixel of a patch also zeroes its
-// row's padding columns [3 P^2, Kp). Batched (mdpt_forward_bgr_batch): blockIdx.y = image b reads frame b of the packed [B,ih,iw,3] source and
-// writes rows b gh gw + py gw + px, the row layout of patchify_kernel.
+// row's padding columns [3 P^2, Kp). Batched (mdpt_forward_bgr_batch / _frames): blockIdx.y = frame b of the launch's frame table, read from its
+// run's source with that run's own size (ih, iw), writes rows b gh gw + py gw + px, the row layout of patchify_kernel.
 template <int INTERP>
-__global__ __launch_bounds__(256) void prepare_patchify_kernel(const unsigned char* __restrict__ bgr, int img_dt, op_t* out_hi, op_t* out_lo, int ih, int iw,
-                                                               int H, int W, int P, int Kp, float m0, float m1, float m2, float s0, float s1, float s2) {
+__global__ __launch_bounds__(256) void prepare_patchify_kernel(const BgrRunTable t, int img_dt, op_t* out_hi, op_t* out_lo, int H, int W, int P, int Kp,
+                                                               float m0, float m1, float m2, float s0, float s1, float s2) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
     const int b = blockIdx.y;
+    int r = 0, j = b;  // frame b = frame j of run r (a block-uniform walk over the table; the grid holds exactly the table's frames)
+    while (r < t.n - 1 && j >= t.run[r].count) j -= t.run[r++].count;
+    const unsigned char* bgr = t.run[r].ptr;
+    const int ih = t.run[r].ih, iw = t.run[r].iw;
     const int ox = idx % W, oy = idx / W;
     float v[3];
-    aa_pixel_rgb<INTERP>(bgr + (size_t)b * ih * iw * 3, ih, iw, H, W, oy, ox, m0, m1, m2, s0, s1, s2, v[0], v[1], v[2]);
+    aa_pixel_rgb<INTERP>(bgr + (size_t)j * ih * iw * 3, ih, iw, H, W, oy, ox, m0, m1, m2, s0, s1, s2, v[0], v[1], v[2]);
     const int py = oy / P, ky = oy - py * P, px = ox / P, kx = ox - px * P;
     const size_t row = ((size_t)b * (H / P) * (W / P) + (size_t)py * (W / P) + px) * Kp;
 #pragma unroll
@@ -1137,17 +1141,22 @@ int MDPT_FN(mdpt_launch_prepare_image)(const unsigned char* bgr, void* out, int 
     LAUNCH_RET();
 }
 
-int MDPT_FN(mdpt_launch_prepare_patchify)(const unsigned char* bgr, int img_dtype, op_t* out_hi, op_t* out_lo, int B, int ih, int iw, int H, int W, int P, int Kp,
+int MDPT_FN(mdpt_launch_prepare_patchify)(const BgrRunTable& t, int img_dtype, op_t* out_hi, op_t* out_lo, int H, int W, int P, int Kp,
                                          const float mean[3], const float inv_std[3], int interp, hipStream_t stream) {
-    if (B <= 0 || B > 65535 || ih <= 0 || iw <= 0 || H <= 0 || W <= 0 || P <= 0 || (H % P) || (W % P) || Kp < 3 * P * P || (interp != 0 && interp != 1) ||
+    if (t.n <= 0 || t.n > MDPT_BGR_RUNS || H <= 0 || W <= 0 || P <= 0 || (H % P) || (W % P) || Kp < 3 * P * P || (interp != 0 && interp != 1) ||
         img_dtype < MDPT_DT_F32 || img_dtype > MDPT_DT_F16)
         return (int)hipErrorInvalidValue;
+    int B = 0;
+    for (int r = 0; r < t.n; ++r) {
+        if (!t.run[r].ptr || t.run[r].ih <= 0 || t.run[r].iw <= 0 || t.run[r].count <= 0 || t.run[r].count > 65535 - B) return (int)hipErrorInvalidValue;
+        B += t.run[r].count;
+    }
     MdptProfScope prof("prepare_patchify_kernel", 0.0, stream);
     if (interp == 0)
-        hipLaunchKernelGGL(prepare_patchify_kernel<0>, dim3((H * W + 255) / 256, B), dim3(256), 0, stream, bgr, img_dtype, out_hi, out_lo, ih, iw, H, W, P, Kp, mean[0], mean[1],
+        hipLaunchKernelGGL(prepare_patchify_kernel<0>, dim3((H * W + 255) / 256, B), dim3(256), 0, stream, t, img_dtype, out_hi, out_lo, H, W, P, Kp, mean[0], mean[1],
                            mean[2], inv_std[0], inv_std[1], inv_std[2]);
     else
-        hipLaunchKernelGGL(prepare_patchify_kernel<1>, dim3((H * W + 255) / 256, B), dim3(256), 0, stream, bgr, img_dtype, out_hi, out_lo, ih, iw, H, W, P, Kp, mean[0], mean[1],
+        hipLaunchKernelGGL(prepare_patchify_kernel<1>, dim3((H * W + 255) / 256, B), dim3(256), 0, stream, t, img_dtype, out_hi, out_lo, H, W, P, Kp, mean[0], mean[1],
                            mean[2], inv_std[0], inv_std[1], inv_std[2]);
     LAUNCH_RET();
 }

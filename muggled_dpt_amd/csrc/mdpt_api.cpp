@@ -429,8 +429,9 @@ static int ensure_side_stream(mdpt_handle* h, hipStream_t s0, void* scratch) {
 
 static inline size_t dtype_bytes(int dt) { return dt == MDPT_DTYPE_F32 ? 4 : 2; }
 
-// mdpt_forward and mdpt_forward_bgr_batch: the source is either an image tensor (image_bchw) or, when bgr != NULL, B packed uint8 frames the
-// im2col kernel reads itself (image_bchw is NULL then; the split's second half starts B0 frames into them, as it starts B0 images into the tensor)
+// mdpt_forward and mdpt_forward_bgr_batch / _frames: the source is either an image tensor (image_bchw) or, when bgr != NULL, B uint8 frames the
+// im2col kernel reads itself (image_bchw is NULL then; the split's second half starts B0 frames into them - or at entry B0 of a per-frame
+// table - as it starts B0 images into the tensor)
 static int forward_batch(mdpt_handle* h, const void* image_bchw, const Ctx::BgrSource* bgr, int32_t image_dtype, int32_t B, int32_t H, int32_t W,
                          void* depth_bhw, int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
     if (h->split_min > 0 && B >= h->split_min && B >= 2 && h->dbg_block < 0) {
@@ -456,7 +457,12 @@ static int forward_batch(mdpt_handle* h, const void* image_bchw, const Ctx::BgrS
         if (bgr) {
             c0.bgr = *bgr;
             c1.bgr = *bgr;
-            c1.bgr.ptr += (size_t)B0 * bgr->ih * bgr->iw * 3;
+            if (bgr->frames) {
+                c1.bgr.frames += B0;  // (table entry B0 on)
+                c1.bgr.frames_hw += 2 * B0;
+            } else {
+                c1.bgr.ptr += (size_t)B0 * bgr->ih * bgr->iw * 3;
+            }
         }
         // Whatever happens after the fork, the side stream is joined back into the caller's stream before returning: kernels already
         // queued there keep using the second half of the workspace and the caller's tensors, which the caller may free or reuse on its
@@ -504,6 +510,26 @@ int mdpt_forward_bgr_batch(mdpt_handle* h, const void* bgr_u8_bhwc, int32_t B, i
     if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);  // (the im2col kernel's grid y is the frame index)
     Ctx::BgrSource src;
     src.ptr = (const unsigned char*)bgr_u8_bhwc; src.ih = in_h; src.iw = in_w; src.round_dtype = image_dtype; src.interp = interpolation;
+    for (int i = 0; i < 3; ++i) { src.mean[i] = rgb_mean[i]; src.inv_std[i] = 1.0f / rgb_std[i]; }  // patch_embed.py:38-39,62
+    return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
+}
+
+// ---- the same for B frames of any sizes, each its own device pointer, all resized to one model tensor size (DPTModel.inference_images)
+int mdpt_forward_bgr_frames(mdpt_handle* h, const void* const* frames_u8_hwc, const int32_t* frames_hw, int32_t B, int32_t image_dtype, int32_t H, int32_t W,
+                            const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw, int32_t depth_dtype, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    if (!h || !frames_u8_hwc || !frames_hw || !depth_bhw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
+    for (int dt : {image_dtype, depth_dtype})
+        if (dt != MDPT_DTYPE_F32 && dt != MDPT_DTYPE_BF16 && dt != MDPT_DTYPE_F16) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
+    if (interpolation != MDPT_INTERP_BILINEAR && interpolation != MDPT_INTERP_BICUBIC)
+        return fail(MDPT_E_UNSUPPORTED, "interpolation %d: antialiased resize exists for bilinear and bicubic only (as in torch)", interpolation);
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    for (int b = 0; b < B; ++b) {
+        if (!frames_u8_hwc[b]) return fail(MDPT_E_INVALID, "null argument (frame %d)", b);
+        if (frames_hw[2 * b] <= 0 || frames_hw[2 * b + 1] <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d (frame %d)", frames_hw[2 * b], frames_hw[2 * b + 1], b);
+    }
+    Ctx::BgrSource src;
+    src.frames = frames_u8_hwc; src.frames_hw = frames_hw; src.round_dtype = image_dtype; src.interp = interpolation;
     for (int i = 0; i < 3; ++i) { src.mean[i] = rgb_mean[i]; src.inv_std[i] = 1.0f / rgb_std[i]; }  // patch_embed.py:38-39,62
     return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
 }
@@ -914,14 +940,30 @@ int mdpt_post_normalize(const void* in_f32, size_t count, const void* minmax, vo
 // ---- per-image display tail (run_video.py:348-361 per frame, over a batch; demo_helpers/postprocess.py:107-145, toadui/colormaps.py:237-259)
 static bool post_dtype_ok(int dt) { return dt == MDPT_DTYPE_F32 || dt == MDPT_DTYPE_BF16 || dt == MDPT_DTYPE_F16; }
 
+// the one-run image table of a uniform batch: B images of ih x iw (-> oh x ow) packed from `in`, outputs packed from element 0
+static PostRunTable uniform_table(const void* in, int B, int ih, int iw, int oh, int ow) {
+    PostRunTable t{};
+    t.n = 1;
+    t.run[0] = PostRun{in, 0, ih, iw, oh, ow, B};
+    return t;
+}
+
+// a uint8 / map count as the ih x iw of one table entry (1 x count)
+static bool count_as_hw(size_t count, int& ih, int& iw) {
+    if (count == 0 || count > (size_t)INT32_MAX) return false;
+    ih = 1;
+    iw = (int)count;
+    return true;
+}
+
 int mdpt_post_minmax_seg(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t in_h, int32_t in_w, void* out_bhw_f32, int32_t out_h, int32_t out_w,
                          void* parts, void* hist_clear, void* stream) {
     if (!in_bhw || !parts) return fail(MDPT_E_INVALID, "null argument");
     if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
     if (B <= 0 || B > 65535 || in_h <= 0 || in_w <= 0 || (out_bhw_f32 && (out_h <= 0 || out_w <= 0)))
         return fail(MDPT_E_INVALID, "bad size %dx%dx%d -> %dx%d", B, in_h, in_w, out_h, out_w);
-    CHK(mdpt_launch_post_seg_minmax(in_bhw, in_dtype, B, in_h, in_w, (float*)out_bhw_f32, out_h, out_w, (unsigned*)parts, (unsigned*)hist_clear,
-                                    (hipStream_t)stream));
+    const PostRunTable t = uniform_table(in_bhw, B, in_h, in_w, out_bhw_f32 ? out_h : in_h, out_bhw_f32 ? out_w : in_w);
+    CHK(mdpt_launch_post_seg_minmax(t, in_dtype, (float*)out_bhw_f32, (unsigned*)parts, (unsigned*)hist_clear, (hipStream_t)stream));
     return 0;
 }
 
@@ -930,8 +972,10 @@ int mdpt_post_u8_hist_seg(const void* in_bhw, int32_t in_dtype, int32_t B, size_
     if (!in_bhw || !parts || !out_u8 || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
     if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
     if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
-    CHK(mdpt_launch_post_seg_u8(in_bhw, in_dtype, B, count, (const unsigned*)parts, reverse != 0, (unsigned char*)out_u8, (unsigned*)hist,
-                                (hipStream_t)stream));
+    int ih, iw;
+    if (!count_as_hw(count, ih, iw)) return fail(MDPT_E_INVALID, "bad image size %zu", count);
+    CHK(mdpt_launch_post_seg_u8(uniform_table(in_bhw, B, ih, iw, ih, iw), in_dtype, (const unsigned*)parts, reverse != 0, (unsigned char*)out_u8,
+                                (unsigned*)hist, (hipStream_t)stream));
     return 0;
 }
 
@@ -955,8 +999,82 @@ int mdpt_post_colorize(const void* in_u8, int32_t B, size_t count, const void* e
     if (!in_u8 || !out || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
     if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
     if (channels != 1 && channels != 3) return fail(MDPT_E_INVALID, "channels must be 1 or 3, got %d", channels);
-    CHK(mdpt_launch_post_colorize((const unsigned char*)in_u8, B, count, (const unsigned char*)eq_lut, (const unsigned char*)cmap_bgr, channels,
+    int ih, iw;
+    if (!count_as_hw(count, ih, iw)) return fail(MDPT_E_INVALID, "bad image size %zu", count);
+    CHK(mdpt_launch_post_colorize(uniform_table(in_u8, B, ih, iw, ih, iw), (const unsigned char*)eq_lut, (const unsigned char*)cmap_bgr, channels,
                                   (unsigned char*)out, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- the same for images of different sizes: one run per image, MDPT_POST_RUNS images per launch; per-image buffers advance by the images before
+static int check_images(const void* const* in, const int32_t* hw, int32_t B, const char* what) {
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    for (int i = 0; i < B; ++i) {
+        if (in && !in[i]) return fail(MDPT_E_INVALID, "null argument (%s %d)", what, i);
+        if (hw[2 * i] <= 0 || hw[2 * i + 1] <= 0) return fail(MDPT_E_INVALID, "bad %s size %dx%d (image %d)", what, hw[2 * i], hw[2 * i + 1], i);
+    }
+    return 0;
+}
+
+int mdpt_post_minmax_images(const void* const* in, const int32_t* in_hw, int32_t in_dtype, int32_t B, void* out_f32, const int32_t* out_hw, void* parts,
+                            void* hist_clear, void* stream) {
+    if (!in || !in_hw || !parts || (out_f32 && !out_hw)) return fail(MDPT_E_INVALID, "null argument");
+    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
+    CHK(check_images(in, in_hw, B, "input"));
+    if (out_f32) CHK(check_images(nullptr, out_hw, B, "output"));
+    const int32_t* ohw = out_f32 ? out_hw : in_hw;
+    size_t off = 0;
+    for (int b0 = 0; b0 < B; b0 += MDPT_POST_RUNS) {
+        PostRunTable t{};
+        t.n = B - b0 < MDPT_POST_RUNS ? B - b0 : MDPT_POST_RUNS;
+        for (int r = 0; r < t.n; ++r) {
+            const int i = b0 + r;
+            t.run[r] = PostRun{in[i], off, in_hw[2 * i], in_hw[2 * i + 1], ohw[2 * i], ohw[2 * i + 1], 1};
+            off += (size_t)ohw[2 * i] * ohw[2 * i + 1];
+        }
+        CHK(mdpt_launch_post_seg_minmax(t, in_dtype, (float*)out_f32, (unsigned*)parts + (size_t)b0 * MDPT_POST_SEG_PARTS * 2,
+                                        hist_clear ? (unsigned*)hist_clear + (size_t)b0 * 256 : nullptr, (hipStream_t)stream));
+    }
+    return 0;
+}
+
+int mdpt_post_u8_hist_images(const void* const* in, const int32_t* hw, int32_t in_dtype, int32_t B, const void* parts, int32_t reverse, void* out_u8,
+                             void* hist, void* stream) {
+    if (!in || !hw || !parts || !out_u8) return fail(MDPT_E_INVALID, "null argument");
+    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
+    CHK(check_images(in, hw, B, "input"));
+    size_t off = 0;
+    for (int b0 = 0; b0 < B; b0 += MDPT_POST_RUNS) {
+        PostRunTable t{};
+        t.n = B - b0 < MDPT_POST_RUNS ? B - b0 : MDPT_POST_RUNS;
+        for (int r = 0; r < t.n; ++r) {
+            const int i = b0 + r;
+            t.run[r] = PostRun{in[i], off, hw[2 * i], hw[2 * i + 1], hw[2 * i], hw[2 * i + 1], 1};
+            off += (size_t)hw[2 * i] * hw[2 * i + 1];
+        }
+        CHK(mdpt_launch_post_seg_u8(t, in_dtype, (const unsigned*)parts + (size_t)b0 * MDPT_POST_SEG_PARTS * 2, reverse != 0, (unsigned char*)out_u8,
+                                    hist ? (unsigned*)hist + (size_t)b0 * 256 : nullptr, (hipStream_t)stream));
+    }
+    return 0;
+}
+
+int mdpt_post_colorize_images(const void* in_u8, const int32_t* hw, int32_t B, const void* eq_lut, const void* cmap_bgr, int32_t channels, void* out,
+                              void* stream) {
+    if (!in_u8 || !hw || !out) return fail(MDPT_E_INVALID, "null argument");
+    if (channels != 1 && channels != 3) return fail(MDPT_E_INVALID, "channels must be 1 or 3, got %d", channels);
+    CHK(check_images(nullptr, hw, B, "input"));
+    size_t off = 0;
+    for (int b0 = 0; b0 < B; b0 += MDPT_POST_RUNS) {
+        PostRunTable t{};
+        t.n = B - b0 < MDPT_POST_RUNS ? B - b0 : MDPT_POST_RUNS;
+        for (int r = 0; r < t.n; ++r) {
+            const int i = b0 + r;
+            t.run[r] = PostRun{(const unsigned char*)in_u8 + off, off, hw[2 * i], hw[2 * i + 1], hw[2 * i], hw[2 * i + 1], 1};
+            off += (size_t)hw[2 * i] * hw[2 * i + 1];
+        }
+        CHK(mdpt_launch_post_colorize(t, eq_lut ? (const unsigned char*)eq_lut + (size_t)b0 * 256 : nullptr, (const unsigned char*)cmap_bgr, channels,
+                                      (unsigned char*)out, (hipStream_t)stream));
+    }
     return 0;
 }
 

@@ -300,7 +300,13 @@ struct Ctx {
     unsigned* poison = nullptr;  // mdpt_forward with non-finite propagation on: the plan's per-image words, cleared, for the im2col kernel to set
     bool consts_cached = false;  // the per-grid constants of this (workspace, shape) are in place (mdpt_set_grid_cache): skip the kernels that write them
     // mdpt_forward_bgr: the patch embedding's im2col kernel builds its rows from this uint8 BGR image (resize + normalise fused in) instead of an image tensor
-    struct BgrSource { const unsigned char* ptr = nullptr; int ih = 0, iw = 0, round_dtype = 0, interp = 0; float mean[3] = {0, 0, 0}, inv_std[3] = {1, 1, 1}; } bgr;
+    // uint8 BGR source of the fused im2col (mdpt_forward_bgr[_batch|_frames]): B packed frames of one size (ptr, ih, iw), or the caller's host table
+    // of per-frame pointers and sizes (frames, frames_hw = h0,w0,h1,w1,...; read only during the call), frame b of this Ctx at entry b
+    struct BgrSource {
+        const unsigned char* ptr = nullptr; int ih = 0, iw = 0, round_dtype = 0, interp = 0; float mean[3] = {0, 0, 0}, inv_std[3] = {1, 1, 1};
+        const void* const* frames = nullptr; const int32_t* frames_hw = nullptr;
+        bool active() const { return ptr || frames; }
+    } bgr;
     void* const* attn_dump = nullptr;  // per block: where to write softmax(q k^T) as fp32 [B,H,N,N] (null entries: skip)
     void* const* block_dump = nullptr; // per block: where to write the block's output tokens as fp32 [B,N,F] (null entries: skip)
     template <class T> T* at(size_t off) const { return off == SIZE_MAX ? nullptr : (T*)(ws + off); }

@@ -177,6 +177,22 @@ struct HeadTailParams {
 // ------------------------------------------------------------------------------------------------
 // SwinV2 helpers (swin.hip)
 // ------------------------------------------------------------------------------------------------
+// frame table of the fused resize + normalise + im2col kernel (prepare_patchify_kernel), passed BY VALUE as a kernel argument (nothing is
+// copied to the device, so a forward from uint8 frames stays graph-capturable): run r holds `count` packed uint8 [ih,iw,3] frames from `ptr`.
+// The frames of a launch are the runs' frames in order (blockIdx.y = frame); one size for the whole batch is one run, a list of frames of
+// different sizes is one run per frame. 64 runs = 1.5 KB of kernel arguments.
+#define MDPT_BGR_RUNS 64
+struct BgrRun { const unsigned char* ptr; int ih, iw, count; };
+struct BgrRunTable { BgrRun run[MDPT_BGR_RUNS]; int n; };
+
+// image table of the per-image display tail (postprocess.hip seg_* and colorize kernels), by value like BgrRunTable: run r holds `count`
+// packed images of ih x iw elements from `in` (image j at in + j ih iw) whose outputs are oh x ow (the resize target; = ih x iw for the
+// kernels that do not resize) and start at element `off` of the packed output (image j at off + j oh ow). The images of a launch are the
+// runs' images in order (blockIdx.y = image); a uniform batch is one run.
+#define MDPT_POST_RUNS 32
+struct PostRun { const void* in; size_t off; int ih, iw, oh, ow, count; };
+struct PostRunTable { PostRun run[MDPT_POST_RUNS]; int n; };
+
 // the same for every block of the encoder in ONE launch (the LUTs depend on weights and window sizes only, not on activations)
 struct SwinCpbBatch {
     const float* w1[32]; const float* b1[32]; const float* w2[32]; float* lut[32];
@@ -192,14 +208,14 @@ int mdpt_launch_post_scale(const float* in, float* out, int B, int ih, int iw, i
                            unsigned* scratch2, hipStream_t stream);
 int mdpt_launch_post_normalize(const float* in, const float* minmax, void* out, size_t n, int mode, int lossy,
                                hipStream_t stream);
-// per-image display tail: parts = [B, MDPT_POST_SEG_PARTS, 2] ordered {min, max} partials, hist / hist_clear = [B, 256] counts, lut = [B, 256]
-int mdpt_launch_post_seg_minmax(const void* in, int in_dt, int B, int ih, int iw, float* out, int oh, int ow, unsigned* parts, unsigned* hist_clear,
-                                hipStream_t stream);
-int mdpt_launch_post_seg_u8(const void* in, int in_dt, int B, size_t n, const unsigned* parts, int reverse, unsigned char* out, unsigned* hist,
+// per-image display tail: parts = [B, MDPT_POST_SEG_PARTS, 2] ordered {min, max} partials, hist / hist_clear = [B, 256] counts, lut = [B, 256],
+// B = the table's images (every per-image buffer starts at the table's first image); out (fp32 / uint8) is the packed output of PostRun::off
+int mdpt_launch_post_seg_minmax(const PostRunTable& t, int in_dt, float* out, unsigned* parts, unsigned* hist_clear, hipStream_t stream);
+int mdpt_launch_post_seg_u8(const PostRunTable& t, int in_dt, const unsigned* parts, int reverse, unsigned char* out, unsigned* hist,
                             hipStream_t stream);
 int mdpt_launch_post_hist(const unsigned char* in, int B, size_t n, unsigned* hist, hipStream_t stream);
 int mdpt_launch_post_eq_lut(const unsigned* hist, int B, const int* bin_of, int vmin, int vmax, unsigned char* lut, hipStream_t stream);
-int mdpt_launch_post_colorize(const unsigned char* in, int B, size_t n, const unsigned char* eq, const unsigned char* cmap, int channels, unsigned char* out,
+int mdpt_launch_post_colorize(const PostRunTable& t, const unsigned char* eq, const unsigned char* cmap, int channels, unsigned char* out,
                               hipStream_t stream);
 
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)

@@ -68,7 +68,8 @@ int MDPT_FN(mdpt_launch_tokens_to_resid)(const float* tokens, const float* pos, 
 // uint8 HWC BGR -> normalised fp32 [3,oh,ow] RGB through PyTorch-compatible antialiased bilinear resize
 int MDPT_FN(mdpt_launch_prepare_image)(const unsigned char* bgr, void* out, int out_dtype, int ih, int iw, int oh, int ow, const float mean[3],
                               const float inv_std[3], int interp, hipStream_t stream);
-int MDPT_FN(mdpt_launch_prepare_patchify)(const unsigned char* bgr, int img_dtype, op_t* out_hi, op_t* out_lo, int B, int ih, int iw, int H, int W, int P, int Kp,
+// ... fused with patchify for the frames of a BgrRunTable (at most 65535), written from im2col row 0 of out_hi / out_lo
+int MDPT_FN(mdpt_launch_prepare_patchify)(const BgrRunTable& t, int img_dtype, op_t* out_hi, op_t* out_lo, int H, int W, int P, int Kp,
                                          const float mean[3], const float inv_std[3], int interp, hipStream_t stream);  // interp: 0 bilinear, 1 bicubic (both antialiased)
 // BEiT relative position bias (reference v31_beit/components/relative_positional_encoder.py:117-309): bilinear-resize the
 // learned [(2Gh-1)(2Gw-1)+3, heads] table to the current grid and lay it out per head as an extended LUT so that the bias of

@@ -43,11 +43,28 @@ int run_pos(const Ctx& c) {
                                 h->cfg.base_patch_grid_w, c.p.gh, c.p.gw, h->F, c.s);
 }
 
-// im2col rows of the patch embedding: from an image tensor, or (mdpt_forward_bgr[_batch]) straight from the caller's uint8 BGR frames
+// im2col rows of the patch embedding: from an image tensor, or (mdpt_forward_bgr[_batch|_frames]) straight from the caller's uint8 BGR frames.
+// Frames of one size are one run of the frame table (one launch); a per-frame table goes MDPT_BGR_RUNS frames per launch, each launch from
+// its first frame's im2col rows.
 int run_patchify(const Ctx& c, const void* image, int image_dtype, const Planes& im, int H, int W) {
     const mdpt_handle* h = c.h;
-    if (c.bgr.ptr)
-        return OPLC(mdpt_launch_prepare_patchify, c.bgr.ptr, c.bgr.round_dtype, im.hi, im.lo, c.p.B, c.bgr.ih, c.bgr.iw, H, W, h->P, h->Kpatch, c.bgr.mean, c.bgr.inv_std, c.bgr.interp, c.s);
+    if (c.bgr.active()) {
+        BgrRunTable t{};
+        if (!c.bgr.frames) {
+            t.n = 1;
+            t.run[0] = BgrRun{c.bgr.ptr, c.bgr.ih, c.bgr.iw, c.p.B};
+            return OPLC(mdpt_launch_prepare_patchify, t, c.bgr.round_dtype, im.hi, im.lo, H, W, h->P, h->Kpatch, c.bgr.mean, c.bgr.inv_std, c.bgr.interp, c.s);
+        }
+        const size_t frame_elems = (size_t)(H / h->P) * (W / h->P) * h->Kpatch;
+        for (int b0 = 0; b0 < c.p.B; b0 += MDPT_BGR_RUNS) {
+            t.n = c.p.B - b0 < MDPT_BGR_RUNS ? c.p.B - b0 : MDPT_BGR_RUNS;
+            for (int r = 0; r < t.n; ++r)
+                t.run[r] = BgrRun{(const unsigned char*)c.bgr.frames[b0 + r], c.bgr.frames_hw[2 * (b0 + r)], c.bgr.frames_hw[2 * (b0 + r) + 1], 1};
+            CHK(OPLC(mdpt_launch_prepare_patchify, t, c.bgr.round_dtype, im.hi + frame_elems * b0, im.lo ? im.lo + frame_elems * b0 : nullptr, H, W, h->P,
+                     h->Kpatch, c.bgr.mean, c.bgr.inv_std, c.bgr.interp, c.s));
+        }
+        return 0;
+    }
     return OPLC(mdpt_launch_patchify, image, image_dtype, im.hi, im.lo, c.p.B, H, W, h->P, h->Kpatch, c.s, c.poison);
 }
 

@@ -123,7 +123,17 @@ __global__ __launch_bounds__(256) void normalize_kernel(const float* __restrict_
 // equalization LUT, colormap. Every image of the batch gets its own min/max, histogram and LUT; nothing crosses from one image to another.
 // Segmented min/max: grid (SEG_PARTS = MDPT_POST_SEG_PARTS, B); block (x, b) leaves the ordered {min, max} of its share of image b in parts[(b PARTS + x) 2 ..],
 // the next kernel reduces the PARTS entries of its image (no atomics, no buffer to clear first). A NaN pins {0, ~0} like block_minmax.
+// Every kernel here takes a PostRunTable (mdpt_kernels.h) by value: blockIdx.y = image b of the table, image j of run r; the uniform batch of
+// the mdpt_post_*_seg / mdpt_post_colorize entry points is one run, images of different sizes (mdpt_post_*_images) one run each.
 constexpr int SEG_PARTS = 64;
+
+// image b of the launch -> its run r and its index j in that run (a block-uniform walk; the grid holds exactly the table's images)
+__device__ __forceinline__ const PostRun& seg_image(const PostRunTable& t, int b, int& j) {
+    int r = 0;
+    j = b;
+    while (r < t.n - 1 && j >= t.run[r].count) j -= t.run[r++].count;
+    return t.run[r];
+}
 
 __device__ __forceinline__ float ld_dt(const void* p, size_t i, int dt) {
     if (dt == MDPT_DT_BF16) return (float)((const __bf16*)p)[i];
@@ -158,15 +168,20 @@ __device__ __forceinline__ void block_minmax_part(float lo, float hi, bool saw_n
     }
 }
 
-// out == null: min/max of each input image. Otherwise F.interpolate(bilinear) of each image to oh x ow (the arithmetic of scale_bilinear_kernel),
-// rounded to the input's dtype, stored as fp32, min/max of that. hist_clear != null: zero the [B,256] histogram the next kernel accumulates into.
-__global__ __launch_bounds__(256) void seg_scale_minmax_kernel(const void* __restrict__ in, int in_dt, float* __restrict__ out, int ih, int iw, int oh,
-                                                               int ow, unsigned* __restrict__ parts, unsigned* __restrict__ hist_clear) {
+// out == null: min/max of each input image. Otherwise F.interpolate(bilinear) of each image to its oh x ow (the arithmetic of scale_bilinear_kernel),
+// rounded to the input's dtype, stored as fp32 at its place of the packed out, min/max of that. hist_clear != null: zero the [B,256] histogram the
+// next kernel accumulates into.
+__global__ __launch_bounds__(256) void seg_scale_minmax_kernel(const PostRunTable t, int in_dt, float* __restrict__ out, unsigned* __restrict__ parts,
+                                                               unsigned* __restrict__ hist_clear) {
     const int b = blockIdx.y;
     if (hist_clear && blockIdx.x == 0) hist_clear[(size_t)b * 256 + threadIdx.x] = 0u;
+    int j;
+    const PostRun& img = seg_image(t, b, j);
+    const void* in = img.in;
+    const int ih = img.ih, iw = img.iw, oh = img.oh, ow = img.ow;
     const bool scale = out != nullptr;
     const size_t n = scale ? (size_t)oh * ow : (size_t)ih * iw;
-    const size_t in_base = (size_t)b * ih * iw;
+    const size_t in_base = (size_t)j * ih * iw, out_base = img.off + (size_t)j * oh * ow;
     const float sy = (float)ih / (float)oh, sx = (float)iw / (float)ow;
     float lo = INFINITY, hi = -INFINITY;
     bool saw_nan = false, any = false;
@@ -185,7 +200,7 @@ __global__ __launch_bounds__(256) void seg_scale_minmax_kernel(const void* __res
             const float top = __fmaf_rn(p01, lx, __fmul_rn(p00, 1.0f - lx)), bot = __fmaf_rn(p10, 1.0f - lx, __fmul_rn(p11, lx));
             v = __fadd_rn(__fmul_rn(1.0f - ly, top), __fmul_rn(ly, bot));
             v = round_dt(v, in_dt);
-            out[(size_t)b * n + i] = v;
+            out[out_base + i] = v;
         } else {
             v = ld_dt(in, in_base + i, in_dt);
         }
@@ -198,10 +213,15 @@ __global__ __launch_bounds__(256) void seg_scale_minmax_kernel(const void* __res
 }
 
 // (255 * normalize_01(image b)).byte() with image b's own min/max (normalize_kernel<1>'s arithmetic), optionally 255 - x, and (hist != null) image
-// b's 256-bin histogram of the result: LDS-private bins, one integer atomic per non-empty bin and block into hist[b, :].
-__global__ __launch_bounds__(256) void seg_u8_hist_kernel(const void* __restrict__ in, int in_dt, size_t n, const unsigned* __restrict__ parts,
-                                                          int reverse, unsigned char* __restrict__ out, unsigned* __restrict__ hist) {
+// b's 256-bin histogram of the result: LDS-private bins, one integer atomic per non-empty bin and block into hist[b, :]. Image b has ih x iw
+// elements; its result goes to its place of the packed out.
+__global__ __launch_bounds__(256) void seg_u8_hist_kernel(const PostRunTable t, int in_dt, const unsigned* __restrict__ parts, int reverse,
+                                                          unsigned char* __restrict__ out, unsigned* __restrict__ hist) {
     const int b = blockIdx.y;
+    int j;
+    const PostRun& img = seg_image(t, b, j);
+    const void* in = img.in;
+    const size_t n = (size_t)img.ih * img.iw;
     __shared__ unsigned bins[256];
     __shared__ unsigned smm[2];
     bins[threadIdx.x] = 0u;
@@ -217,13 +237,13 @@ __global__ __launch_bounds__(256) void seg_u8_hist_kernel(const void* __restrict
     __syncthreads();
     const float lo = ord2f(smm[0]), hi = ord2f(smm[1]);
     const float range = hi - lo;
-    const size_t base = (size_t)b * n;
+    const size_t base = (size_t)j * n, obase = img.off + (size_t)j * n;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         float v = (ld_dt(in, base + i, in_dt) - lo) / range;
         v = v == v ? fminf(fmaxf(v, 0.0f), 1.0f) : 0.0f;
         int q = (int)(255.0f * v);
         if (reverse) q = 255 - q;
-        out[base + i] = (unsigned char)q;
+        out[obase + i] = (unsigned char)q;
         if (hist) atomicAdd(&bins[q], 1u);
     }
     if (!hist) return;
@@ -289,18 +309,23 @@ __global__ __launch_bounds__(256) void equalize_lut_kernel(const unsigned* __res
     out[t] = (unsigned char)(int)__dmul_rn(255.0, norm);
 }
 
-// out[b, i] = cmap[eq[b][x[b, i]]] as BGR (channels 3) or eq[b][x[b, i]] (channels 1); eq == null: identity, cmap == null: gray (cv2.cvtColor GRAY2BGR)
-__global__ __launch_bounds__(256) void colorize_kernel(const unsigned char* __restrict__ in, size_t n, const unsigned char* __restrict__ eq,
-                                                       const unsigned char* __restrict__ cmap, int channels, unsigned char* __restrict__ out) {
+// out[b, i] = cmap[eq[b][x[b, i]]] as BGR (channels 3) or eq[b][x[b, i]] (channels 1); eq == null: identity, cmap == null: gray (cv2.cvtColor GRAY2BGR).
+// Image b (ih x iw uint8 at its run's in) goes to its place of the packed out (element off + j ih iw, times channels).
+__global__ __launch_bounds__(256) void colorize_kernel(const PostRunTable tab, const unsigned char* __restrict__ eq, const unsigned char* __restrict__ cmap,
+                                                       int channels, unsigned char* __restrict__ out) {
     const int b = blockIdx.y, t = threadIdx.x;
+    int j;
+    const PostRun& img = seg_image(tab, b, j);
+    const size_t n = (size_t)img.ih * img.iw;
+    const unsigned char* in = (const unsigned char*)img.in + (size_t)j * n;
     __shared__ unsigned char seq[256];
     __shared__ unsigned char scm[256 * 3];
     seq[t] = eq ? eq[(size_t)b * 256 + t] : (unsigned char)t;
     for (int c = 0; c < 3; ++c) scm[t * 3 + c] = cmap ? cmap[t * 3 + c] : (unsigned char)t;
     __syncthreads();
-    const size_t base = (size_t)b * n;
+    const size_t base = img.off + (size_t)j * n;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + t; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int e = seq[in[base + i]];
+        const int e = seq[in[i]];
         if (channels == 1) {
             out[base + i] = (unsigned char)e;
         } else {
@@ -315,6 +340,21 @@ __global__ __launch_bounds__(256) void colorize_kernel(const unsigned char* __re
 inline int grid_for(size_t total) {
     size_t g = (total + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
+// images of a table (at most 65535, the grid's y) and the largest of their sizes (in: ih iw, out: oh ow); false: a malformed table
+inline bool table_extent(const PostRunTable& t, int& B, size_t& max_in, size_t& max_out) {
+    B = 0;
+    max_in = max_out = 0;
+    if (t.n <= 0 || t.n > MDPT_POST_RUNS) return false;
+    for (int r = 0; r < t.n; ++r) {
+        const PostRun& p = t.run[r];
+        if (!p.in || p.ih <= 0 || p.iw <= 0 || p.oh <= 0 || p.ow <= 0 || p.count <= 0 || p.count > 65535 - B) return false;
+        B += p.count;
+        max_in = (size_t)p.ih * p.iw > max_in ? (size_t)p.ih * p.iw : max_in;
+        max_out = (size_t)p.oh * p.ow > max_out ? (size_t)p.oh * p.ow : max_out;
+    }
+    return true;
 }
 
 }  // namespace
@@ -345,17 +385,21 @@ int mdpt_launch_post_normalize(const float* in, const float* minmax, void* out, 
     return (int)hipGetLastError();
 }
 
-int mdpt_launch_post_seg_minmax(const void* in, int in_dt, int B, int ih, int iw, float* out, int oh, int ow, unsigned* parts, unsigned* hist_clear,
-                                hipStream_t stream) {
+int mdpt_launch_post_seg_minmax(const PostRunTable& t, int in_dt, float* out, unsigned* parts, unsigned* hist_clear, hipStream_t stream) {
+    int B;
+    size_t max_in, max_out;
+    if (!table_extent(t, B, max_in, max_out)) return (int)hipErrorInvalidValue;
     MdptProfScope prof("seg_scale_minmax_kernel", 0.0, stream);
-    hipLaunchKernelGGL(seg_scale_minmax_kernel, dim3(SEG_PARTS, B), dim3(256), 0, stream, in, in_dt, out, ih, iw, oh, ow, parts, hist_clear);
+    hipLaunchKernelGGL(seg_scale_minmax_kernel, dim3(SEG_PARTS, B), dim3(256), 0, stream, t, in_dt, out, parts, hist_clear);
     return (int)hipGetLastError();
 }
 
-int mdpt_launch_post_seg_u8(const void* in, int in_dt, int B, size_t n, const unsigned* parts, int reverse, unsigned char* out, unsigned* hist,
-                            hipStream_t stream) {
+int mdpt_launch_post_seg_u8(const PostRunTable& t, int in_dt, const unsigned* parts, int reverse, unsigned char* out, unsigned* hist, hipStream_t stream) {
+    int B;
+    size_t n, max_out;
+    if (!table_extent(t, B, n, max_out)) return (int)hipErrorInvalidValue;
     MdptProfScope prof("seg_u8_hist_kernel", 0.0, stream);
-    hipLaunchKernelGGL(seg_u8_hist_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, in, in_dt, n, parts, reverse, out, hist);
+    hipLaunchKernelGGL(seg_u8_hist_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, t, in_dt, parts, reverse, out, hist);
     return (int)hipGetLastError();
 }
 
@@ -371,9 +415,12 @@ int mdpt_launch_post_eq_lut(const unsigned* hist, int B, const int* bin_of, int 
     return (int)hipGetLastError();
 }
 
-int mdpt_launch_post_colorize(const unsigned char* in, int B, size_t n, const unsigned char* eq, const unsigned char* cmap, int channels, unsigned char* out,
+int mdpt_launch_post_colorize(const PostRunTable& t, const unsigned char* eq, const unsigned char* cmap, int channels, unsigned char* out,
                               hipStream_t stream) {
+    int B;
+    size_t n, max_out;
+    if (!table_extent(t, B, n, max_out)) return (int)hipErrorInvalidValue;
     MdptProfScope prof("colorize_kernel", 0.0, stream);
-    hipLaunchKernelGGL(colorize_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, in, n, eq, cmap, channels, out);
+    hipLaunchKernelGGL(colorize_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, t, eq, cmap, channels, out);
     return (int)hipGetLastError();
 }

@@ -457,6 +457,45 @@ def _check_frames(images_bgr):
     return list(images_bgr), False, images_bgr[0].shape[0:2]
 
 
+def _check_images(images_bgr, batch_size) -> tuple[list, bool]:
+    """Argument checks of DPTModel.inference_images (host-side only, nothing touches a GPU) -> (images, on_device): a list of uint8 HxWx3
+    ndarrays, or of contiguous uint8 HxWx3 CUDA tensors."""
+    if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)):
+        raise TypeError(f"inference_images: batch_size must be an int, got {type(batch_size)}")
+    if batch_size < 1:
+        raise ValueError(f"inference_images: batch_size must be at least 1, got {batch_size}")
+    if not isinstance(images_bgr, (list, tuple)):
+        raise TypeError(f"inference_images expects a list of uint8 HxWx3 BGR images (ndarrays or CUDA tensors), got {type(images_bgr)}")
+    if len(images_bgr) == 0:
+        raise ValueError("inference_images got no images")
+    n_dev = sum(isinstance(f, torch.Tensor) for f in images_bgr)
+    if 0 < n_dev < len(images_bgr):
+        raise TypeError("inference_images expects host arrays or device tensors, not a mix of both")
+    on_device = n_dev > 0
+    for f in images_bgr:
+        if on_device:
+            ok = f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 3 and f.device.type == "cuda"
+        else:
+            ok = isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3
+        if not ok:
+            raise TypeError("inference_images expects OpenCV-style uint8 HxWx3 BGR images (cv2.imread output), or uint8 HxWx3 CUDA tensors")
+        if f.shape[0] == 0 or f.shape[1] == 0:
+            raise ValueError(f"inference_images got an empty image ({f.shape[0]}x{f.shape[1]})")
+    if on_device and len({f.device for f in images_bgr}) != 1:
+        raise RuntimeError("inference_images: the device tensors are on different devices")
+    return [f.contiguous() if on_device else f for f in images_bgr], on_device
+
+
+def image_chunks(sizes_hw, scaled_hw, batch_size: int) -> list[tuple[tuple[int, int], list[int]]]:
+    """Forward plan of DPTModel.inference_images (pure host code): image sizes [(h, w), ...] and the size rule scaled_hw(h, w) -> model
+    tensor (H, W) -> [((H, W), [image indices]), ...]. A group is every image with the same tensor size, groups in order of first appearance,
+    indices in input order; each group is cut into chunks of at most batch_size images, one batched forward each."""
+    groups: dict[tuple[int, int], list[int]] = {}
+    for i, (h, w) in enumerate(sizes_hw):
+        groups.setdefault(tuple(int(v) for v in scaled_hw(int(h), int(w))), []).append(i)
+    return [(hw, idx[k:k + batch_size]) for hw, idx in groups.items() for k in range(0, len(idx), batch_size)]
+
+
 class _Engine:
     """Owns the C handle, the packed-weight buffer and cached workspaces for one (device, dtype) of a DPTModel."""
 
@@ -856,6 +895,57 @@ class DPTModel(nn.Module):
                 eng.call_checked("mdpt_forward_bgr_batch", src, b, img_h, img_w, native.dtype_code(img_dtype), h, w, mean3, std3, native.INTERP_BILINEAR,
                                  out, native.dtype_code(out.dtype), size_hw=(h, w), batch=b)
             return out
+
+    def inference_images(self, images_bgr, max_side_length: int | None = None, use_square_sizing: bool = True, batch_size: int = 32) -> list[Tensor]:
+        """inference() for a list of images of ANY sizes (not in the reference; its run_image.py loops over files) -> a list in input order, element
+        i the [1,H_i,W_i] map of image i in the model dtype (a view into its chunk's output). Takes uint8 HxWx3 BGR ndarrays, or uint8 HxWx3 CUDA
+        tensors on the model's device (not a mix). Images whose size rule gives the same tensor size share batched forwards of at most batch_size
+        images (image_chunks; square sizing, the default, gives every image the same size), each one mdpt_forward_bgr_frames call reading every
+        image from its own place. Element i equals model(torch.cat([prepare_image_bgr(f) for f in its chunk]))[its row] bit for bit; in the
+        default (batch-invariant) modes that is inference(image i)."""
+        images, on_device = _check_images(images_bgr, batch_size)
+        pe = self.patch_embed
+        p = next(self.parameters())
+        if p.device.type != "cuda":
+            raise RuntimeError("inference_images runs on the GPU only (no CPU fallback): move the model to a cuda device first")
+        if on_device and images[0].device != p.device:
+            raise RuntimeError(f"Expected all tensors to be on the same device, model is on {p.device} but the images are on {images[0].device}")
+        chunks = image_chunks([f.shape[0:2] for f in images], lambda h, w: pe._scaled_hw(h, w, max_side_length, use_square_sizing), batch_size)
+        out: list[Tensor | None] = [None] * len(images)
+        with torch.inference_mode():
+            probes = self.imgencoder.__dict__.get("_softmax_probes") or []
+            blocks = self.imgencoder.__dict__.get("_block_probes") or []
+            img_dtype = p.dtype if p.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
+            staged = img_dtype != p.dtype or any(len(pr._forward_hooks) > 0 for pr in probes) or any(len(node._forward_hooks) > 0 for node, _ in blocks)
+            eng = None if staged else self._get_engine()
+            mean3, std3 = pe._norm_constants()
+            for (h, w), idx in chunks:
+                b = len(idx)
+                if staged:
+                    # hooks listening: the stage-by-stage route of forward(), on the tensor prepare_image_bgr gives per image
+                    if on_device:
+                        x = torch.cat([pe._prepare_device(images[i], images[i].shape[0], images[i].shape[1], (h, w), native.INTERP_BILINEAR, p, img_dtype)
+                                       for i in idx])
+                    else:
+                        x = torch.cat([pe.prepare_image(images[i], max_side_length, use_square_sizing) for i in idx])
+                    y = self(x)
+                else:
+                    with torch.cuda.device(p.device):
+                        if on_device:
+                            ptrs = [images[i].data_ptr() for i in idx]
+                        else:
+                            # one pinned staging copy for the chunk: image k starts where image k-1 ends
+                            src = pe._stage_host_image([images[i] for i in idx], p.device)
+                            offs = np.cumsum([0] + [images[i].size for i in idx[:-1]])
+                            ptrs = [src.data_ptr() + int(o) for o in offs]
+                        ptr_arr = np.asarray(ptrs, dtype=np.uint64)
+                        hw_arr = np.asarray([images[i].shape[0:2] for i in idx], dtype=np.int32).ravel()
+                        y = torch.empty((b, h, w), device=p.device, dtype=eng.dtype)
+                        eng.call_checked("mdpt_forward_bgr_frames", ptr_arr.ctypes.data, hw_arr.ctypes.data, b, native.dtype_code(img_dtype), h, w, mean3,
+                                         std3, native.INTERP_BILINEAR, y, native.dtype_code(y.dtype), size_hw=(h, w), batch=b)
+                for k, i in enumerate(idx):
+                    out[i] = y[k:k + 1]
+        return out
 
     def prepare_image_bgr(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True,
                           interpolation_mode: str = "bilinear") -> Tensor:

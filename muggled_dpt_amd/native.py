@@ -47,6 +47,7 @@ FAMILY_SWINV2 = 3
 E_GRID = -7
 POST_F32, POST_U8, POST_U24 = 0, 1, 2
 POST_SEG_PARTS = 64  # MDPT_POST_SEG_PARTS
+BGR_RUNS, POST_RUNS = 64, 32  # MDPT_BGR_RUNS / MDPT_POST_RUNS (csrc/mdpt_kernels.h): images per launch of a per-image table
 INTERP_BILINEAR, INTERP_BICUBIC = 0, 1
 
 
@@ -191,6 +192,8 @@ SYMBOLS = {
     "mdpt_forward_bgr": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _I, _VP, _I, _VP, _SZ, _VP]),
     "mdpt_forward_bgr_batch": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _I, _VP, _I, _VP, _SZ,
                                               _VP]),
+    "mdpt_forward_bgr_frames": (ctypes.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _I, _VP, _I, _VP,
+                                               _SZ, _VP]),
     "mdpt_post_minmax": (ctypes.c_int, [_VP, _SZ, _VP, _VP, _VP]),
     "mdpt_post_scale_prediction": (ctypes.c_int, [_VP, _I, _I, _I, _VP, _I, _I, _VP, _VP, _VP]),
     "mdpt_post_normalize": (ctypes.c_int, [_VP, _SZ, _VP, _VP, _I, _I, _VP]),
@@ -199,6 +202,9 @@ SYMBOLS = {
     "mdpt_post_histogram": (ctypes.c_int, [_VP, _I, _SZ, _VP, _VP]),
     "mdpt_post_equalize_lut": (ctypes.c_int, [_VP, _I, _VP, _I, _I, _VP, _VP]),
     "mdpt_post_colorize": (ctypes.c_int, [_VP, _I, _SZ, _VP, _VP, _I, _VP, _VP]),
+    "mdpt_post_minmax_images": (ctypes.c_int, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "mdpt_post_u8_hist_images": (ctypes.c_int, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP, _VP]),
+    "mdpt_post_colorize_images": (ctypes.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

@@ -231,3 +231,124 @@ def depth_to_color(prediction: Tensor, target_wh: tuple[int, int] | None = None,
     out = torch.empty((b, oh, ow, 3), device=dev, dtype=torch.uint8)
     _launch(dev, "mdpt_post_colorize", u8.data_ptr(), b, n, None if eq is None else eq.data_ptr(), None if cmap is None else cmap.data_ptr(), 3, out.data_ptr())
     return out
+
+
+# ---- the same for images of different sizes
+
+
+def _prediction_list(predictions, what: str) -> list[Tensor]:
+    """[1,h,w] / [h,w] tensors (sizes may differ) or a [B,h,w] tensor -> list of contiguous [h,w] maps of one device and one float dtype."""
+    if isinstance(predictions, torch.Tensor):
+        if predictions.dim() != 3:
+            raise RuntimeError(f"{what} expects a list of [1,h,w] / [h,w] maps or a BxHxW tensor, got {tuple(predictions.shape)}")
+        maps = list(predictions.detach().unbind(0))
+    elif isinstance(predictions, (list, tuple)):
+        maps = []
+        for p in predictions:
+            if not isinstance(p, torch.Tensor):
+                raise TypeError(f"{what} expects depth tensors, got {type(p)}")
+            p = p.detach()
+            if p.dim() == 3 and p.shape[0] == 1:
+                p = p[0]
+            if p.dim() != 2:
+                raise RuntimeError(f"{what} expects [1,h,w] or [h,w] maps, got {tuple(p.shape)}")
+            maps.append(p)
+    else:
+        raise TypeError(f"{what} expects a list of depth tensors or a BxHxW tensor, got {type(predictions)}")
+    if not maps:
+        raise ValueError(f"{what} got no predictions")
+    if any(m.device.type != "cuda" for m in maps):
+        raise RuntimeError(f"{what}: expected CUDA tensors (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+    if len({m.device for m in maps}) != 1 or len({m.dtype for m in maps}) != 1:
+        raise RuntimeError(f"{what}: all predictions must share one device and one dtype")
+    if any(m.numel() == 0 for m in maps):
+        raise RuntimeError(f"{what}: empty prediction")
+    if maps[0].dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        maps = [m.to(torch.float32) for m in maps]
+    return [m.contiguous() for m in maps]
+
+
+def _target_hw(target_whs, n: int, what: str) -> list[tuple[int, int]]:
+    whs = list(target_whs)
+    if len(whs) != n:
+        raise ValueError(f"{what}: {n} predictions but {len(whs)} target sizes")
+    hw = [(int(wh[1]), int(wh[0])) for wh in whs]
+    if any(h <= 0 or w <= 0 for h, w in hw):
+        raise ValueError(f"{what}: target sizes must be positive, got {whs}")
+    return hw
+
+
+def _ptrs_hw(ptrs, hws):
+    """host arrays of the *_images entry points (they are read during the call only; the caller keeps these alive until then)"""
+    return np.asarray(ptrs, dtype=np.uint64), np.asarray(hws, dtype=np.int32).reshape(-1)
+
+
+def _minmax_images(maps: list[Tensor], out_hw, hist: Tensor | None):
+    """mdpt_post_minmax_images: per-image min/max partials, and (out_hw given) every map resized into one packed fp32 buffer -> (parts, scaled)"""
+    dev = maps[0].device
+    b = len(maps)
+    ptrs, in_hw = _ptrs_hw([m.data_ptr() for m in maps], [m.shape for m in maps])
+    scaled = None
+    o_hw = None
+    if out_hw is not None:
+        o_hw = np.asarray(out_hw, dtype=np.int32).reshape(-1)
+        scaled = torch.empty(int(sum(h * w for h, w in out_hw)), device=dev, dtype=torch.float32)
+    parts = torch.empty((b, native.POST_SEG_PARTS, 2), device=dev, dtype=torch.int32)
+    _launch(dev, "mdpt_post_minmax_images", ptrs.ctypes.data, in_hw.ctypes.data, native.dtype_code(maps[0].dtype), b,
+            None if scaled is None else scaled.data_ptr(), None if o_hw is None else o_hw.ctypes.data, parts.data_ptr(),
+            None if hist is None else hist.data_ptr())
+    return parts, scaled
+
+
+def _views(flat: Tensor, hws, tail=()) -> list[Tensor]:
+    out, at = [], 0
+    for h, w in hws:
+        n = h * w * int(np.prod(tail, dtype=np.int64))
+        out.append(flat[at:at + n].view(1, h, w, *tail))
+        at += n
+    return out
+
+
+def scale_prediction_images(predictions, target_whs) -> list[Tensor]:
+    """scale_prediction for images of different sizes: predictions (a list of [1,h,w] / [h,w] maps whose sizes may differ, as
+    DPTModel.inference_images returns, or a [B,h,w] tensor) and one (w, h) per image -> a list of [1,H_i,W_i] maps in the predictions' dtype.
+    Element i equals scale_prediction(prediction i, target_whs[i]) bit for bit. One launch per 32 images; the outputs are views into one
+    allocation."""
+    maps = _prediction_list(predictions, "scale_prediction_images")
+    hws = _target_hw(target_whs, len(maps), "scale_prediction_images")
+    _, scaled = _minmax_images(maps, hws, None)  # (the resize kernel rounds to the input dtype, so the cast below is exact)
+    out_dtype = predictions.dtype if isinstance(predictions, torch.Tensor) else predictions[0].dtype
+    return _views(scaled.to(out_dtype), hws)
+
+
+def depth_to_color_images(predictions, target_whs=None, reverse: bool = False, high_contrast: bool = False, lut=None) -> list[Tensor]:
+    """depth_to_color for images of different sizes: predictions as for scale_prediction_images, target_whs one (w, h) per image (None: each
+    map's own size) -> a list of uint8 [1,H_i,W_i,3] BGR frames, element i equal to depth_to_color(prediction i, target_whs[i], reverse,
+    high_contrast, lut) bit for bit (its own min/max and histogram). At most four launches per 32 images: resize + min/max (also clears the
+    histograms), uint8 + histogram, LUT, equalize-and-colormap. The outputs are views into one allocation."""
+    maps = _prediction_list(predictions, "depth_to_color_images")
+    dev = maps[0].device
+    cmap = _cmap_tensor(lut, dev)
+    b = len(maps)
+    in_hw = [tuple(m.shape) for m in maps]
+    out_hw = None if target_whs is None else _target_hw(target_whs, b, "depth_to_color_images")
+    hws = in_hw if out_hw is None else out_hw
+    hist = torch.empty((b, 256), device=dev, dtype=torch.int32) if high_contrast else None
+    hist_ptr = None if hist is None else hist.data_ptr()
+    parts, scaled = _minmax_images(maps, out_hw, hist)
+    if scaled is None:
+        src_ptrs, src_dt = [m.data_ptr() for m in maps], native.dtype_code(maps[0].dtype)
+    else:
+        offs = np.cumsum([0] + [h * w for h, w in hws[:-1]])
+        src_ptrs, src_dt = [scaled.data_ptr() + 4 * int(o) for o in offs], native.DTYPE_F32
+    ptrs, hw_arr = _ptrs_hw(src_ptrs, hws)
+    u8 = torch.empty(int(sum(h * w for h, w in hws)), device=dev, dtype=torch.uint8)
+    _launch(dev, "mdpt_post_u8_hist_images", ptrs.ctypes.data, hw_arr.ctypes.data, src_dt, b, parts.data_ptr(), int(bool(reverse)), u8.data_ptr(), hist_ptr)
+    eq = None
+    if high_contrast:
+        eq = torch.empty((b, 256), device=dev, dtype=torch.uint8)
+        _launch(dev, "mdpt_post_equalize_lut", hist.data_ptr(), b, None, 0, 255, eq.data_ptr())
+    out = torch.empty(u8.numel() * 3, device=dev, dtype=torch.uint8)
+    _launch(dev, "mdpt_post_colorize_images", u8.data_ptr(), hw_arr.ctypes.data, b, None if eq is None else eq.data_ptr(),
+            None if cmap is None else cmap.data_ptr(), 3, out.data_ptr())
+    return _views(out, hws, (3,))

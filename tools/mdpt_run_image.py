@@ -3,9 +3,12 @@
 run DPTModel.inference on one BGR uint8 image and print load ms, inference ms and the output shape, like the reference's
 run_image.py:204-208 does before it opens its window. No display, no OpenCV: images come from a .npy file (HxWx3 uint8, BGR) or
 are synthesised; the 8-bit depth map can be saved as .npy (device-side post-processing, muggled_dpt_amd.postprocess).
+Several -i files (of any sizes) run together through DPTModel.inference_images, batched per model tensor size; -o is then a directory
+that receives every image's 8-bit depth map at the image's own size (postprocess.depth_to_color_images).
 
   python tools/mdpt_run_image.py --synthetic vits --size 518 --fp32
   python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i image.npy -o depth_u8.npy
+  python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i a.npy -i b.npy -i c.npy -o depth_dir
 """
 import argparse
 import os
@@ -23,7 +26,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-m", "--model_path", default=None, help="checkpoint file (any of the four supported families)")
     ap.add_argument("--synthetic", default="vits", help="config name for seeded synthetic weights when no checkpoint is given")
-    ap.add_argument("-i", "--image_path", default=None, help=".npy file holding an HxWx3 uint8 BGR image")
+    ap.add_argument("-i", "--image_path", action="append", default=None,
+                    help=".npy file holding an HxWx3 uint8 BGR image; give it several times to run several images (any sizes) batched")
+    ap.add_argument("-b", "--batch_size", type=int, default=32, help="several images: at most this many per batched forward")
     ap.add_argument("-s", "--size", type=int, default=None, help="max side length (default: the model's base size)")
     ap.add_argument("-a", "--use_aspect_ratio", action="store_true", help="keep the image aspect ratio (default: square sizing)")
     ap.add_argument("--fp32", action="store_true", help="float32 model = split-bf16 fp32-class arithmetic (default: bfloat16)")
@@ -41,8 +46,10 @@ def main():
         from muggled_dpt_amd.synthetic import make_synthetic_original_state_dict
         cfg, model = make_depthanythingv2_dpt_from_original_state_dict(make_synthetic_original_state_dict(args.synthetic, 0))
     model.to("cuda", torch.float32 if args.fp32 else torch.bfloat16)
+    if args.image_path and len(args.image_path) > 1:
+        return run_images(model, args, t0)
     if args.image_path:
-        img = np.load(args.image_path)
+        img = np.load(args.image_path[0])
     else:
         img = np.random.default_rng(1).integers(0, 256, (518, 518, 3), dtype=np.uint8)
     model.inference(img, args.size, not args.use_aspect_ratio)  # first call builds the engine (weight repack)
@@ -56,6 +63,30 @@ def main():
     if args.output:
         np.save(args.output, convert_to_uint8(depth).squeeze(0).cpu().numpy())
         print("saved", args.output)
+
+
+def run_images(model, args, t0):
+    """several images of any sizes: DPTModel.inference_images, then every 8-bit map back at its image's own size"""
+    from muggled_dpt_amd.postprocess import depth_to_color_images
+    images = [np.load(p) for p in args.image_path]
+    square = not args.use_aspect_ratio
+    model.inference_images(images, args.size, square, args.batch_size)  # first call builds the engine (weight repack)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    print(f"Loading model & first call: {round(1000 * (t1 - t0))} ms", flush=True)
+    depths = model.inference_images(images, args.size, square, args.batch_size)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    print(f"Inference of {len(images)} images: {round(1000 * (t2 - t1), 2)} ms ({round(1000 * (t2 - t1) / len(images), 2)} ms per image)")
+    for path, img, d in zip(args.image_path, images, depths):
+        print(f"  {path}: {img.shape[1]}x{img.shape[0]} -> prediction {tuple(d.shape)}, dtype {d.dtype}")
+    if args.output:
+        os.makedirs(args.output, exist_ok=True)
+        grey = depth_to_color_images(depths, [(img.shape[1], img.shape[0]) for img in images])
+        for path, g in zip(args.image_path, grey):
+            out = os.path.join(args.output, os.path.splitext(os.path.basename(path))[0] + "_depth_u8.npy")
+            np.save(out, g[0, :, :, 0].cpu().numpy())
+            print("saved", out)
 
 
 if __name__ == "__main__":
