@@ -47,10 +47,15 @@ extern "C" {
                               bf16 is not preferred (demo_helpers/misc.py:61-77: float16). The layer-scale-folded matrices are packed
                               times a power of two that the GEMMs undo exactly, so checkpoints with gammas of 1e-2 ... 1e-5 keep their
                               hi / lo planes in fp16's normal range                                                   */
-#define MDPT_PREC_FP16X3 3 /* split-fp16 (hi+lo) operands, 3 passes                                                 */
+#define MDPT_PREC_FP16X3 3 /* split-fp16 (hi+lo) operands, 3 passes. Range: fp32-class while the largest |value| M of every operand
+                              tensor lies in [2^-2, 32768]. Below, the lo plane (|A_lo| <= 2^-12 |A|) turns fp16-subnormal for the
+                              typical element - an absolute 2^-25 floor; measured on the decoder stages: the max-norm error is
+                              <= 1.25x its value at M ~ 4 down to M = 2^-2, 1.6 ... 2.8x at 2^-4, ~100x at 2^-10. Above 32768 the
+                              hi planes approach saturation (65504). (tests/test_gpu_operand_range.py)                */
 #define MDPT_PREC_MIXED 4  /* fp16 operands; the op classes listed in mdpt_default_mixed_passes() run 3 or 2 passes, the others 1:
                               the cheapest per-class assignment that keeps the depth map within 1e-3 of the fp32 reference
-                              (profiles/r05_precision_budget.md)                                                     */
+                              (profiles/r05_precision_budget.md). Range of the decoder classes (fp8 cross terms, MDPT_PASSES_2F8 /
+                              _3F8 below): largest |activation| of an operand tensor in [2^-5, 32768]                         */
 
 /* op classes of the path (what mdpt_set_class_passes / MDPT_PREC_MIXED address) */
 #define MDPT_CLASS_PATCH 0  /* patch-embed projection                    patch_embed.py:92                         */
@@ -127,8 +132,12 @@ void mdpt_destroy(mdpt_handle* h);
  * products with the CROSS TERMS (A_lo W_hi, A_hi W_lo: 2^-11 of the main term) on fp8 operands through gfx950's block-scaled MFMA at twice
  * the fp16 rate - activations E5M2 with one constant power-of-two scale, weights E4M3 with one power-of-two scale per output row
  * (csrc/f8_cross.h) - i.e. 1.5 / 2 pass-equivalents instead of 2 / 3 at the accuracy of the fp16 cross terms
- * (tests/precision_budget/emulate_operand_rounding.py, format "sf8"). A class whose contraction lengths are not all multiples of 128 (the
- * small encoders' reassembly widths, fusion widths below 128), the SwinV2 family and the bf16 operand modes run the fp16-plane form of the
+ * (tests/precision_budget/emulate_operand_rounding.py, format "sf8"). Range: the largest |activation| M of an operand tensor in
+ * [2^-5, 32768] - the residue plane is e5m2(A_lo * 2^11), unsaturated for every normal fp16 value (<= 32768 < 57344), normal from a residue of
+ * 2^-25 up; the a8 plane e5m2(A_hi) saturates at 57344. tests/test_gpu_operand_range.py sweeps M over this range: the error of the fp8 forms
+ * stays within 1.3x its value at M ~ 4 and they keep carrying what the fp16 cross terms carry (the reassembly / fusion forms alone hold down
+ * to M = 2^-9; a 3-term head in front of a head tail on fp16 planes sees that tail's floor from 2^-6). A class whose contraction lengths
+ * are not all multiples of 128 (the small encoders' reassembly widths, fusion widths below 128), the SwinV2 family and the bf16 operand modes run the fp16-plane form of the
  * same term count instead (mdpt_get_class_f8 tells). Changes the packed-weight layout and the workspace
  * plan: call it after mdpt_create and BEFORE mdpt_packed_bytes / mdpt_finalize / mdpt_workspace_bytes (bound pointers are kept).
  * mdpt_get_class_passes reads the current assignment; mdpt_default_mixed_passes fills the table MDPT_PREC_MIXED uses. */

@@ -420,7 +420,8 @@ __global__ __launch_bounds__(256) void pack_weight_kernel(const void* __restrict
 // fp8 planes of an F8 class (f8_cross.h): one workgroup per packed row. w8[n][k] = e4m3(W_hi[n][k] / 2^e_n), wlo8 = e4m3((W - W_hi)[n][k] / 2^e'_n)
 // with the row's largest magnitude in [128, 256) (e4m3's largest finite value is 448: the conversion turns anything beyond 464 into NaN, so the
 // row maximum stays a binade below it), K in the fp8 planes' order (conv: 128-channel blocks). scales[n] = E8M0(e_n), scales[Np + n] =
-// E8M0(e'_n + 16): the activations' constant 2^-16 (F8_A_SCALE) belongs to the residue plane only, the second term's a8 plane is unshifted.
+// E8M0(e'_n + F8_LO_SHIFT): the activations' constant 2^-F8_LO_SHIFT (F8_A_SCALE) belongs to the residue plane only, the second term's a8
+// plane is unshifted.
 __global__ __launch_bounds__(256) void pack_weight_f8_kernel(const void* __restrict__ src, int sdt, unsigned char* w8, unsigned char* wlo8, unsigned char* scales,
                                                              int kind, int N, int K, int Np, int Kp, int ksz, int src_ld, int src_col0,
                                                              const void* __restrict__ row_scale, int rdt, const float* __restrict__ wscale) {
@@ -524,7 +525,7 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
 #if MDPT_HAVE_F8
             if (out_lo && out_f8) {  // the fp8 form an F8 consumer reads (f8_cross.h); stage-level entry points only: one element at a time
                 unsigned char* b8 = (unsigned char*)out_lo;
-                b8[idx] = (unsigned char)(f8_pk_e5m2((v - (float)h) * 65536.0f, 0.0f, 0u, false) & 0xFF);
+                b8[idx] = (unsigned char)(f8_pk_e5m2((v - (float)h) * F8_LO_SCALE, 0.0f, 0u, false) & 0xFF);
                 if (out_a8) b8[out_f8 + idx] = (unsigned char)(f8_pk_e5m2((float)h, 0.0f, 0u, false) & 0xFF);
                 continue;
             }
@@ -534,7 +535,7 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
     }
 }
 
-// lo_f8 != 0: in_lo is the e5m2 residue plane of an F8 consumer (bytes; f8_cross.h): value = hi + e5m2(byte) * 2^-16 (an e5m2 byte is the top byte of an fp16)
+// lo_f8 != 0: in_lo is the e5m2 residue plane of an F8 consumer (bytes; f8_cross.h): value = hi + e5m2(byte) * 2^-F8_LO_SHIFT (an e5m2 byte is the top byte of an fp16)
 __global__ __launch_bounds__(256) void tokens_export_kernel(const op_t* in_hi, const op_t* in_lo, const float* in_f32,
                                                             float* __restrict__ out, int B, int N, int npad, int F, int skip_cls, size_t lo_f8) {
     const int nout = N - skip_cls;
@@ -548,7 +549,7 @@ __global__ __launch_bounds__(256) void tokens_export_kernel(const op_t* in_hi, c
         if (in_f32) v = in_f32[o];
         else if (in_lo && lo_f8) {
             const unsigned short b16 = (unsigned short)(((const unsigned char*)in_lo)[o] << 8);
-            v = (float)in_hi[o] + (float)__builtin_bit_cast(_Float16, b16) * (1.0f / 65536.0f);
+            v = (float)in_hi[o] + (float)__builtin_bit_cast(_Float16, b16) * (1.0f / F8_LO_SCALE);
         }
         else { v = (float)in_hi[o]; if (in_lo) v += (float)in_lo[o]; }
         out[idx] = v;
@@ -568,7 +569,7 @@ __global__ __launch_bounds__(256) void tokens_import_kernel(const float* __restr
 #if MDPT_HAVE_F8
         if (out_lo && out_f8) {  // the fp8 form an F8 consumer reads (f8_cross.h), one element at a time (stage-level / BEiT tap path: not hot)
             unsigned char* b8 = (unsigned char*)out_lo;
-            b8[idx] = (unsigned char)(f8_pk_e5m2((v - (float)h) * 65536.0f, 0.0f, 0u, false) & 0xFF);
+            b8[idx] = (unsigned char)(f8_pk_e5m2((v - (float)h) * F8_LO_SCALE, 0.0f, 0u, false) & 0xFF);
             if (out_a8) b8[out_f8 + idx] = (unsigned char)(f8_pk_e5m2((float)h, 0.0f, 0u, false) & 0xFF);
             continue;
         }

@@ -6,14 +6,17 @@
 // STATIC scales - no per-block scale arithmetic anywhere:
 //
 //   activations   E5M2 (fp16's exponent range, 2 significand bits), produced by the epilogue that produces the fp16 plane:
-//                   lo8 = e5m2((A - A_hi) * 2^16)   the residue is <= 2^-11 |A|: the shift keeps the residue of every normal fp16 value in e5m2's
-//                                                    normal range (a plain e5m2 of the residue would be subnormal below |A| = 2^-3)
+//                   lo8 = e5m2((A - A_hi) * 2^11)   (F8_LO_SHIFT) the residue is at most half an fp16 ulp of A: 2^-25 ... 16 over the normal fp16
+//                                                    values 2^-14 <= |A| <= 65504, times 2^11 that is 2^-14 ... 32768 - inside e5m2's normal range
+//                                                    (2^-14 ... 57344) for every normal fp16 value, unsaturated at the top (a shift of 16 saturated
+//                                                    the residues of |A| >= 2048; a plain e5m2 of the residue would be subnormal below |A| = 2^-3)
 //                   a8  = e5m2(A_hi)                 (3F8 only: the operand of the A_hi W_lo^T term)
-//                 both enter the MFMA with ONE constant E8M0 scale byte, 2^-16 (F8_A_SCALE): the a8 term's 2^16 is folded into its weight rows' scale.
-//   weights       E4M3 with one power-of-two scale per OUTPUT ROW (pack time): w8 = e4m3(W_hi / 2^e_row), row maximum in [256, 448]; a float format
+//                 both enter the MFMA with ONE constant E8M0 scale byte, 2^-11 (F8_A_SCALE): the a8 term's 2^11 is folded into its weight rows' scale.
+//                 Range: include/mdpt.h (largest |A| of an operand tensor up to 32768; tests/test_gpu_operand_range.py).
+//   weights       E4M3 with one power-of-two scale per OUTPUT ROW (pack time): w8 = e4m3(W_hi / 2^e_row), row maximum in [128, 256); a float format
 //                 keeps its 3 significand bits over 15 binades below the row maximum, so the MX block granularity (32 K elements) buys nothing
 //                 here, and a per-row scale is a register constant of the kernel (4 bytes per lane: one per 16-row block the lane touches).
-//                   wlo8 = e4m3((W - W_hi) / 2^e'_row), scale byte e'_row + 16 + 127.
+//                   wlo8 = e4m3((W - W_hi) / 2^e'_row), scale byte e'_row + F8_LO_SHIFT + 127.
 //   Measured premise: tests/precision_budget/emulate_operand_rounding.py --study lowlo (format "sf8") - the mixed table with every cross term
 //   in this form reads 6.8e-4 / 8.1e-4 on ViT-L images 0 / 31 against 7.3e-4 / 8.3e-4 with fp16 cross terms. Instruction semantics pinned by
 //   tools/probes/mfma_scale_probe.hip (layout, scale rows) and tools/probes/f8_cross_probe.hip (formats, op_sel, conversions).
@@ -25,9 +28,13 @@
 #pragma once
 #include "op_types.h"
 
+// the residue plane's shift: lo8 = e5m2(residue * 2^F8_LO_SHIFT), decoded as e5m2(byte) / F8_LO_SCALE (every producer, the MFMA scale byte,
+// the packed weight-row scales and the token exporter; tests/precision_budget/emulate_operand_rounding.py reads the same number from here)
+constexpr int F8_LO_SHIFT = 11;
+constexpr float F8_LO_SCALE = (float)(1 << F8_LO_SHIFT);
+
 #if MDPT_OP_IS_F16 && (defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__))
 #define MDPT_HAVE_F8 1
-constexpr int F8_LO_SHIFT = 16;                    // lo8 = e5m2(residue * 2^16)
 constexpr int F8_A_SCALE = 127 - F8_LO_SHIFT;      // E8M0 byte of every activation operand
 constexpr float F8_E5M2_MAX = 57344.0f;
 
@@ -43,15 +50,16 @@ __device__ __forceinline__ unsigned f8_pk_e5m2(float a, float b, unsigned old, b
     b = __builtin_amdgcn_fmed3f(b, -F8_E5M2_MAX, F8_E5M2_MAX);
     return hi ? (unsigned)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, (int)old, true) : (unsigned)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, (int)old, false);
 }
-// the same without the clamp, for values known to be inside the range (a residue times 2^16: |.| <= 2^-11 * 65504 * 2^16 overflows only for
-// |A| > 1792 - NOT bounded; the fp16 value itself: bounded by 65504 > 57344 - NOT bounded either. Kept for the halo builders whose values are bounded.)
+// the same without the clamp, for values known to be inside the range (a residue times 2^F8_LO_SHIFT: <= 32768 only while A itself is inside
+// fp16's range - an fp32 A beyond 65504 leaves a residue of any size, NOT bounded; the fp16 value itself: bounded by 65504 > 57344 - NOT bounded
+// either. Kept for the halo builders whose values are bounded.)
 __device__ __forceinline__ unsigned f8_pk_e5m2_bounded(float a, float b, unsigned old, bool hi) {
     return hi ? (unsigned)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, (int)old, true) : (unsigned)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, (int)old, false);
 }
 
 // four values v[0..3] and their fp16 roundings h[0..3] (as fp32) -> one dword of lo8 bytes / one dword of a8 bytes
 __device__ __forceinline__ unsigned f8_lo8x4(float v0, float v1, float v2, float v3, float h0, float h1, float h2, float h3) {
-    const float s = 65536.0f;
+    const float s = F8_LO_SCALE;
     unsigned d = f8_pk_e5m2((v0 - h0) * s, (v1 - h1) * s, 0u, false);
     return f8_pk_e5m2((v2 - h2) * s, (v3 - h3) * s, d, true);
 }

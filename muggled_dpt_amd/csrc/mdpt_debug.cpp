@@ -68,7 +68,7 @@ int mdpt_debug_read(mdpt_handle* h, const char* name, void* out_f32, size_t out_
     const std::string n = name;
     const size_t* planes = nullptr;
     size_t f32_off = SIZE_MAX, elems = 0;
-    size_t bf16_only[2] = {SIZE_MAX, SIZE_MAX};  // a bf16 map without a lo plane
+    size_t bf16_only[3] = {SIZE_MAX, SIZE_MAX, 0};  // a bf16 map without a lo plane ([2]: no fp8 plane - Ctx::pl reads three entries)
     const bool bf16_head = head_tail_fused(h) && mdpt_head_tail_scale_ok(8 * p.gh, 8 * p.gw, p.H, p.W);
     const size_t px[4] = {(size_t)16 * p.Np, (size_t)4 * p.Np, (size_t)p.Np, (size_t)p.Np / 4};
     if (n == "im2col") { planes = p.im2col; elems = (size_t)p.B * p.Np * h->Kpatch; }

@@ -101,7 +101,7 @@ struct Mat {  // packed operand panel [Np][Kp]
     size_t off_scale;      // fp16 handles, layer-scale-folded matrices: 2 floats {s, 1 / s} in the packed buffer (SIZE_MAX = none), GemmParams::wscale
     const float* wscale;
     // fp8 cross-term planes of an F8 class (f8_cross.h; SIZE_MAX = none): [Np][Kp] e4m3 bytes of W_hi (K order of the 128-wide fp8 K tiles),
-    // of W - W_hi (3 terms only), and the per-row E8M0 scale bytes of both ([Np] each, the second with the activations' 2^16 folded in)
+    // of W - W_hi (3 terms only), and the per-row E8M0 scale bytes of both ([Np] each, the second with the activations' 2^F8_LO_SHIFT folded in)
     size_t off_w8, off_wlo8, off_s8;
     const uint8_t* w8; const uint8_t* wlo8; const uint8_t* s8; const uint8_t* slo8;
 };

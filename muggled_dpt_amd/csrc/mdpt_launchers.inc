@@ -42,7 +42,7 @@ int MDPT_FN(mdpt_launch_pack_weight)(const void* src, int src_dtype, op_t* dst_h
                             int ksz, hipStream_t stream, int src_ld = 0, int src_col0 = 0, const void* row_scale = nullptr, int scale_dtype = 0,
                             const float* wscale = nullptr);  // wscale: device {s, 1 / s}, every entry is multiplied by s (a power of two) before the split
 // fp8 planes of an F8 class (fp16 build; f8_cross.h): w8 / wlo8 [Np][Kp] e4m3 bytes of W_hi / W - W_hi in the fp8 K order (conv: 128-channel blocks),
-// scales [2 Np] E8M0 bytes (row scales of w8, then of wlo8 with the activations' 2^16 folded in); Kp % 128 == 0; wlo8 may be null (two terms)
+// scales [2 Np] E8M0 bytes (row scales of w8, then of wlo8 with the activations' 2^F8_LO_SHIFT folded in); Kp % 128 == 0; wlo8 may be null (two terms)
 int MDPT_FN(mdpt_launch_pack_weight_f8)(const void* src, int src_dtype, unsigned char* w8, unsigned char* wlo8, unsigned char* scales, int kind, int N, int K,
                                        int Np, int Kp, int ksz, hipStream_t stream, int src_ld = 0, int src_col0 = 0, const void* row_scale = nullptr,
                                        int scale_dtype = 0, const float* wscale = nullptr);

@@ -90,11 +90,15 @@ def mx_quant(x: torch.Tensor, fmt: str, dim: int) -> torch.Tensor:
 
 
 # ---- the form round 6 BUILT (csrc/f8_cross.h): fp8 cross terms with STATIC scales - no per-block scale arithmetic in any kernel.
-#   activations: E5M2 (fp16's exponent range, 2 significand bits). lo plane = e5m2((A - A_hi) * 2^16) with the constant E8M0 scale 2^-16 in
-#                the MFMA's scale operand (A_lo <= 2^-11 |A|: the shift keeps the residue of every normal fp16 value inside e5m2's NORMAL range);
+#   activations: E5M2 (fp16's exponent range, 2 significand bits). lo plane = e5m2((A - A_hi) * 2^F8_LO_SHIFT) with the constant E8M0 scale
+#                2^-F8_LO_SHIFT in the MFMA's scale operand (the residue is at most half an fp16 ulp, 2^-25 ... 16 for the normal fp16 values: times
+#                2^11 it stays inside e5m2's NORMAL range, 2^-14 ... 57344, unsaturated - tests/test_mx_emulation_cpu.py);
 #                the A_hi W_lo term of the 3-pass classes reads a8 = e5m2(A_hi), scale 1. Saturating.
-#   weights:     E4M3 with ONE power-of-two scale per output row (row maximum into [256, 448]): a float format keeps 3 significand bits
+#   weights:     E4M3 with ONE power-of-two scale per output row (row maximum into [128, 256)): a float format keeps 3 significand bits
 #                over 15 binades below the row maximum, so the MX block scale buys nothing here; per-row = a register constant of the kernel.
+F8_LO_SHIFT = 11  # csrc/f8_cross.h F8_LO_SHIFT (tests/test_mx_emulation_cpu.py keeps the two equal)
+
+
 def _fp_quant(v: torch.Tensor, m: int, emin: int, vmax: float) -> torch.Tensor:
     e = torch.floor(torch.log2(v.abs().clamp_min(1e-300))).clamp_min(emin)
     q = torch.exp2(e - m)
@@ -182,7 +186,7 @@ class _FProxy:
         xh, wh = rnd(x, "f16"), rnd(weight, "f16")
         if fmt == "sf8":  # static-scale fp8 (the built form): rows of a Linear / conv weight = dim 0, of a transposed-conv weight = dim 1
             rows = 1 if fn is TF.conv_transpose2d else 0
-            y = fn(xh, wh, bias, **kw) + fn(sf8_act(x - xh, 16), sf8_weight(wh, rows), None, **kw)
+            y = fn(xh, wh, bias, **kw) + fn(sf8_act(x - xh, F8_LO_SHIFT), sf8_weight(wh, rows), None, **kw)
             if base == "f16x3":
                 y = y + fn(sf8_act(xh, 0), sf8_weight(weight - wh, rows), None, **kw)
             return y

@@ -2,7 +2,7 @@
 e5m2 activation planes / row-scaled e4m3 weight planes through gfx950's block-scaled MFMA. Run with `pytest -m gpu` on an MI355X.
 
 The yardstick is the CPU emulation of exactly this arithmetic (tests/precision_budget/emulate_operand_rounding.py, format "sf8": the same
-quantisers - e5m2 of the residue times 2^16, e5m2 of the values, e4m3 with one power-of-two scale per output row - applied to the operands of
+quantisers - e5m2 of the residue times 2^F8_LO_SHIFT, e5m2 of the values, e4m3 with one power-of-two scale per output row - applied to the operands of
 the oracle's contractions, products in fp32). GPU and emulation round the same values the same way, so they differ by accumulation order and
 by where a bilinear upsample sits relative to a rounding (the library applies the 1x1 fusion projection before the x2 upsample: exact in real
 arithmetic, a different operand to round) - two orders of magnitude below what a wrong scale, a wrong K order or a missing term would show.
