@@ -369,6 +369,43 @@ int mdpt_post_u8_hist_images(const void* const* in, const int32_t* hw, int32_t i
 int mdpt_post_colorize_images(const void* in_u8, const int32_t* hw, int32_t B, const void* eq_lut, const void* cmap_bgr, int32_t channels, void* out,
                               void* stream);
 
+/* Still-image display tail and 24-bit edge alpha on the device (additive to ABI v6): the per-image loop of the reference's still-image demo
+ * (run_image.py:185-195 display, :323-343 threshold / equalization / colormap, :350-358 .npy save) and the alpha channel of its 3D viewer
+ * (run_3dviewer.py:455-505 edge mask, :576-593 packing). Uniform batches of B images of H x W; nothing is read back, nothing synchronises.
+ * Buffers (device): parts as above; coef [B, 4] fp64 plane {nx, ny, nz, d} (plane = -(d + nx x + ny y) / nz); vparts [B, MDPT_POST_SEG_PARTS, 2]
+ * fp64 {min, max} partials; mag [B, H, W] fp32; mag_max [B] uint32 (fp32 bits); sample_xy int32 (x, y) pairs, [N, 2] or [B, N, 2].
+ *   mdpt_post_display_prep ... remove_inf(scale_prediction(x)) per image: bilinear resize to out_h x out_w (a copy when the size is unchanged),
+ *                              rounded to in_dtype, +-inf -> 0, stored in in_dtype at out_bhw; parts = its per-image min/max; hist_clear zeroes [B,256]
+ *   mdpt_post_plane_fit ...... one workgroup per image (demo_helpers/plane_fit.py): z at the sample points (parts != NULL: of normalize_01 of the
+ *                              map, evaluated in in_dtype as torch does), the 3x3 Gram matrix of the centred samples (x / y means (W-1)/2,
+ *                              (H-1)/2) in fp64, its smallest eigenvector by Jacobi -> coef. Points are clamped into the map. A constant map
+ *                              gives the constant plane.
+ *   mdpt_post_plane_eval ..... the plane images of coef -> out_f32 [B,H,W]
+ *   mdpt_post_plane_minmax ... v = normalize_01(x) - factor * plane in fp64 (parts, coef of the same map) -> vparts
+ *   mdpt_post_threshold ...... t = clip((normalize_01(v) - thresh_min) / max(0.001, thresh_max - thresh_min), 0, 1) in fp64. mode MDPT_POST_U8:
+ *                              round-half-even(255 t) -> out uint8 [B,H,W], hist != NULL counts it (zero it first); reverse must be 0 (255 - x
+ *                              comes after the equalization: reverse the colormap instead). mode MDPT_POST_F32: t, or 1 - t with reverse -> fp32
+ *   mdpt_post_edge_mag ....... the viewer's 5x5 Gaussian blur (blur_weights: blur_ksize^2 fp32 on the HOST, read during the call; odd size up to 15)
+ *                              and 3x3 Sobel, both with reflect padding, mag = sqrt(dx^2 + dy^2) -> mag_f32 and its per-image max -> mag_max
+ *                              (cleared by the call). parts != NULL: of normalize_01 of the map (fp32). Sides must be at least max(2, pad + 1).
+ *   mdpt_post_edge_mask ...... ~round(255 mag / max) -> uint8 [B,count]; a flat map (max 0) gives 255 everywhere
+ *   mdpt_post_pack_u24_alpha . mdpt_post_normalize(MDPT_POST_U24) per image (parts: its min/max; NULL: metric, as is) with the alpha byte in the same
+ *                              pass: the edge byte of mag_f32 / mag_max, or mask_u8 ([count], or [B,count] with mask_per_image), or 0 */
+int mdpt_post_display_prep(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t in_h, int32_t in_w, void* out_bhw, int32_t out_h, int32_t out_w,
+                           void* parts, void* hist_clear, void* stream);
+int mdpt_post_plane_fit(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* sample_xy, int32_t num_samples,
+                        int32_t xy_per_image, void* coef_out, void* stream);
+int mdpt_post_plane_eval(const void* coef, int32_t B, int32_t H, int32_t W, void* out_f32, void* stream);
+int mdpt_post_plane_minmax(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* coef, double factor,
+                           void* vparts, void* stream);
+int mdpt_post_threshold(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* coef, double factor,
+                        const void* vparts, double thresh_min, double thresh_max, int32_t mode, int32_t reverse, void* out, void* hist, void* stream);
+int mdpt_post_edge_mag(const void* in_bhw_f32, int32_t B, int32_t H, int32_t W, const void* parts, const float* blur_weights, int32_t blur_ksize,
+                       void* mag_f32, void* mag_max, void* stream);
+int mdpt_post_edge_mask(const void* mag_f32, const void* mag_max, int32_t B, size_t count, void* out_u8, void* stream);
+int mdpt_post_pack_u24_alpha(const void* in_bhw_f32, int32_t B, size_t count, const void* parts, int32_t lossy, const void* mag_f32, const void* mag_max,
+                             const void* mask_u8, int32_t mask_per_image, void* out_bgra, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

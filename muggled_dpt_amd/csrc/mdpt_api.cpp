@@ -1006,6 +1006,92 @@ int mdpt_post_colorize(const void* in_u8, int32_t B, size_t count, const void* e
     return 0;
 }
 
+// ---- still-image display tail (run_image.py:185-195, 323-343, 350-358) and the viewer's edge alpha (run_3dviewer.py:455-505, 576-593)
+static int check_batch_hw(int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || B > 65535 || H <= 0 || W <= 0) return fail(MDPT_E_INVALID, "bad size %dx%dx%d", B, H, W);
+    return 0;
+}
+
+int mdpt_post_display_prep(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t in_h, int32_t in_w, void* out_bhw, int32_t out_h, int32_t out_w,
+                           void* parts, void* hist_clear, void* stream) {
+    if (!in_bhw || !out_bhw || !parts) return fail(MDPT_E_INVALID, "null argument");
+    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
+    CHK(check_batch_hw(B, in_h, in_w));
+    CHK(check_batch_hw(B, out_h, out_w));
+    CHK(mdpt_launch_post_display_prep(in_bhw, in_dtype, B, in_h, in_w, out_bhw, out_h, out_w, (unsigned*)parts, (unsigned*)hist_clear, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_plane_fit(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* sample_xy, int32_t num_samples,
+                        int32_t xy_per_image, void* coef_out, void* stream) {
+    if (!in_bhw || !sample_xy || !coef_out) return fail(MDPT_E_INVALID, "null argument");
+    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
+    CHK(check_batch_hw(B, H, W));
+    if (num_samples <= 0) return fail(MDPT_E_INVALID, "bad sample count %d", num_samples);
+    CHK(mdpt_launch_post_plane_fit(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const int*)sample_xy, num_samples,
+                                   xy_per_image ? (size_t)num_samples * 2 : 0, (double*)coef_out, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_plane_eval(const void* coef, int32_t B, int32_t H, int32_t W, void* out_f32, void* stream) {
+    if (!coef || !out_f32) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_batch_hw(B, H, W));
+    CHK(mdpt_launch_post_plane_eval((const double*)coef, B, H, W, (float*)out_f32, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_plane_minmax(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* coef, double factor,
+                           void* vparts, void* stream) {
+    if (!in_bhw || !parts || !coef || !vparts) return fail(MDPT_E_INVALID, "null argument");
+    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
+    CHK(check_batch_hw(B, H, W));
+    CHK(mdpt_launch_post_plane_minmax(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const double*)coef, factor, (double*)vparts, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_threshold(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* coef, double factor,
+                        const void* vparts, double thresh_min, double thresh_max, int32_t mode, int32_t reverse, void* out, void* hist, void* stream) {
+    if (!in_bhw || !parts || !coef || !vparts || !out) return fail(MDPT_E_INVALID, "null argument");
+    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
+    CHK(check_batch_hw(B, H, W));
+    if (mode != MDPT_POST_F32 && mode != MDPT_POST_U8) return fail(MDPT_E_INVALID, "threshold mode must be MDPT_POST_F32 or MDPT_POST_U8, got %d", mode);
+    if (mode == MDPT_POST_U8 && reverse) return fail(MDPT_E_INVALID, "the uint8 threshold pass does not reverse (255 - x follows the equalization)");
+    if (!(thresh_min <= thresh_max)) return fail(MDPT_E_INVALID, "threshold out of order: [%g, %g]", thresh_min, thresh_max);
+    const double delta = thresh_max - thresh_min > 0.001 ? thresh_max - thresh_min : 0.001;  // run_image.py:329
+    CHK(mdpt_launch_post_threshold(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const double*)coef, factor, (const double*)vparts, thresh_min, delta,
+                                   mode, reverse != 0, out, mode == MDPT_POST_U8 ? (unsigned*)hist : nullptr, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_edge_mag(const void* in_bhw_f32, int32_t B, int32_t H, int32_t W, const void* parts, const float* blur_weights, int32_t blur_ksize,
+                       void* mag_f32, void* mag_max, void* stream) {
+    if (!in_bhw_f32 || !blur_weights || !mag_f32 || !mag_max) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_batch_hw(B, H, W));
+    if (blur_ksize < 1 || blur_ksize > 15 || blur_ksize % 2 == 0) return fail(MDPT_E_INVALID, "blur kernel size must be odd, 1..15, got %d", blur_ksize);
+    const int pad = blur_ksize / 2, min_side = pad + 1 > 2 ? pad + 1 : 2;  // reflect padding needs pad < side (blur pad, Sobel pad 1)
+    if (H < min_side || W < min_side) return fail(MDPT_E_INVALID, "map %dx%d is too small for reflect padding (sides of at least %d)", H, W, min_side);
+    CHK(mdpt_launch_post_edge_mag((const float*)in_bhw_f32, B, H, W, (const unsigned*)parts, blur_weights, blur_ksize, (float*)mag_f32, (unsigned*)mag_max,
+                                  (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_edge_mask(const void* mag_f32, const void* mag_max, int32_t B, size_t count, void* out_u8, void* stream) {
+    if (!mag_f32 || !mag_max || !out_u8 || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    CHK(mdpt_launch_post_edge_mask((const float*)mag_f32, (const unsigned*)mag_max, B, count, (unsigned char*)out_u8, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_pack_u24_alpha(const void* in_bhw_f32, int32_t B, size_t count, const void* parts, int32_t lossy, const void* mag_f32, const void* mag_max,
+                             const void* mask_u8, int32_t mask_per_image, void* out_bgra, void* stream) {
+    if (!in_bhw_f32 || !out_bgra || count == 0 || (mag_f32 && !mag_max)) return fail(MDPT_E_INVALID, "null argument / empty input");
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    if (mag_f32 && mask_u8) return fail(MDPT_E_INVALID, "alpha is either the edge mask or the caller's mask");
+    CHK(mdpt_launch_post_pack_u24((const float*)in_bhw_f32, B, count, (const unsigned*)parts, lossy != 0, (const float*)mag_f32, (const unsigned*)mag_max,
+                                  (const unsigned char*)mask_u8, mask_per_image ? count : 0, (unsigned char*)out_bgra, (hipStream_t)stream));
+    return 0;
+}
+
 // ---- the same for images of different sizes: one run per image, MDPT_POST_RUNS images per launch; per-image buffers advance by the images before
 static int check_images(const void* const* in, const int32_t* hw, int32_t B, const char* what) {
     if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);

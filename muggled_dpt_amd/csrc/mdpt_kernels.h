@@ -217,6 +217,22 @@ int mdpt_launch_post_hist(const unsigned char* in, int B, size_t n, unsigned* hi
 int mdpt_launch_post_eq_lut(const unsigned* hist, int B, const int* bin_of, int vmin, int vmax, unsigned char* lut, hipStream_t stream);
 int mdpt_launch_post_colorize(const PostRunTable& t, const unsigned char* eq, const unsigned char* cmap, int channels, unsigned char* out,
                               hipStream_t stream);
+// still-image display tail and edge alpha (uniform batches): vparts = [B, MDPT_POST_SEG_PARTS, 2] fp64 {min, max} partials of the plane-removed
+// map, coef = [B, 4] fp64 plane {nx, ny, nz, d}, mag = [B, h, w] fp32 Sobel magnitude, mag_max = [B] fp32 bits (cleared by the edge launcher)
+int mdpt_launch_post_display_prep(const void* in, int dt, int B, int ih, int iw, void* out, int oh, int ow, unsigned* parts, unsigned* hist_clear,
+                                  hipStream_t stream);
+int mdpt_launch_post_plane_fit(const void* in, int dt, int B, int h, int w, const unsigned* parts, const int* xy, int N, size_t xy_stride, double* coef,
+                               hipStream_t stream);
+int mdpt_launch_post_plane_eval(const double* coef, int B, int h, int w, float* out, hipStream_t stream);
+int mdpt_launch_post_plane_minmax(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, double* vparts,
+                                  hipStream_t stream);
+int mdpt_launch_post_threshold(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, const double* vparts,
+                               double tmin, double delta, int mode, int reverse, void* out, unsigned* hist, hipStream_t stream);
+int mdpt_launch_post_edge_mag(const float* in, int B, int h, int w, const unsigned* parts, const float* blur_w, int ksize, float* mag, unsigned* mag_max,
+                              hipStream_t stream);
+int mdpt_launch_post_edge_mask(const float* mag, const unsigned* mag_max, int B, size_t n, unsigned char* out, hipStream_t stream);
+int mdpt_launch_post_pack_u24(const float* in, int B, size_t n, const unsigned* parts, int lossy, const float* mag, const unsigned* mag_max,
+                              const unsigned char* mask, size_t mask_stride, unsigned char* out, hipStream_t stream);
 
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);

@@ -168,6 +168,20 @@ __device__ __forceinline__ void block_minmax_part(float lo, float hi, bool saw_n
     }
 }
 
+// F.interpolate(bilinear) of image `base` (ih x iw, dtype dt) at output pixel (oy, ox), rounded to dt (the map scale_prediction returns).
+// scale_bilinear_kernel's arithmetic as the compiler contracts it there (its gfx950 code: fma for the source position, one fma and one
+// product per row, two products and an add across the rows), spelled out with _rn intrinsics so that no contraction choice here can differ
+__device__ __forceinline__ float bilinear_at(const void* in, size_t base, int dt, int ih, int iw, float sy, float sx, int oy, int ox) {
+    const float fy = fmaxf(__fmaf_rn(sy, (float)oy + 0.5f, -0.5f), 0.0f), fx = fmaxf(__fmaf_rn(sx, (float)ox + 0.5f, -0.5f), 0.0f);
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + (y0 < ih - 1), x1 = x0 + (x0 < iw - 1);
+    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    const float p00 = ld_dt(in, base + (size_t)y0 * iw + x0, dt), p01 = ld_dt(in, base + (size_t)y0 * iw + x1, dt);
+    const float p10 = ld_dt(in, base + (size_t)y1 * iw + x0, dt), p11 = ld_dt(in, base + (size_t)y1 * iw + x1, dt);
+    const float top = __fmaf_rn(p01, lx, __fmul_rn(p00, 1.0f - lx)), bot = __fmaf_rn(p10, 1.0f - lx, __fmul_rn(p11, lx));
+    return round_dt(__fadd_rn(__fmul_rn(1.0f - ly, top), __fmul_rn(ly, bot)), dt);
+}
+
 // out == null: min/max of each input image. Otherwise F.interpolate(bilinear) of each image to its oh x ow (the arithmetic of scale_bilinear_kernel),
 // rounded to the input's dtype, stored as fp32 at its place of the packed out, min/max of that. hist_clear != null: zero the [B,256] histogram the
 // next kernel accumulates into.
@@ -188,18 +202,7 @@ __global__ __launch_bounds__(256) void seg_scale_minmax_kernel(const PostRunTabl
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         float v;
         if (scale) {
-            const int ox = (int)(i % ow), oy = (int)(i / ow);
-            // scale_bilinear_kernel's arithmetic as the compiler contracts it there (its gfx950 code: fma for the source position, one fma and one
-            // product per row, two products and an add across the rows), spelled out with _rn intrinsics so that no contraction choice here can differ
-            const float fy = fmaxf(__fmaf_rn(sy, (float)oy + 0.5f, -0.5f), 0.0f), fx = fmaxf(__fmaf_rn(sx, (float)ox + 0.5f, -0.5f), 0.0f);
-            const int y0 = (int)fy, x0 = (int)fx;
-            const int y1 = y0 + (y0 < ih - 1), x1 = x0 + (x0 < iw - 1);
-            const float ly = fy - (float)y0, lx = fx - (float)x0;
-            const float p00 = ld_dt(in, in_base + (size_t)y0 * iw + x0, in_dt), p01 = ld_dt(in, in_base + (size_t)y0 * iw + x1, in_dt);
-            const float p10 = ld_dt(in, in_base + (size_t)y1 * iw + x0, in_dt), p11 = ld_dt(in, in_base + (size_t)y1 * iw + x1, in_dt);
-            const float top = __fmaf_rn(p01, lx, __fmul_rn(p00, 1.0f - lx)), bot = __fmaf_rn(p10, 1.0f - lx, __fmul_rn(p11, lx));
-            v = __fadd_rn(__fmul_rn(1.0f - ly, top), __fmul_rn(ly, bot));
-            v = round_dt(v, in_dt);
+            v = bilinear_at(in, in_base, in_dt, ih, iw, sy, sx, (int)(i / ow), (int)(i % ow));
             out[out_base + i] = v;
         } else {
             v = ld_dt(in, in_base + i, in_dt);
@@ -357,6 +360,362 @@ inline bool table_extent(const PostRunTable& t, int& B, size_t& max_in, size_t& 
     return true;
 }
 
+// ---- still-image display tail (the reference's run_image.py:185-195, 323-343, 350-358) and the 3D viewer's edge alpha (run_3dviewer.py:455-505).
+// Every kernel takes a uniform batch: image b is [h, w] at element b h w; grids are (parts, B) or one block per image. The arithmetic whose order the
+// reference fixes (numpy's fp64, torch's per-op rounding) is written out with contraction off.
+
+__device__ __forceinline__ void st_dt(void* p, size_t i, float v, int dt) {
+    if (dt == MDPT_DT_BF16) ((__bf16*)p)[i] = (__bf16)v;
+    else if (dt == MDPT_DT_F16) ((_Float16*)p)[i] = (_Float16)v;
+    else ((float*)p)[i] = v;
+}
+
+// image b's {min, max} from its SEG_PARTS partials (seg_u8_hist_kernel's reduction); a block-wide call, every thread gets the pair
+__device__ __forceinline__ void seg_range(const unsigned* __restrict__ parts, int b, float& lo, float& hi) {
+    __shared__ unsigned smm[2];
+    if (threadIdx.x < 64) {
+        unsigned mn = parts[((size_t)b * SEG_PARTS + threadIdx.x) * 2], mx = parts[((size_t)b * SEG_PARTS + threadIdx.x) * 2 + 1];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            mn = min(mn, (unsigned)__shfl_xor((int)mn, o));
+            mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
+        }
+        if (threadIdx.x == 0) { smm[0] = mn; smm[1] = mx; }
+    }
+    __syncthreads();
+    lo = ord2f(smm[0]);
+    hi = ord2f(smm[1]);
+}
+
+// normalize_01 of a map stored in dtype dt as torch evaluates it in that dtype: (x - min) and (max - min) each rounded to dt, then the quotient
+__device__ __forceinline__ float norm01_dt(float x, float lo, float hi, int dt) {
+#pragma clang fp contract(off)
+    return round_dt(round_dt(x - lo, dt) / round_dt(hi - lo, dt), dt);
+}
+
+// numpy's plane image at pixel (x, y): -(d + nx x + ny y) / nz in fp64 (plane_fit.py generate_image_from_plane_normal); c = {nx, ny, nz, d}
+__device__ __forceinline__ double plane_at(const double* c, int x, int y) {
+#pragma clang fp contract(off)
+    return -(c[3] + c[0] * (double)x + c[1] * (double)y) / c[2];
+}
+
+// d = -(nx mx + ny my + nz mz), numpy's order
+__device__ __forceinline__ double plane_offset(const double* n, double mx, double my, double mz) {
+#pragma clang fp contract(off)
+    return -1.0 * (n[0] * mx + n[1] * my + n[2] * mz);
+}
+
+// torch's reflect padding index (no edge repeat) for offsets up to n - 1 past either end; clamped so that no index leaves the map
+__device__ __forceinline__ int reflect_idx(int v, int n) {
+    v = v < 0 ? -v : (v >= n ? 2 * (n - 1) - v : v);
+    return v < 0 ? 0 : (v >= n ? n - 1 : v);
+}
+
+// K doubles summed over the block (256 threads); every thread gets the sums
+template <int K>
+__device__ __forceinline__ void block_sum_f64(double (&v)[K]) {
+    __shared__ double s[4][K];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < K; ++k) s[wave][k] = v[k];
+    __syncthreads();
+    for (int k = 0; k < K; ++k) v[k] = ((s[0][k] + s[1][k]) + s[2][k]) + s[3][k];
+    __syncthreads();
+}
+
+// remove_inf_tensor(scale_prediction(x)) per image: the bilinear resize of scale_prediction (an identity copy when the size does not change, as
+// torch's upsample does), rounded to the input dtype, +-inf -> 0, stored in that dtype; and the image's min/max partials of the result
+__global__ __launch_bounds__(256) void disp_prep_kernel(const void* __restrict__ in, int dt, int ih, int iw, void* __restrict__ out, int oh, int ow,
+                                                        unsigned* __restrict__ parts, unsigned* __restrict__ hist_clear) {
+    const int b = blockIdx.y;
+    if (hist_clear && blockIdx.x == 0) hist_clear[(size_t)b * 256 + threadIdx.x] = 0u;
+    const bool same = ih == oh && iw == ow;
+    const size_t n = (size_t)oh * ow, in_base = (size_t)b * ih * iw;
+    const float sy = (float)ih / (float)oh, sx = (float)iw / (float)ow;
+    float lo = INFINITY, hi = -INFINITY;
+    bool saw_nan = false, any = false;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float v = same ? ld_dt(in, in_base + i, dt) : bilinear_at(in, in_base, dt, ih, iw, sy, sx, (int)(i / ow), (int)(i % ow));
+        if (isinf(v)) v = 0.0f;
+        st_dt(out, (size_t)b * n + i, v, dt);
+        any = true;
+        saw_nan |= v != v;
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+    block_minmax_part(lo, hi, saw_nan, any, parts + ((size_t)b * SEG_PARTS + blockIdx.x) * 2);
+}
+
+// the eigenvector of the smallest eigenvalue of a symmetric 3x3 matrix, by cyclic Jacobi with a fixed number of sweeps (quadratic convergence:
+// 3x3 in fp64 is converged after 4 or 5). A zero off-diagonal element is skipped, so a diagonal matrix (a constant map: z row and column zero)
+// keeps its axes. Ties go to the later axis, so a degenerate fit prefers the z normal (a constant plane) over an x / y one.
+__device__ void jacobi3_min_eigvec(double a[3][3], double n[3]) {
+    double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    for (int sweep = 0; sweep < 10; ++sweep) {
+        for (int k = 0; k < 3; ++k) {
+            const int p = k == 2 ? 1 : 0, q = k == 0 ? 1 : 2;
+            const double apq = a[p][q];
+            if (apq == 0.0) continue;
+            const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+            const double t = fabs(theta) > 1e150 ? 0.5 / theta : (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+            for (int r = 0; r < 3; ++r) {
+                const double arp = a[r][p], arq = a[r][q];
+                a[r][p] = c * arp - s * arq;
+                a[r][q] = s * arp + c * arq;
+            }
+            for (int r = 0; r < 3; ++r) {
+                const double apr = a[p][r], aqr = a[q][r];
+                a[p][r] = c * apr - s * aqr;
+                a[q][r] = s * apr + c * aqr;
+            }
+            for (int r = 0; r < 3; ++r) {
+                const double vrp = v[r][p], vrq = v[r][q];
+                v[r][p] = c * vrp - s * vrq;
+                v[r][q] = s * vrp + c * vrq;
+            }
+        }
+    }
+    int m = 0;
+    for (int k = 1; k < 3; ++k)
+        if (a[k][k] <= a[m][m]) m = k;
+    for (int r = 0; r < 3; ++r) n[r] = v[r][m];
+}
+
+// plane of best fit of image b (one block per image; plane_fit.py get_xyz_samples / find_plane_normal / generate_image_from_plane_normal):
+// z at the N sample points (parts != null: of normalize_01(image b) in dtype dt), the known x / y means (w-1)/2, (h-1)/2 and the sample z mean,
+// the 3x3 Gram matrix of the centred samples in fp64, its smallest eigenvector (numpy's smallest right singular vector, up to sign) -> coef[b] =
+// {nx, ny, nz, d}, d = -(nx mx + ny my + nz mz). Sample points are clamped into the map.
+__global__ __launch_bounds__(256) void plane_fit_kernel(const void* __restrict__ in, int dt, int h, int w, const unsigned* __restrict__ parts,
+                                                        const int* __restrict__ xy, int N, size_t xy_stride, double* __restrict__ coef) {
+    const int b = blockIdx.x;
+    float lo = 0.0f, hi = 1.0f;
+    if (parts) seg_range(parts, b, lo, hi);
+    const int* pts = xy + (size_t)b * xy_stride;
+    const size_t base = (size_t)b * h * w;
+    auto z_at = [&](int k, int& x, int& y) -> double {
+        x = min(max(pts[2 * k], 0), w - 1);
+        y = min(max(pts[2 * k + 1], 0), h - 1);
+        const float z = ld_dt(in, base + (size_t)y * w + x, dt);
+        return (double)(parts ? norm01_dt(z, lo, hi, dt) : z);
+    };
+    double zs[1] = {0.0};
+    for (int k = threadIdx.x; k < N; k += blockDim.x) {
+        int x, y;
+        zs[0] += z_at(k, x, y);
+    }
+    block_sum_f64<1>(zs);
+    const double mx = (w - 1) * 0.5, my = (h - 1) * 0.5, mz = zs[0] / N;
+    double g[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // xx xy xz yy yz zz
+    for (int k = threadIdx.x; k < N; k += blockDim.x) {
+        int x, y;
+        const double cz = z_at(k, x, y) - mz, cx = x - mx, cy = y - my;
+        g[0] += cx * cx; g[1] += cx * cy; g[2] += cx * cz;
+        g[3] += cy * cy; g[4] += cy * cz; g[5] += cz * cz;
+    }
+    block_sum_f64<6>(g);
+    if (threadIdx.x != 0) return;
+    double a[3][3] = {{g[0], g[1], g[2]}, {g[1], g[3], g[4]}, {g[2], g[4], g[5]}}, nrm[3];
+    jacobi3_min_eigvec(a, nrm);
+    double* c = coef + (size_t)b * 4;
+    c[0] = nrm[0];
+    c[1] = nrm[1];
+    c[2] = nrm[2];
+    c[3] = plane_offset(nrm, mx, my, mz);
+}
+
+// the plane image of coef[b], rounded to fp32
+__global__ __launch_bounds__(256) void plane_eval_kernel(const double* __restrict__ coef, int h, int w, float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const double* c = coef + (size_t)b * 4;
+    const size_t n = (size_t)h * w;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        out[(size_t)b * n + i] = (float)plane_at(c, (int)(i % w), (int)(i / w));
+}
+
+// v = dn - factor * plane in fp64 (numpy: the fp32 map minus the fp64 plane), dn = normalize_01(image b) in dtype dt
+__device__ __forceinline__ double plane_removed(float x, float lo, float hi, int dt, const double* c, double factor, size_t i, int w) {
+#pragma clang fp contract(off)
+    return (double)norm01_dt(x, lo, hi, dt) - plane_at(c, (int)(i % w), (int)(i / w)) * factor;
+}
+
+// per-image fp64 {min, max} partials of v: vparts[b][part] (a share without pixels is neutral; a NaN pins NaN, numpy's min / max propagate it)
+__global__ __launch_bounds__(256) void plane_minmax_kernel(const void* __restrict__ in, int dt, int h, int w, const unsigned* __restrict__ parts,
+                                                           const double* __restrict__ coef, double factor, double* __restrict__ vparts) {
+    const int b = blockIdx.y;
+    float lo, hi;
+    seg_range(parts, b, lo, hi);
+    const double* c = coef + (size_t)b * 4;
+    const size_t n = (size_t)h * w, base = (size_t)b * n;
+    double vlo = INFINITY, vhi = -INFINITY;
+    bool saw_nan = false;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const double v = plane_removed(ld_dt(in, base + i, dt), lo, hi, dt, c, factor, i, w);
+        saw_nan |= v != v;
+        vlo = fmin(vlo, v);
+        vhi = fmax(vhi, v);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        vlo = fmin(vlo, __shfl_xor(vlo, o));
+        vhi = fmax(vhi, __shfl_xor(vhi, o));
+    }
+    const bool wave_nan = __any(saw_nan);
+    __shared__ double slo[4], shi[4];
+    __shared__ int snan[4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { slo[wave] = vlo; shi[wave] = vhi; snan[wave] = wave_nan; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        bool any_nan = false;
+        for (int k = 0; k < 4; ++k) { vlo = fmin(vlo, slo[k]); vhi = fmax(vhi, shi[k]); any_nan |= snan[k] != 0; }
+        double* o = vparts + ((size_t)b * SEG_PARTS + blockIdx.x) * 2;
+        o[0] = any_nan ? NAN : vlo;
+        o[1] = any_nan ? NAN : vhi;
+    }
+}
+
+// t = clip((normalize_01(v) - tmin) / delta, 0, 1) in fp64 (run_image.py:331-333, 355-356). Mode 1 (MDPT_POST_U8): round-half-even(255 t) -> uint8
+// (a NaN -> 0), and (hist != null) its 256-bin histogram into hist[b]; mode 0 (MDPT_POST_F32): t, or 1 - t with reverse, -> fp32.
+template <int MODE>
+__global__ __launch_bounds__(256) void threshold_kernel(const void* __restrict__ in, int dt, int h, int w, const unsigned* __restrict__ parts,
+                                                        const double* __restrict__ coef, double factor, const double* __restrict__ vparts,
+                                                        double tmin, double delta, int reverse, void* __restrict__ out, unsigned* __restrict__ hist) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y;
+    __shared__ unsigned bins[256];
+    __shared__ double svr[2];
+    bins[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) {
+        double vlo = INFINITY, vhi = -INFINITY;
+        bool any_nan = false;
+        for (int k = 0; k < SEG_PARTS; ++k) {
+            const double a = vparts[((size_t)b * SEG_PARTS + k) * 2], z = vparts[((size_t)b * SEG_PARTS + k) * 2 + 1];
+            any_nan |= a != a || z != z;
+            vlo = fmin(vlo, a);
+            vhi = fmax(vhi, z);
+        }
+        svr[0] = any_nan ? NAN : vlo;
+        svr[1] = any_nan ? NAN : vhi;
+    }
+    float lo, hi;
+    seg_range(parts, b, lo, hi);  // (its __syncthreads also publishes bins and svr)
+    const double vlo = svr[0], vrange = svr[1] - svr[0];
+    const double* c = coef + (size_t)b * 4;
+    const size_t n = (size_t)h * w, base = (size_t)b * n;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const double v = (plane_removed(ld_dt(in, base + i, dt), lo, hi, dt, c, factor, i, w) - vlo) / vrange;
+        double t = (v - tmin) / delta;
+        t = t != t ? t : (t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t));
+        if (MODE == 1) {
+            const int q = t == t ? (int)rint(255.0 * t) : 0;
+            ((unsigned char*)out)[base + i] = (unsigned char)q;
+            if (hist) atomicAdd(&bins[q], 1u);
+        } else {
+            ((float*)out)[base + i] = (float)(reverse ? 1.0 - t : t);
+        }
+    }
+    if (MODE != 1 || !hist) return;
+    __syncthreads();
+    if (bins[threadIdx.x]) atomicAdd(hist + (size_t)b * 256 + threadIdx.x, bins[threadIdx.x]);
+}
+
+// ---- edge alpha (run_3dviewer.py:455-505): blur = conv(x, gauss, reflect pad p), (dx, dy) = conv(blur, sobel, reflect pad 1), mag = sqrt(dx^2 + dy^2)
+constexpr int EDGE_TILE = 16;
+constexpr int EDGE_MAX_PAD = 7;
+struct EdgeBlur { float w[(2 * EDGE_MAX_PAD + 1) * (2 * EDGE_MAX_PAD + 1)]; int ksize; };
+
+// one 16x16 tile of image b per block: the input tile with a (1 + p)-pixel halo in LDS (each LDS element the input at the reflected coordinate),
+// the blurred tile with a 1-pixel halo (each at the reflected blurred coordinate, so the Sobel halo reflects on the blurred map as torch pads it),
+// then the Sobel magnitude -> mag[b] (blur and Sobel in fp64: the Sobel differences neighbouring blurred values of up to ~k^2 times the map, which
+// leaves fp32 sums a few 1e-3 of a byte off at 1080p; fp64 keeps the bytes off the reference's only at rounding ties), and the image's max through an atomicMax on the bits of the (non-negative) fp32 magnitudes. parts != null:
+// the map is normalize_01(x) in fp32 first (normalize_kernel's arithmetic).
+__global__ __launch_bounds__(256) void edge_mag_kernel(const float* __restrict__ in, int h, int w, const unsigned* __restrict__ parts, const EdgeBlur blur,
+                                                       float* __restrict__ mag, unsigned* __restrict__ mag_max) {
+    constexpr int BT = EDGE_TILE + 2, RMAX = BT + 2 * EDGE_MAX_PAD;
+    __shared__ float sx[RMAX * RMAX];
+    __shared__ double sb[BT * BT];
+    const int b = blockIdx.z, t = threadIdx.x;
+    float lo = 0.0f, hi = 1.0f;
+    if (parts) seg_range(parts, b, lo, hi);
+    const float range = hi - lo;
+    const int ks = blur.ksize, p = ks / 2, R = BT + 2 * p;
+    const int y0 = blockIdx.y * EDGE_TILE, x0 = blockIdx.x * EDGE_TILE;
+    const float* img = in + (size_t)b * h * w;
+    for (int e = t; e < R * R; e += 256) {
+        const int vy = y0 - 1 - p + e / R, vx = x0 - 1 - p + e % R;
+        const float v = img[(size_t)reflect_idx(vy, h) * w + reflect_idx(vx, w)];
+        sx[e] = parts ? (v - lo) / range : v;
+    }
+    __syncthreads();
+    for (int e = t; e < BT * BT; e += 256) {
+        const int gy = y0 - 1 + e / BT, gx = x0 - 1 + e % BT;
+        double acc = 0.0;
+        if (gy <= h && gx <= w) {  // (rows / columns past h / w are no Sobel neighbour of a pixel of the map)
+            const int ry = reflect_idx(gy, h) - y0 + 1, rx = reflect_idx(gx, w) - x0 + 1;  // in [0, BT): see the comment above
+            for (int ky = 0; ky < ks; ++ky)
+                for (int kx = 0; kx < ks; ++kx) acc = fma((double)blur.w[ky * ks + kx], (double)sx[(ry + ky) * R + rx + kx], acc);
+        }
+        sb[e] = acc;
+    }
+    __syncthreads();
+    const int ty = t / EDGE_TILE, tx = t % EDGE_TILE, y = y0 + ty, x = x0 + tx;
+    float m = 0.0f;
+    if (y < h && x < w) {
+        const double* s = sb + ty * BT + tx;  // s[i BT + j] = blurred at (reflect(y + i - 1), reflect(x + j - 1))
+        const double dy = 3.0 * (s[0] - s[2 * BT]) + 10.0 * (s[1] - s[2 * BT + 1]) + 3.0 * (s[2] - s[2 * BT + 2]);
+        const double dx = 3.0 * (s[0] - s[2]) + 10.0 * (s[BT] - s[BT + 2]) + 3.0 * (s[2 * BT] - s[2 * BT + 2]);
+        m = (float)sqrt(dx * dx + dy * dy);
+        mag[(size_t)b * h * w + (size_t)y * w + x] = m;
+    }
+    unsigned bits = m != m ? 0x7fffffffu : __float_as_uint(m);  // a NaN wins the max (torch's max propagates it)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bits = max(bits, (unsigned)__shfl_xor((int)bits, o));
+    if ((t & 63) == 0) atomicMax(mag_max + b, bits);
+}
+
+// ~round(255 mag / max) (torch: 255 * mag, then / max, round half to even, .byte(), bitwise_not); max 0 (a flat map) or NaN -> 0 before the not: 255
+__device__ __forceinline__ unsigned char edge_byte(float m, float mx) {
+#pragma clang fp contract(off)
+    const float r = rintf((255.0f * m) / mx);
+    return (unsigned char)(255 - (r == r ? (int)fminf(fmaxf(r, 0.0f), 255.0f) : 0));
+}
+
+__global__ __launch_bounds__(256) void edge_mask_kernel(const float* __restrict__ mag, const unsigned* __restrict__ mag_max, size_t n,
+                                                        unsigned char* __restrict__ out) {
+    const int b = blockIdx.y;
+    const float mx = __uint_as_float(mag_max[b]);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        out[(size_t)b * n + i] = edge_byte(mag[(size_t)b * n + i], mx);
+}
+
+// pack_depth_u24 per image (normalize_kernel<2>'s arithmetic with image b's min/max from parts; parts == null: metric, as is) with the alpha byte
+// in the same pass: the edge byte of mag (mag != null), the caller's mask (mask != null; per image or one for all), or 0
+__global__ __launch_bounds__(256) void pack_u24_kernel(const float* __restrict__ in, size_t n, const unsigned* __restrict__ parts, int lossy,
+                                                       const float* __restrict__ mag, const unsigned* __restrict__ mag_max,
+                                                       const unsigned char* __restrict__ mask, size_t mask_stride, uchar4* __restrict__ out) {
+    const int b = blockIdx.y;
+    float lo = 0.0f, hi = 1.0f;
+    if (parts) seg_range(parts, b, lo, hi);
+    const float range = hi - lo;
+    const float mx = mag ? __uint_as_float(mag_max[b]) : 0.0f;
+    const size_t base = (size_t)b * n;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float v = parts ? (in[base + i] - lo) / range : in[base + i];
+        v = v == v ? fminf(fmaxf(v, 0.0f), 1.0f) : 0.0f;
+        const int q = (int)rintf(16777215.0f * v);
+        uchar4 px;
+        px.x = lossy ? 0 : (unsigned char)(q & 255);
+        px.y = lossy ? 0 : (unsigned char)((q >> 8) & 255);
+        px.z = (unsigned char)((q >> 16) & 255);
+        px.w = mag ? edge_byte(mag[base + i], mx) : (mask ? mask[(size_t)b * mask_stride + i] : (unsigned char)0);
+        out[base + i] = px;
+    }
+}
+
 }  // namespace
 
 int mdpt_launch_post_minmax(const float* in, size_t n, float* minmax_out, unsigned* scratch2, hipStream_t stream) {
@@ -422,5 +781,71 @@ int mdpt_launch_post_colorize(const PostRunTable& t, const unsigned char* eq, co
     if (!table_extent(t, B, n, max_out)) return (int)hipErrorInvalidValue;
     MdptProfScope prof("colorize_kernel", 0.0, stream);
     hipLaunchKernelGGL(colorize_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, t, eq, cmap, channels, out);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_display_prep(const void* in, int dt, int B, int ih, int iw, void* out, int oh, int ow, unsigned* parts, unsigned* hist_clear,
+                                  hipStream_t stream) {
+    MdptProfScope prof("disp_prep_kernel", 0.0, stream);
+    hipLaunchKernelGGL(disp_prep_kernel, dim3(SEG_PARTS, B), dim3(256), 0, stream, in, dt, ih, iw, out, oh, ow, parts, hist_clear);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_plane_fit(const void* in, int dt, int B, int h, int w, const unsigned* parts, const int* xy, int N, size_t xy_stride, double* coef,
+                               hipStream_t stream) {
+    MdptProfScope prof("plane_fit_kernel", 0.0, stream);
+    hipLaunchKernelGGL(plane_fit_kernel, dim3(B), dim3(256), 0, stream, in, dt, h, w, parts, xy, N, xy_stride, coef);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_plane_eval(const double* coef, int B, int h, int w, float* out, hipStream_t stream) {
+    const size_t n = (size_t)h * w;
+    MdptProfScope prof("plane_eval_kernel", 0.0, stream);
+    hipLaunchKernelGGL(plane_eval_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, coef, h, w, out);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_plane_minmax(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, double* vparts,
+                                  hipStream_t stream) {
+    MdptProfScope prof("plane_minmax_kernel", 0.0, stream);
+    hipLaunchKernelGGL(plane_minmax_kernel, dim3(SEG_PARTS, B), dim3(256), 0, stream, in, dt, h, w, parts, coef, factor, vparts);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_threshold(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, const double* vparts,
+                               double tmin, double delta, int mode, int reverse, void* out, unsigned* hist, hipStream_t stream) {
+    const size_t n = (size_t)h * w;
+    const dim3 grid(grid_for(n) < 256 ? grid_for(n) : 256, B);
+    MdptProfScope prof("threshold_kernel", 0.0, stream);
+    if (mode == 1) hipLaunchKernelGGL(threshold_kernel<1>, grid, dim3(256), 0, stream, in, dt, h, w, parts, coef, factor, vparts, tmin, delta, reverse, out, hist);
+    else hipLaunchKernelGGL(threshold_kernel<0>, grid, dim3(256), 0, stream, in, dt, h, w, parts, coef, factor, vparts, tmin, delta, reverse, out, hist);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_edge_mag(const float* in, int B, int h, int w, const unsigned* parts, const float* blur_w, int ksize, float* mag, unsigned* mag_max,
+                              hipStream_t stream) {
+    if (ksize < 1 || ksize > 2 * EDGE_MAX_PAD + 1 || ksize % 2 == 0) return (int)hipErrorInvalidValue;
+    EdgeBlur blur{};
+    for (int i = 0; i < ksize * ksize; ++i) blur.w[i] = blur_w[i];
+    blur.ksize = ksize;
+    hipError_t e = hipMemsetAsync(mag_max, 0, sizeof(unsigned) * (size_t)B, stream);
+    if (e != hipSuccess) return (int)e;
+    MdptProfScope prof("edge_mag_kernel", 0.0, stream);
+    hipLaunchKernelGGL(edge_mag_kernel, dim3((w + EDGE_TILE - 1) / EDGE_TILE, (h + EDGE_TILE - 1) / EDGE_TILE, B), dim3(256), 0, stream, in, h, w, parts,
+                       blur, mag, mag_max);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_edge_mask(const float* mag, const unsigned* mag_max, int B, size_t n, unsigned char* out, hipStream_t stream) {
+    MdptProfScope prof("edge_mask_kernel", 0.0, stream);
+    hipLaunchKernelGGL(edge_mask_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, mag, mag_max, n, out);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_pack_u24(const float* in, int B, size_t n, const unsigned* parts, int lossy, const float* mag, const unsigned* mag_max,
+                              const unsigned char* mask, size_t mask_stride, unsigned char* out, hipStream_t stream) {
+    MdptProfScope prof("pack_u24_kernel", 0.0, stream);
+    hipLaunchKernelGGL(pack_u24_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, in, n, parts, lossy, mag, mag_max, mask,
+                       mask_stride, (uchar4*)out);
     return (int)hipGetLastError();
 }

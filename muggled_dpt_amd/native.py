@@ -165,6 +165,7 @@ class MdptConfig(ctypes.Structure):
 _VP = ctypes.c_void_p
 _SZ = ctypes.c_size_t
 _I = ctypes.c_int32
+_D = ctypes.c_double
 _VP4 = ctypes.POINTER(ctypes.c_void_p)
 SYMBOLS = {
     "mdpt_abi_version": (ctypes.c_int, []),
@@ -205,6 +206,14 @@ SYMBOLS = {
     "mdpt_post_minmax_images": (ctypes.c_int, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "mdpt_post_u8_hist_images": (ctypes.c_int, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP, _VP]),
     "mdpt_post_colorize_images": (ctypes.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP, _VP]),
+    "mdpt_post_display_prep": (ctypes.c_int, [_VP, _I, _I, _I, _I, _VP, _I, _I, _VP, _VP, _VP]),
+    "mdpt_post_plane_fit": (ctypes.c_int, [_VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _VP]),
+    "mdpt_post_plane_eval": (ctypes.c_int, [_VP, _I, _I, _I, _VP, _VP]),
+    "mdpt_post_plane_minmax": (ctypes.c_int, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _VP]),
+    "mdpt_post_threshold": (ctypes.c_int, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _D, _D, _I, _I, _VP, _VP, _VP]),
+    "mdpt_post_edge_mag": (ctypes.c_int, [_VP, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP]),
+    "mdpt_post_edge_mask": (ctypes.c_int, [_VP, _VP, _I, _SZ, _VP, _VP]),
+    "mdpt_post_pack_u24_alpha": (ctypes.c_int, [_VP, _I, _SZ, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

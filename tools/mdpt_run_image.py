@@ -5,6 +5,8 @@ run_image.py:204-208 does before it opens its window. No display, no OpenCV: ima
 are synthesised; the 8-bit depth map can be saved as .npy (device-side post-processing, muggled_dpt_amd.postprocess).
 Several -i files (of any sizes) run together through DPTModel.inference_images, batched per model tensor size; -o is then a directory
 that receives every image's 8-bit depth map at the image's own size (postprocess.depth_to_color_images).
+For one image, --display saves the still-image demo's BGR frame (postprocess.depth_to_display: --remove_plane, --threshold, --reverse,
+--high_contrast as in run_image.py) and --u24 the 3D viewer's BGRA 24-bit frame with its edge alpha (postprocess.pack_depth_u24_frames).
 
   python tools/mdpt_run_image.py --synthetic vits --size 518 --fp32
   python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i image.npy -o depth_u8.npy
@@ -33,6 +35,12 @@ def main():
     ap.add_argument("-a", "--use_aspect_ratio", action="store_true", help="keep the image aspect ratio (default: square sizing)")
     ap.add_argument("--fp32", action="store_true", help="float32 model = split-bf16 fp32-class arithmetic (default: bfloat16)")
     ap.add_argument("-o", "--output", default=None, help="save the 8-bit depth map (.npy)")
+    ap.add_argument("--remove_plane", type=float, default=0.0, metavar="F", help="single image: remove F times the plane of best fit (run_image.py)")
+    ap.add_argument("--threshold", type=float, nargs=2, default=(0.0, 1.0), metavar=("MIN", "MAX"), help="single image: display threshold window")
+    ap.add_argument("--reverse", action="store_true", help="single image: reverse the display values")
+    ap.add_argument("--high_contrast", action="store_true", help="single image: thresholded histogram equalization")
+    ap.add_argument("--display", default=None, metavar="OUT.npy", help="single image: save the still-image demo's BGR display frame (.npy)")
+    ap.add_argument("--u24", default=None, metavar="OUT.npy", help="single image: save the 3D viewer's BGRA 24-bit frame with edge alpha (.npy)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mdpt_run_image needs an MI355X: no GPU visible (there is no CPU fallback)")
@@ -63,6 +71,15 @@ def main():
     if args.output:
         np.save(args.output, convert_to_uint8(depth).squeeze(0).cpu().numpy())
         print("saved", args.output)
+    if args.display:
+        from muggled_dpt_amd.postprocess import depth_to_display
+        frame = depth_to_display(depth, (img.shape[1], img.shape[0]), args.remove_plane, tuple(args.threshold), args.reverse, args.high_contrast)
+        np.save(args.display, frame[0].cpu().numpy())
+        print("saved", args.display)
+    if args.u24:
+        from muggled_dpt_amd.postprocess import pack_depth_u24_frames
+        np.save(args.u24, pack_depth_u24_frames(depth, is_metric=bool(cfg.get("is_metric", False)))[0].cpu().numpy())
+        print("saved", args.u24)
 
 
 def run_images(model, args, t0):
