@@ -406,6 +406,28 @@ int mdpt_post_edge_mask(const void* mag_f32, const void* mag_max, int32_t B, siz
 int mdpt_post_pack_u24_alpha(const void* in_bhw_f32, int32_t B, size_t count, const void* parts, int32_t lossy, const void* mag_f32, const void* mag_max,
                              const void* mask_u8, int32_t mask_per_image, void* out_bgra, void* stream);
 
+/* Depth masking on the device (additive to ABI v6): the reference's background removal by depth (experiments/depth_masking.py: display :189-199,
+ * :314-332; save :341-361), nothing read back, nothing synchronised. The map side is the still-image chain above (mdpt_post_display_prep ->
+ * mdpt_post_plane_fit -> mdpt_post_plane_minmax: parts, coef, vparts of the prepared map); n = normalize_01(normalize_01(x) - factor * plane) in fp64,
+ * mask = 255 where thresh_min <= value <= thresh_max (a NaN compares false: 0), 255 - mask with invert. cv2.resize(INTER_LINEAR) is restated per
+ * axis: p = float((d + 0.5) * (1 / (out / in)) - 0.5), s = floor(p), a = p - s (fp32); s < 0 -> s = 0, a = 0; s >= in - 1 -> s = in - 1, a = 0.
+ *   mdpt_post_mask_display ........ uniform batch at the display size H x W: mask of n -> mask_out uint8 [B,H,W]; composite_out uint8 [B,H,W,3] =
+ *                                   cv2.resize of photo b (images_bgr uint8 [B,image_h,image_w,3], CV_8U: weights round(2048 w), integer sums,
+ *                                   (v + 2^21) >> 22 - cv2's scalar fixed-point path; its SIMD / IPP paths may differ by 1) where the mask is 255,
+ *                                   CheckerPattern() (169 / 214, 32-px tiles, centred by BORDER_WRAP) where it is 0
+ *   mdpt_post_mask_cutout_images .. B photos of any sizes, each cut out by its own prepared map: maps[k] (map_hw[2k] x map_hw[2k+1], map_dtype) with
+ *                                   its parts[k] / coef[k] / vparts[k] (device pointers of ONE image's rows), photo images[k] (device, uint8
+ *                                   image_hw[2k] x image_hw[2k+1] x 3 BGR): s = cv2.resize(n, photo size) in fp64 (CV_64F: fp32 weights, fp64
+ *                                   sums, rows first), its mask -> out_mask + out_offsets[k] (pixels), BGRA (BGR AND mask, alpha = mask) ->
+ *                                   out_bgra + 4 * out_offsets[k] (4-byte aligned). Host arrays are read during the call only; one launch per
+ *                                   32 photos. */
+int mdpt_post_mask_display(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* coef, double factor,
+                           const void* vparts, double thresh_min, double thresh_max, int32_t invert, const void* images_bgr, int32_t image_h, int32_t image_w,
+                           void* mask_out, void* composite_out, void* stream);
+int mdpt_post_mask_cutout_images(const void* const* maps, const int32_t* map_hw, int32_t map_dtype, const void* const* parts, const void* const* coef,
+                                 const void* const* vparts, double factor, const void* const* images, const int32_t* image_hw, const int64_t* out_offsets,
+                                 int32_t B, double thresh_min, double thresh_max, int32_t invert, void* out_bgra, void* out_mask, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

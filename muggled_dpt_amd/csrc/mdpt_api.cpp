@@ -1164,4 +1164,54 @@ int mdpt_post_colorize_images(const void* in_u8, const int32_t* hw, int32_t B, c
     return 0;
 }
 
+// ---- depth masking (experiments/depth_masking.py:189-199, 314-332 display; :341-361 save)
+static int check_mask_window(double thresh_min, double thresh_max) {
+    if (!(0.0 <= thresh_min && thresh_min <= thresh_max && thresh_max <= 1.0))
+        return fail(MDPT_E_INVALID, "threshold must be (min, max) with 0 <= min <= max <= 1, got [%g, %g]", thresh_min, thresh_max);
+    return 0;
+}
+
+int mdpt_post_mask_display(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* coef, double factor,
+                           const void* vparts, double thresh_min, double thresh_max, int32_t invert, const void* images_bgr, int32_t image_h, int32_t image_w,
+                           void* mask_out, void* composite_out, void* stream) {
+    if (!in_bhw || !parts || !coef || !vparts || !images_bgr || !mask_out || !composite_out) return fail(MDPT_E_INVALID, "null argument");
+    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
+    CHK(check_batch_hw(B, H, W));
+    CHK(check_batch_hw(B, image_h, image_w));
+    CHK(check_mask_window(thresh_min, thresh_max));
+    CHK(mdpt_launch_post_mask_display(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const double*)coef, factor, (const double*)vparts, thresh_min,
+                                      thresh_max, invert != 0, (const unsigned char*)images_bgr, image_h, image_w, (unsigned char*)mask_out,
+                                      (unsigned char*)composite_out, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_mask_cutout_images(const void* const* maps, const int32_t* map_hw, int32_t map_dtype, const void* const* parts, const void* const* coef,
+                                 const void* const* vparts, double factor, const void* const* images, const int32_t* image_hw, const int64_t* out_offsets,
+                                 int32_t B, double thresh_min, double thresh_max, int32_t invert, void* out_bgra, void* out_mask, void* stream) {
+    if (!maps || !map_hw || !parts || !coef || !vparts || !images || !image_hw || !out_offsets || !out_bgra || !out_mask)
+        return fail(MDPT_E_INVALID, "null argument");
+    if (((uintptr_t)out_bgra & 3) != 0) return fail(MDPT_E_INVALID, "the BGRA output must be 4-byte aligned");
+    if (!post_dtype_ok(map_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", map_dtype);
+    CHK(check_mask_window(thresh_min, thresh_max));
+    CHK(check_images(maps, map_hw, B, "map"));
+    CHK(check_images(images, image_hw, B, "image"));
+    for (int k = 0; k < B; ++k) {
+        if (!parts[k] || !coef[k] || !vparts[k]) return fail(MDPT_E_INVALID, "null argument (statistics of image %d)", k);
+        if (out_offsets[k] < 0) return fail(MDPT_E_INVALID, "bad output offset %lld (image %d)", (long long)out_offsets[k], k);
+    }
+    for (int b0 = 0; b0 < B; b0 += MDPT_MASK_IMAGES) {
+        MaskTable t{};
+        t.n = B - b0 < MDPT_MASK_IMAGES ? B - b0 : MDPT_MASK_IMAGES;
+        t.dt = map_dtype;
+        for (int r = 0; r < t.n; ++r) {
+            const int k = b0 + r;
+            t.im[r] = MaskImage{maps[k], (const unsigned*)parts[k], (const double*)coef[k], (const double*)vparts[k], (const unsigned char*)images[k],
+                                (size_t)out_offsets[k], map_hw[2 * k], map_hw[2 * k + 1], image_hw[2 * k], image_hw[2 * k + 1]};
+        }
+        CHK(mdpt_launch_post_mask_cutout(t, factor, thresh_min, thresh_max, invert != 0, (unsigned char*)out_bgra, (unsigned char*)out_mask,
+                                         (hipStream_t)stream));
+    }
+    return 0;
+}
+
 }  // extern "C"

@@ -193,6 +193,13 @@ struct BgrRunTable { BgrRun run[MDPT_BGR_RUNS]; int n; };
 struct PostRun { const void* in; size_t off; int ih, iw, oh, ow, count; };
 struct PostRunTable { PostRun run[MDPT_POST_RUNS]; int n; };
 
+// photo table of the depth-masking cutout (postprocess.hip mask_cutout_kernel), by value: photo k is img (ih x iw x 3 BGR bytes), cut out by its
+// prepared map (h x w, dtype dt of the table) with that map's min/max partials, plane coef and plane-removed min/max partials; its outputs start at
+// pixel `off` of the packed BGRA / mask outputs (blockIdx.y = photo)
+#define MDPT_MASK_IMAGES 32
+struct MaskImage { const void* map; const unsigned* parts; const double* coef; const double* vparts; const unsigned char* img; size_t off; int h, w, ih, iw; };
+struct MaskTable { MaskImage im[MDPT_MASK_IMAGES]; int n, dt; };
+
 // the same for every block of the encoder in ONE launch (the LUTs depend on weights and window sizes only, not on activations)
 struct SwinCpbBatch {
     const float* w1[32]; const float* b1[32]; const float* w2[32]; float* lut[32];
@@ -233,6 +240,13 @@ int mdpt_launch_post_edge_mag(const float* in, int B, int h, int w, const unsign
 int mdpt_launch_post_edge_mask(const float* mag, const unsigned* mag_max, int B, size_t n, unsigned char* out, hipStream_t stream);
 int mdpt_launch_post_pack_u24(const float* in, int B, size_t n, const unsigned* parts, int lossy, const float* mag, const unsigned* mag_max,
                               const unsigned char* mask, size_t mask_stride, unsigned char* out, hipStream_t stream);
+// depth masking (experiments/depth_masking.py): the display mask + checker composite of a uniform batch (images [B, ih, iw, 3]) and the
+// per-photo cutout at each photo's own size
+int mdpt_launch_post_mask_display(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, const double* vparts,
+                                  double tmin, double tmax, int invert, const unsigned char* img, int ih, int iw, unsigned char* mask, unsigned char* comp,
+                                  hipStream_t stream);
+int mdpt_launch_post_mask_cutout(const MaskTable& t, double factor, double tmin, double tmax, int invert, unsigned char* bgra, unsigned char* mask,
+                                 hipStream_t stream);
 
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);

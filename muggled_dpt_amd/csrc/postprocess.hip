@@ -716,6 +716,223 @@ __global__ __launch_bounds__(256) void pack_u24_kernel(const float* __restrict__
     }
 }
 
+// ---- depth masking (the reference's experiments/depth_masking.py: display :189-199, 314-332; save :341-361). n = normalize_01(normalize_01(x) - f plane)
+// in fp64 (threshold_kernel's value before its window), mask = 255 where tmin <= n <= tmax (a NaN compares false: 0), 255 - mask with invert.
+// cv2.resize(INTER_LINEAR) is restated per axis: p = float((d + 0.5) scale - 0.5) with scale = 1 / (out / in) in fp64 (cv2's own form), s = floor(p),
+// a = p - s in fp32; s < 0 -> s = 0, a = 0; s >= in - 1 -> s = in - 1, a = 0. CV_64F: weights (1 - a, a) in fp32, sums in fp64, rows first, then
+// across them. CV_8U: weights round(2048 w), integer sums, (v + 2^21) >> 22: cv2's scalar fixed-point path (its SIMD / IPP paths may round 1 off).
+constexpr int MASK_PX = 4;  // consecutive pixels per thread: 12 BGR bytes in (one dwordx3 load), 16 BGRA + 4 mask bytes out (dwordx4 + dword stores)
+
+struct CvTap { int s0, s1; float a; };
+struct alignas(4) Bytes12 { unsigned w0, w1, w2; };  // (not uint3: a 3-vector may be accessed as 16 bytes)
+
+__device__ __forceinline__ CvTap cv_tap(int d, double scale, int n) {
+#pragma clang fp contract(off)
+    const float p = (float)(((double)d + 0.5) * scale - 0.5);
+    int s = (int)floorf(p);
+    float a = p - (float)s;
+    if (s < 0) { s = 0; a = 0.0f; }
+    if (s >= n - 1) { s = n - 1; a = 0.0f; }
+    return CvTap{s, s + (a != 0.0f), a};  // (a != 0 only where s + 1 < n)
+}
+
+// v0 (1 - a) + v1 a in fp64 with fp32 weights; a == 0: v0 (cv2's one-tap border columns)
+__device__ __forceinline__ double lerp_cv64(double v0, double v1, float a) {
+#pragma clang fp contract(off)
+    return a == 0.0f ? v0 : v0 * (double)(1.0f - a) + v1 * (double)a;
+}
+
+// the photo's statistics, block-wide: the map's fp32 {min, max} from its parts and the fp64 {min, max - min} of its plane-removed values from its
+// vparts (threshold_kernel's reduction: a NaN partial pins NaN; one lane per partial)
+__device__ __forceinline__ void mask_stats(const unsigned* __restrict__ parts, const double* __restrict__ vparts, float& lo, float& hi, double& vlo,
+                                           double& vrange) {
+    __shared__ unsigned smm[2];
+    __shared__ double svr[2];
+    if (threadIdx.x < SEG_PARTS) {
+        unsigned mn = parts[threadIdx.x * 2], mx = parts[threadIdx.x * 2 + 1];
+        double a = vparts[threadIdx.x * 2], z = vparts[threadIdx.x * 2 + 1];
+        const bool any_nan = __any(a != a || z != z);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            mn = min(mn, (unsigned)__shfl_xor((int)mn, o));
+            mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
+            a = fmin(a, __shfl_xor(a, o));
+            z = fmax(z, __shfl_xor(z, o));
+        }
+        if (threadIdx.x == 0) {
+            smm[0] = mn;
+            smm[1] = mx;
+            svr[0] = any_nan ? NAN : a;
+            svr[1] = any_nan ? NAN : z;
+        }
+    }
+    __syncthreads();
+    lo = ord2f(smm[0]);
+    hi = ord2f(smm[1]);
+    vlo = svr[0];
+    vrange = svr[1] - svr[0];
+}
+
+// n at pixel (x, y) of the map at element `base` (plane_removed's arithmetic, then threshold_kernel's normalisation)
+__device__ __forceinline__ double mask_n(const void* map, size_t base, int dt, int w, int x, int y, float lo, float hi, const double* c, double factor,
+                                         double vlo, double vrange) {
+#pragma clang fp contract(off)
+    const double v = (double)norm01_dt(ld_dt(map, base + (size_t)y * w + x, dt), lo, hi, dt) - plane_at(c, x, y) * factor;
+    return (v - vlo) / vrange;
+}
+
+__device__ __forceinline__ unsigned mask_byte(double n, double tmin, double tmax, int invert) {
+    return ((n >= tmin && n <= tmax) != (invert != 0)) ? 255u : 0u;
+}
+
+// cv2.resize of a BGR uint8 image at the output pixel of taps (tx, ty), the scalar fixed-point formula -> o[0..2]
+__device__ __forceinline__ void bgr_lerp_u8(const unsigned char* __restrict__ src, int iw, CvTap tx, CvTap ty, unsigned char* o) {
+    const int ax1 = (int)rintf(tx.a * 2048.0f), ax0 = (int)rintf((1.0f - tx.a) * 2048.0f);
+    const int ay1 = (int)rintf(ty.a * 2048.0f), ay0 = (int)rintf((1.0f - ty.a) * 2048.0f);
+    const unsigned char* r0 = src + (size_t)ty.s0 * iw * 3;
+    const unsigned char* r1 = src + (size_t)ty.s1 * iw * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const int h0 = r0[tx.s0 * 3 + ch] * ax0 + r0[tx.s1 * 3 + ch] * ax1;
+        const int h1 = r1[tx.s0 * 3 + ch] * ax0 + r1[tx.s1 * 3 + ch] * ax1;
+        const int v = (h0 * ay0 + h1 * ay1 + (1 << 21)) >> 22;
+        o[ch] = (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
+    }
+}
+
+// display (uniform batch, map b at the display size h x w, photo b ih x iw): the mask of n, and the composite - cv2.resize of the photo where the
+// mask is 255, CheckerPattern() where it is 0: A = 169 where ((y - t) mod 64 < 32) == ((x - l) mod 64 < 32), else B = 214, t = max(h - 64, 0) / 2,
+// l = max(w - 64, 0) / 2 (toadui/helpers/checker_pattern.py: 32-px tiles, BORDER_WRAP padding, cropped). MASK_PX pixels of the flat image per thread.
+__global__ __launch_bounds__(256) void mask_display_kernel(const void* __restrict__ map, int dt, int h, int w, const unsigned* __restrict__ parts,
+                                                           const double* __restrict__ coef, double factor, const double* __restrict__ vparts, double tmin,
+                                                           double tmax, int invert, const unsigned char* __restrict__ img, int ih, int iw,
+                                                           unsigned char* __restrict__ mask_out, unsigned char* __restrict__ comp_out) {
+    const int b = blockIdx.y;
+    float lo, hi;
+    double vlo, vrange;
+    mask_stats(parts + (size_t)b * SEG_PARTS * 2, vparts + (size_t)b * SEG_PARTS * 2, lo, hi, vlo, vrange);
+    const double* c = coef + (size_t)b * 4;
+    const size_t n = (size_t)h * w, base = (size_t)b * n;
+    const unsigned char* src = img + (size_t)b * ih * iw * 3;
+    const double scale_x = 1.0 / ((double)w / (double)iw), scale_y = 1.0 / ((double)h / (double)ih);
+    const int top = max(h - 64, 0) / 2, left = max(w - 64, 0) / 2;
+    for (size_t p0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * MASK_PX; p0 < n; p0 += (size_t)gridDim.x * blockDim.x * MASK_PX) {
+        const int cnt = n - p0 < (size_t)MASK_PX ? (int)(n - p0) : MASK_PX;
+        int y = (int)(p0 / w), x = (int)(p0 % w);
+        CvTap ty = cv_tap(y, scale_y, ih);
+        unsigned mword = 0u;
+        unsigned char px[MASK_PX * 3];
+#pragma unroll
+        for (int k = 0; k < MASK_PX; ++k) {
+            px[k * 3] = px[k * 3 + 1] = px[k * 3 + 2] = 0;
+            if (k >= cnt) continue;
+            const unsigned m = mask_byte(mask_n(map, base, dt, w, x, y, lo, hi, c, factor, vlo, vrange), tmin, tmax, invert);
+            mword |= m << (8 * k);
+            if (m) {
+                bgr_lerp_u8(src, iw, cv_tap(x, scale_x, iw), ty, px + k * 3);
+            } else {
+                const unsigned char v = (((y - top) & 63) < 32) == (((x - left) & 63) < 32) ? 169 : 214;
+                px[k * 3] = px[k * 3 + 1] = px[k * 3 + 2] = v;
+            }
+            if (++x == w) {
+                x = 0;
+                ty = cv_tap(++y, scale_y, ih);
+            }
+        }
+        unsigned char* mo = mask_out + base + p0;
+        unsigned char* co = comp_out + (base + p0) * 3;
+        if (cnt == MASK_PX && ((uintptr_t)mo & 3) == 0) {
+            *(unsigned*)mo = mword;
+        } else {
+            for (int k = 0; k < cnt; ++k) mo[k] = (unsigned char)(mword >> (8 * k));
+        }
+        if (cnt == MASK_PX && ((uintptr_t)co & 3) == 0) {
+            unsigned wd[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                wd[q] = (unsigned)px[4 * q] | (unsigned)px[4 * q + 1] << 8 | (unsigned)px[4 * q + 2] << 16 | (unsigned)px[4 * q + 3] << 24;
+            *(Bytes12*)co = Bytes12{wd[0], wd[1], wd[2]};
+        } else {
+            for (int k = 0; k < cnt * 3; ++k) co[k] = px[k];
+        }
+    }
+}
+
+// cutout (one photo per blockIdx.y, any sizes): s = cv2.resize(n, (iw, ih)) in fp64 from the 2 x 2 map taps evaluated on the fly, the mask of s,
+// BGRA = (BGR AND mask, mask), both at the photo's packed offset. The taps of consecutive pixels are shared where they repeat (an enlargement).
+__global__ __launch_bounds__(256) void mask_cutout_kernel(const MaskTable t, double factor, double tmin, double tmax, int invert,
+                                                          unsigned char* __restrict__ out_bgra, unsigned char* __restrict__ out_mask) {
+    const MaskImage& im = t.im[blockIdx.y];
+    float lo, hi;
+    double vlo, vrange;
+    mask_stats(im.parts, im.vparts, lo, hi, vlo, vrange);
+    const int dt = t.dt, h = im.h, w = im.w, ih = im.ih, iw = im.iw;
+    const void* map = im.map;
+    const double* c = im.coef;
+    const unsigned char* img = im.img;
+    const double scale_x = 1.0 / ((double)iw / (double)w), scale_y = 1.0 / ((double)ih / (double)h);
+    const size_t n = (size_t)ih * iw;
+    unsigned char* bgra = out_bgra + im.off * 4;
+    unsigned char* msk = out_mask + im.off;
+    for (size_t p0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * MASK_PX; p0 < n; p0 += (size_t)gridDim.x * blockDim.x * MASK_PX) {
+        const int cnt = n - p0 < (size_t)MASK_PX ? (int)(n - p0) : MASK_PX;
+        const unsigned char* in = img + p0 * 3;
+        unsigned wd[3] = {0u, 0u, 0u};
+        if (cnt == MASK_PX && ((uintptr_t)in & 3) == 0) {
+            const Bytes12 v = *(const Bytes12*)in;
+            wd[0] = v.w0;
+            wd[1] = v.w1;
+            wd[2] = v.w2;
+        } else {
+            for (int k = 0; k < cnt * 3; ++k) wd[k >> 2] |= (unsigned)in[k] << (8 * (k & 3));
+        }
+        int y = (int)(p0 / iw), x = (int)(p0 % iw);
+        CvTap ty = cv_tap(y, scale_y, h);
+        int key_x = -1, key_y = -1;
+        double n00 = 0.0, n01 = 0.0, n10 = 0.0, n11 = 0.0;
+        unsigned mword = 0u, px[MASK_PX];
+#pragma unroll
+        for (int k = 0; k < MASK_PX; ++k) {
+            px[k] = 0u;
+            if (k >= cnt) continue;
+            const CvTap tx = cv_tap(x, scale_x, w);
+            const bool bx = tx.s1 != tx.s0, by = ty.s1 != ty.s0;
+            if (2 * tx.s0 + bx != key_x || 2 * ty.s0 + by != key_y) {
+                key_x = 2 * tx.s0 + bx;
+                key_y = 2 * ty.s0 + by;
+                n00 = mask_n(map, 0, dt, w, tx.s0, ty.s0, lo, hi, c, factor, vlo, vrange);
+                n01 = bx ? mask_n(map, 0, dt, w, tx.s1, ty.s0, lo, hi, c, factor, vlo, vrange) : n00;
+                n10 = by ? mask_n(map, 0, dt, w, tx.s0, ty.s1, lo, hi, c, factor, vlo, vrange) : n00;
+                n11 = bx && by ? mask_n(map, 0, dt, w, tx.s1, ty.s1, lo, hi, c, factor, vlo, vrange) : (bx ? n01 : n10);
+            }
+            const double s = lerp_cv64(lerp_cv64(n00, n01, tx.a), lerp_cv64(n10, n11, tx.a), ty.a);
+            const unsigned m = mask_byte(s, tmin, tmax, invert);
+            mword |= m << (8 * k);
+            // BGR of pixel k: bytes 3k .. 3k + 2 of the loaded words
+            unsigned bgr = 0u;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) bgr |= ((wd[(3 * k + ch) >> 2] >> (8 * ((3 * k + ch) & 3))) & 255u) << (8 * ch);
+            px[k] = (m ? bgr : 0u) | m << 24;
+            if (++x == iw) {
+                x = 0;
+                ty = cv_tap(++y, scale_y, h);
+            }
+        }
+        unsigned char* bo = bgra + p0 * 4;
+        unsigned char* mo = msk + p0;
+        if (cnt == MASK_PX && ((uintptr_t)bo & 15) == 0) {
+            *(uint4*)bo = make_uint4(px[0], px[1], px[2], px[3]);
+        } else {
+            for (int k = 0; k < cnt; ++k) *(unsigned*)(bo + 4 * k) = px[k];  // (the BGRA output is 4-byte aligned: checked by the entry point)
+        }
+        if (cnt == MASK_PX && ((uintptr_t)mo & 3) == 0) {
+            *(unsigned*)mo = mword;
+        } else {
+            for (int k = 0; k < cnt; ++k) mo[k] = (unsigned char)(mword >> (8 * k));
+        }
+    }
+}
+
 }  // namespace
 
 int mdpt_launch_post_minmax(const float* in, size_t n, float* minmax_out, unsigned* scratch2, hipStream_t stream) {
@@ -847,5 +1064,26 @@ int mdpt_launch_post_pack_u24(const float* in, int B, size_t n, const unsigned* 
     MdptProfScope prof("pack_u24_kernel", 0.0, stream);
     hipLaunchKernelGGL(pack_u24_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, in, n, parts, lossy, mag, mag_max, mask,
                        mask_stride, (uchar4*)out);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_mask_display(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, const double* vparts,
+                                  double tmin, double tmax, int invert, const unsigned char* img, int ih, int iw, unsigned char* mask, unsigned char* comp,
+                                  hipStream_t stream) {
+    const size_t g = ((size_t)h * w + 256 * MASK_PX - 1) / (256 * MASK_PX);
+    MdptProfScope prof("mask_display_kernel", 0.0, stream);
+    hipLaunchKernelGGL(mask_display_kernel, dim3(g > 512 ? 512 : (int)g, B), dim3(256), 0, stream, in, dt, h, w, parts, coef, factor, vparts, tmin, tmax,
+                       invert, img, ih, iw, mask, comp);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_mask_cutout(const MaskTable& t, double factor, double tmin, double tmax, int invert, unsigned char* bgra, unsigned char* mask,
+                                 hipStream_t stream) {
+    if (t.n <= 0 || t.n > MDPT_MASK_IMAGES) return (int)hipErrorInvalidValue;
+    size_t most = 0;
+    for (int k = 0; k < t.n; ++k) most = (size_t)t.im[k].ih * t.im[k].iw > most ? (size_t)t.im[k].ih * t.im[k].iw : most;
+    const size_t g = (most + 256 * MASK_PX - 1) / (256 * MASK_PX);
+    MdptProfScope prof("mask_cutout_kernel", 0.0, stream);
+    hipLaunchKernelGGL(mask_cutout_kernel, dim3(g > 2048 ? 2048 : (int)g, t.n), dim3(256), 0, stream, t, factor, tmin, tmax, invert, bgra, mask);
     return (int)hipGetLastError();
 }

@@ -214,6 +214,8 @@ SYMBOLS = {
     "mdpt_post_edge_mag": (ctypes.c_int, [_VP, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP]),
     "mdpt_post_edge_mask": (ctypes.c_int, [_VP, _VP, _I, _SZ, _VP, _VP]),
     "mdpt_post_pack_u24_alpha": (ctypes.c_int, [_VP, _I, _SZ, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP]),
+    "mdpt_post_mask_display": (ctypes.c_int, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _D, _D, _I, _VP, _I, _I, _VP, _VP, _VP]),
+    "mdpt_post_mask_cutout_images": (ctypes.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _D, _VP, _VP, _VP, _I, _D, _D, _I, _VP, _VP, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

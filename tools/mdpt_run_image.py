@@ -7,10 +7,13 @@ Several -i files (of any sizes) run together through DPTModel.inference_images, 
 that receives every image's 8-bit depth map at the image's own size (postprocess.depth_to_color_images).
 For one image, --display saves the still-image demo's BGR frame (postprocess.depth_to_display: --remove_plane, --threshold, --reverse,
 --high_contrast as in run_image.py) and --u24 the 3D viewer's BGRA 24-bit frame with its edge alpha (postprocess.pack_depth_u24_frames).
+For one image or several, --cutout DIR saves the depth masking demo's results at each image's own size (postprocess.depth_mask_images:
+--mask MIN MAX, --invert_mask and --remove_plane as in experiments/depth_masking.py): <name>_mask.npy (uint8) and <name>_cutout.npy (BGRA).
 
   python tools/mdpt_run_image.py --synthetic vits --size 518 --fp32
   python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i image.npy -o depth_u8.npy
   python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i a.npy -i b.npy -i c.npy -o depth_dir
+  python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i a.npy -i b.npy --mask 0.5 1 --remove_plane 0.5 --cutout cut_dir
 """
 import argparse
 import os
@@ -41,6 +44,9 @@ def main():
     ap.add_argument("--high_contrast", action="store_true", help="single image: thresholded histogram equalization")
     ap.add_argument("--display", default=None, metavar="OUT.npy", help="single image: save the still-image demo's BGR display frame (.npy)")
     ap.add_argument("--u24", default=None, metavar="OUT.npy", help="single image: save the 3D viewer's BGRA 24-bit frame with edge alpha (.npy)")
+    ap.add_argument("--mask", type=float, nargs=2, default=(0.0, 1.0), metavar=("MIN", "MAX"), help="depth masking: keep pixels whose depth is in MIN..MAX")
+    ap.add_argument("--invert_mask", action="store_true", help="depth masking: keep the pixels outside the --mask range instead")
+    ap.add_argument("--cutout", default=None, metavar="DIR", help="save every image's depth mask and BGRA cutout (.npy) at its own size into DIR")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mdpt_run_image needs an MI355X: no GPU visible (there is no CPU fallback)")
@@ -80,6 +86,21 @@ def main():
         from muggled_dpt_amd.postprocess import pack_depth_u24_frames
         np.save(args.u24, pack_depth_u24_frames(depth, is_metric=bool(cfg.get("is_metric", False)))[0].cpu().numpy())
         print("saved", args.u24)
+    save_cutouts(args, args.image_path or ["synthetic.npy"], [img], [depth])
+
+
+def save_cutouts(args, paths, images, depths):
+    """--cutout: the depth masking demo's save step for every image (postprocess.depth_mask_images, one call for the whole list)"""
+    if not args.cutout:
+        return
+    from muggled_dpt_amd.postprocess import depth_mask_images
+    os.makedirs(args.cutout, exist_ok=True)
+    results = depth_mask_images(depths, images, args.remove_plane, tuple(args.mask), args.invert_mask)
+    for path, (cutout, mask) in zip(paths, results):
+        stem = os.path.join(args.cutout, os.path.splitext(os.path.basename(path))[0])
+        np.save(stem + "_mask.npy", mask.cpu().numpy())
+        np.save(stem + "_cutout.npy", cutout.cpu().numpy())
+        print("saved", stem + "_mask.npy", stem + "_cutout.npy")
 
 
 def run_images(model, args, t0):
@@ -104,6 +125,7 @@ def run_images(model, args, t0):
             out = os.path.join(args.output, os.path.splitext(os.path.basename(path))[0] + "_depth_u8.npy")
             np.save(out, g[0, :, :, 0].cpu().numpy())
             print("saved", out)
+    save_cutouts(args, args.image_path, images, depths)
 
 
 if __name__ == "__main__":
