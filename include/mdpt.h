@@ -226,6 +226,15 @@ int mdpt_attn_probe_shape(const mdpt_handle* h, int32_t B, int32_t gh, int32_t g
  * [B, tokens of the block's stage, features of the stage] (SwinV2). attn_out and block_out may each be NULL. */
 int mdpt_encoder_probe_blocks(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4],
                               void* const* attn_out, void* const* block_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The same pass with the per-token L2 NORMS of every block's output instead of the tokens (experiments/block_norm_visualization.py:133-147 keeps
+ * block_tensor.norm(dim=-1) of the patch tokens and nothing else) - additive to ABI v6. norm_out has one entry per block (SwinV2: stage-major);
+ * every non-NULL entry receives sqrt(sum x^2) over the features of each patch token of that block's fp32 output as fp32 [B, gh, gw] (ViT / BEiT
+ * families, the cls token dropped) or [B, gh >> s, gw >> s] (a SwinV2 block of stage s). channel_out (may be NULL) has the same layout; a non-NULL
+ * entry l receives channel channel_index[l] of the same tokens (the script's "Channel" view, tensor[0, :, :, ch]); a channel_index[l] outside
+ * [0, features of the block) is MDPT_E_INVALID before anything is launched. stage_out receives the four encoder taps as with mdpt_encoder; the
+ * taps, and every kernel of the pass itself, are those of mdpt_encoder. A row's norm does not depend on the batch it is part of. */
+int mdpt_encoder_block_norms(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4], void* const* norm_out,
+                             const int32_t* channel_index, void* const* channel_out, void* workspace, size_t workspace_bytes, void* stream);
 /* FusionModel.blocks[index].forward (fusion_model.py:89-114 top-most block, :148-154 regular blocks; called one by one by
  * experiments/fusion_scaling.py:330-334): reassembly map [B,C,sh,sw] (+ the previous block's output [B,C,sh,sw]; NULL for index 3,
  * the top-most block) -> [B,C,2sh,2sw]. */
@@ -427,6 +436,16 @@ int mdpt_post_mask_display(const void* in_bhw, int32_t in_dtype, int32_t B, int3
 int mdpt_post_mask_cutout_images(const void* const* maps, const int32_t* map_hw, int32_t map_dtype, const void* const* parts, const void* const* coef,
                                  const void* const* vparts, double factor, const void* const* images, const int32_t* image_hw, const int64_t* out_offsets,
                                  int32_t B, double thresh_min, double thresh_max, int32_t invert, void* out_bgra, void* out_mask, void* stream);
+
+/* Block norm tiles on the device (additive to ABI v6): BlockData.__init__ of the reference's experiments/block_norm_visualization.py:137-147 and the
+ * nearest-neighbour enlargement of its display (:207-233) for L maps (norms or channel planes, maps[l] = device fp32 [B, map_hw[2l], map_hw[2l+1]]) of
+ * B images at once: every (map, image) is normalised by its OWN min / max in fp32, one IEEE operation per step as numpy does it -
+ * u8 = round_half_even(((n - min) / (max - min)) * 255) - and written to tiles_u8 [L, B, H, W] at (y, x) from cell (y / (H / h), x / (W / w)); H and
+ * W must be whole multiples of every map's sides (what SwinV2's stages give; every nearest rule agrees there). minmax_f32 [L, B, 2] receives each
+ * map's {min, max}. A constant map (0 / 0) and a map holding a NaN (min = max = NaN) give an all-zero tile, where the reference's NaN -> uint8
+ * conversion is undefined. map_hw and maps are host arrays read during the call only; one launch per 32 maps; nothing is read back. */
+int mdpt_post_block_norm_tiles(const void* const* maps, const int32_t* map_hw, int32_t L, int32_t B, int32_t H, int32_t W, void* tiles_u8, void* minmax_f32,
+                               void* stream);
 
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */

@@ -556,6 +556,39 @@ __global__ __launch_bounds__(256) void tokens_export_kernel(const op_t* in_hi, c
     }
 }
 
+// Per-token L2 norm of the fp32 residual stream (block_tensor.norm(dim=-1) of experiments/block_norm_visualization.py:133-147 without the
+// [B, N, F] export): one wave per token row, `skip` leading rows of every image (the cls token) and the rows from skip + ntok on (pads) are
+// not read. Lane l takes the 16-byte chunks l, l + 64, ... of the row into ONE fp32 accumulator (chunk order, x y z w inside a chunk), then
+// a 6-step butterfly adds the lanes: the order depends on F alone, so a row's bits do not depend on the batch it is part of. vec4 = 0: F or
+// the base address rules out 16-byte loads, same walk one float at a time. chan_out != null: out plane of channel `chan` of every token
+// (tensor[..., chan], the script's "Channel" view), copied by lane 0. HBM-bound: rows x F x 4 bytes in, 4 (8) bytes per row out.
+__global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__ in, float* __restrict__ norm_out, float* __restrict__ chan_out, int chan,
+                                                       int B, int ntok, int npad, int skip, int F, int vec4) {
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
+    if (row >= (size_t)B * ntok) return;
+    const int lane = threadIdx.x & 63;
+    const float* src = in + ((row / ntok) * npad + row % ntok + skip) * F;
+    float acc = 0.0f;
+    if (vec4) {
+        const float4* src4 = (const float4*)src;
+        for (int c = lane; c < F / 4; c += 64) {
+            const float4 v = src4[c];
+            acc = __fmaf_rn(v.x, v.x, acc);
+            acc = __fmaf_rn(v.y, v.y, acc);
+            acc = __fmaf_rn(v.z, v.z, acc);
+            acc = __fmaf_rn(v.w, v.w, acc);
+        }
+    } else {
+        for (int f = lane; f < F; f += 64) acc = __fmaf_rn(src[f], src[f], acc);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc = __fadd_rn(acc, __shfl_xor(acc, o));
+    if (lane == 0) {
+        if (norm_out) norm_out[row] = __fsqrt_rn(acc);
+        if (chan_out) chan_out[row] = src[chan];
+    }
+}
+
 __global__ __launch_bounds__(256) void tokens_import_kernel(const float* __restrict__ in, op_t* out_hi, op_t* out_lo, int B,
                                                             int N, int npad, int F, size_t out_f8, int out_a8) {
     const size_t total = (size_t)B * npad * F;
@@ -1116,6 +1149,17 @@ int MDPT_FN(mdpt_launch_nchw_to_nhwc)(const float* in, float* out_f32, op_t* out
 int MDPT_FN(mdpt_launch_tokens_export)(const op_t* in_hi, const op_t* in_lo, const float* in_f32, float* out, int B, int N, int npad,
                               int F, int skip_cls, hipStream_t stream, size_t lo_f8) {
     hipLaunchKernelGGL(tokens_export_kernel, dim3(grid_for((size_t)B * (N - skip_cls) * F)), dim3(256), 0, stream, in_hi, in_lo, in_f32, out, B, N, npad, F, skip_cls, lo_f8);
+    LAUNCH_RET();
+}
+
+int MDPT_FN(mdpt_launch_row_norm)(const float* in, float* norm_out, float* chan_out, int chan, int B, int ntok, int npad, int skip, int F,
+                                  hipStream_t stream) {
+    if (B <= 0 || ntok <= 0 || F <= 0 || skip < 0 || skip + ntok > npad || (chan_out && (chan < 0 || chan >= F))) return (int)hipErrorInvalidValue;
+    if (!norm_out && !chan_out) return 0;
+    const size_t rows = (size_t)B * ntok;
+    MdptProfScope prof("row_norm_kernel", 0.0, stream);
+    hipLaunchKernelGGL(row_norm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, in, norm_out, chan_out, chan, B, ntok, npad, skip, F,
+                       (F % 4 == 0 && ((uintptr_t)in & 15) == 0) ? 1 : 0);
     LAUNCH_RET();
 }
 

@@ -675,8 +675,10 @@ int mdpt_encoder_probe(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_
 
 // ... and / or the output tokens of selected blocks (what a forward hook on a TransformerBlock sees: demo_helpers/model_capture.py:54-59
 // used by experiments/block_norm_visualization.py:282)
-int mdpt_encoder_probe_blocks(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4],
-                              void* const* attn_out, void* const* block_out, void* workspace, size_t workspace_bytes, void* stream) {
+// (the pass behind mdpt_encoder_probe_blocks and mdpt_encoder_block_norms: mdpt_encoder plus whatever dumps are asked for)
+static int encoder_with_dumps(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4], void* const* attn_out,
+                              void* const* block_out, void* const* norm_out, const int32_t* channel_index, void* const* channel_out, void* workspace,
+                              size_t workspace_bytes, void* stream) {
     if (!h || !tokens_bnf || !stage_out) return fail(MDPT_E_INVALID, "null argument");
     for (int i = 0; i < 4; ++i)
         if (!stage_out[i]) return fail(MDPT_E_INVALID, "null stage output %d", i);
@@ -685,6 +687,7 @@ int mdpt_encoder_probe_blocks(mdpt_handle* h, const void* tokens_bnf, int32_t B,
     if (h->swin) {  // as mdpt_encoder, plus the window-attention weights of the listed blocks (stage-major block order)
         CHK(make_ctx(h, B, gh * h->P, gw * h->P, workspace, workspace_bytes, stream, &c));
         c.attn_dump = attn_out; c.block_dump = block_out;
+        c.norm_dump = norm_out; c.chan_dump = channel_out; c.chan_index = channel_index;
         const size_t n = (size_t)B * gh * gw * h->F;
         Planes xn = c.pl(c.p.sw.xn);
         CHK(hipMemcpyAsync(c.at<float>(c.p.sw.resid[0]), tokens_bnf, n * 4, hipMemcpyDeviceToDevice, c.s));
@@ -699,6 +702,7 @@ int mdpt_encoder_probe_blocks(mdpt_handle* h, const void* tokens_bnf, int32_t B,
     if (rup(c.p.N, 8) > c.p.npad) return fail(MDPT_E_INVALID, "internal: plan too small");
     c.p.npad = rup(c.p.N, 8); c.p.npadv = rup(c.p.N, 64);
     c.attn_dump = attn_out; c.block_dump = block_out;
+    c.norm_dump = norm_out; c.chan_dump = channel_out; c.chan_index = channel_index;
     if (is_beit(h)) {
         CHK(OPLC(mdpt_launch_memset_f32, c.at<float>(c.p.pos), 0.0f, (size_t)c.p.Np * h->F, c.s));
     } else {
@@ -710,6 +714,28 @@ int mdpt_encoder_probe_blocks(mdpt_handle* h, const void* tokens_bnf, int32_t B,
     CHK(run_encoder(c, stage_out));
     h->has_last = false;
     return 0;
+}
+
+int mdpt_encoder_probe_blocks(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4],
+                              void* const* attn_out, void* const* block_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return encoder_with_dumps(h, tokens_bnf, B, gh, gw, stage_out, attn_out, block_out, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The same pass with the per-token L2 norms of every block's output instead of the tokens themselves (experiments/block_norm_visualization.py:
+// 133-147 keeps nothing else of a block): entry l of norm_out receives fp32 [B, gh, gw] (SwinV2, stage s: [B, gh >> s, gw >> s]), the cls token
+// dropped; entry l of channel_out (may be NULL) channel channel_index[l] of the same tokens (the script's "Channel" view)
+int mdpt_encoder_block_norms(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4], void* const* norm_out,
+                             const int32_t* channel_index, void* const* channel_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !norm_out || (channel_out && !channel_index)) return fail(MDPT_E_INVALID, "null argument");
+    if (channel_out) {
+        for (int l = 0, s = 0, in_stage = 0; l < h->nblocks; ++l, ++in_stage) {
+            while (h->swin && s < 3 && in_stage >= h->sL[s]) { in_stage = 0; ++s; }
+            const int F = h->swin ? h->hid[s] : h->F;
+            if (channel_out[l] && (channel_index[l] < 0 || channel_index[l] >= F))
+                return fail(MDPT_E_INVALID, "channel index %d of block %d is outside [0, %d)", channel_index[l], l, F);
+        }
+    }
+    return encoder_with_dumps(h, tokens_bnf, B, gh, gw, stage_out, nullptr, nullptr, norm_out, channel_index, channel_out, workspace, workspace_bytes, stream);
 }
 
 int mdpt_attn_probe_shape(const mdpt_handle* h, int32_t B, int32_t gh, int32_t gw, int32_t block, int64_t shape[4]) {
@@ -1210,6 +1236,27 @@ int mdpt_post_mask_cutout_images(const void* const* maps, const int32_t* map_hw,
         }
         CHK(mdpt_launch_post_mask_cutout(t, factor, thresh_min, thresh_max, invert != 0, (unsigned char*)out_bgra, (unsigned char*)out_mask,
                                          (hipStream_t)stream));
+    }
+    return 0;
+}
+
+// ---- block norm tiles (experiments/block_norm_visualization.py:137-147, 207-233)
+int mdpt_post_block_norm_tiles(const void* const* maps, const int32_t* map_hw, int32_t L, int32_t B, int32_t H, int32_t W, void* tiles_u8, void* minmax_f32,
+                               void* stream) {
+    if (!maps || !map_hw || !tiles_u8 || !minmax_f32) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_batch_hw(B, H, W));
+    if (L <= 0 || (size_t)H * W > ((size_t)1 << 24)) return fail(MDPT_E_INVALID, "bad map count %d / tile size %dx%d", L, H, W);
+    CHK(check_images(maps, map_hw, L, "map"));
+    for (int l = 0; l < L; ++l)
+        if (H % map_hw[2 * l] || W % map_hw[2 * l + 1])
+            return fail(MDPT_E_INVALID, "map %d (%dx%d) does not divide the tile size %dx%d", l, map_hw[2 * l], map_hw[2 * l + 1], H, W);
+    const int per_launch = 65535 / B < MDPT_POST_RUNS ? 65535 / B : MDPT_POST_RUNS;  // (maps per launch: a launch holds at most 65535 images)
+    for (int l0 = 0; l0 < L; l0 += per_launch) {
+        PostRunTable t{};
+        t.n = L - l0 < per_launch ? L - l0 : per_launch;
+        for (int r = 0; r < t.n; ++r)
+            t.run[r] = PostRun{maps[l0 + r], (size_t)(l0 + r) * B * H * W, map_hw[2 * (l0 + r)], map_hw[2 * (l0 + r) + 1], H, W, B};
+        CHK(mdpt_launch_post_block_norm_tiles(t, (unsigned char*)tiles_u8, (float*)minmax_f32 + (size_t)l0 * B * 2, (hipStream_t)stream));
     }
     return 0;
 }

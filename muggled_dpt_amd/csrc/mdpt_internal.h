@@ -309,6 +309,12 @@ struct Ctx {
     } bgr;
     void* const* attn_dump = nullptr;  // per block: where to write softmax(q k^T) as fp32 [B,H,N,N] (null entries: skip)
     void* const* block_dump = nullptr; // per block: where to write the block's output tokens as fp32 [B,N,F] (null entries: skip)
+    // per block (mdpt_encoder_block_norms): where to write the L2 norm of every patch token of the block's output as fp32 [B, h, w], and / or
+    // channel chan_index[block] of those tokens (null arrays / null entries: skip); cls and pad rows are not read
+    void* const* norm_dump = nullptr;
+    void* const* chan_dump = nullptr;
+    const int32_t* chan_index = nullptr;
+    bool norm_wanted(int block) const { return (norm_dump && norm_dump[block]) || (chan_dump && chan_dump[block]); }
     template <class T> T* at(size_t off) const { return off == SIZE_MAX ? nullptr : (T*)(ws + off); }
     Planes pl(const size_t o[3]) const {
         Planes r;

@@ -247,6 +247,9 @@ int mdpt_launch_post_mask_display(const void* in, int dt, int B, int h, int w, c
                                   hipStream_t stream);
 int mdpt_launch_post_mask_cutout(const MaskTable& t, double factor, double tmin, double tmax, int invert, unsigned char* bgra, unsigned char* mask,
                                  hipStream_t stream);
+// block norm tiles (experiments/block_norm_visualization.py): run r of the table = the B = count fp32 maps [ih, iw] of one block, each normalised by
+// its own min / max to uint8 and enlarged by the whole factors oh / ih, ow / iw into its tile of the packed out; minmax = [images of the table, 2]
+int mdpt_launch_post_block_norm_tiles(const PostRunTable& t, unsigned char* out, float* minmax, hipStream_t stream);
 
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);

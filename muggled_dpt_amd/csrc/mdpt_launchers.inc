@@ -58,6 +58,10 @@ int MDPT_FN(mdpt_launch_nhwc_to_nchw)(const float* in_f32, const op_t* in_hi, co
                              int C, int Cp, hipStream_t stream);
 int MDPT_FN(mdpt_launch_tokens_export)(const op_t* in_hi, const op_t* in_lo, const float* in_f32, float* out, int B, int N,
                               int npad, int F, int skip_cls, hipStream_t stream, size_t lo_f8 = 0);  // lo_f8: in_lo is an e5m2 residue plane (Planes::f8)
+// per-token L2 norm of fp32 rows [B, npad, F]: rows skip .. skip + ntok - 1 of every image -> norm_out [B, ntok] and / or channel `chan` of
+// the same rows -> chan_out [B, ntok] (either may be null); one wave per row, no atomics, batch-invariant summation order
+int MDPT_FN(mdpt_launch_row_norm)(const float* in, float* norm_out, float* chan_out, int chan, int B, int ntok, int npad, int skip, int F,
+                                  hipStream_t stream);
 int MDPT_FN(mdpt_launch_tokens_import)(const float* in, op_t* out_hi, op_t* out_lo, int B, int N, int npad, int F,
                               hipStream_t stream, size_t out_f8 = 0, int out_a8 = 0);
 int MDPT_FN(mdpt_launch_nchw_to_nhwc)(const float* in, float* out_f32, op_t* out_hi, op_t* out_lo, int relu_bf16, int B, int H,

@@ -239,9 +239,9 @@ int run_encoder(const Ctx& c, void* const taps_f32[4]) {
             g.acc_init = 1;
             g.resid = resid; g.out_f32 = resid; g.ldr = F; g.ldc = F;
             CHK(wrc_bias(c, g, h->M(giant ? n + ".mlp.outer_linear.weight" : n + ".mlp.layers.2.weight"), g.bias));
-            // a LayerNorm must be the next reader of the residual stream: not when this block's raw output is exported (block hooks, BEiT's
+            // a LayerNorm must be the next reader of the residual stream: not when this block's raw output is exported (block hooks, block norms, BEiT's
             // un-normed taps, a debug stop) or nothing follows (BEiT's last block is a tap)
-            if (!(c.block_dump && c.block_dump[b]) && !(is_beit(h) && is_tap) && (b + 1 < h->nblocks || is_tap) && ksplit_setup(g)) {
+            if (!(c.block_dump && c.block_dump[b]) && !c.norm_wanted(b) && !(is_beit(h) && is_tap) && (b + 1 < h->nblocks || is_tap) && ksplit_setup(g)) {
                 pending = g.ks_part; npending = g.ksplit - 1;
             }
             CHK(OPLC(mdpt_launch_gemm, g, c.s));
@@ -249,6 +249,9 @@ int run_encoder(const Ctx& c, void* const taps_f32[4]) {
         DBG_STOP(6);
         if (c.block_dump && c.block_dump[b])  // TransformerBlock output (transformer_block.py:61-62), pad rows dropped
             CHK(OPLC(mdpt_launch_tokens_export, nullptr, nullptr, resid, (float*)c.block_dump[b], p.B, p.N, p.npad, F, 0, c.s));
+        if (c.norm_wanted(b))  // ... or only its per-token norms / one channel, patch tokens only (block_norm_visualization.py:133-147)
+            CHK(OPLC(mdpt_launch_row_norm, resid, c.norm_dump ? (float*)c.norm_dump[b] : nullptr, c.chan_dump ? (float*)c.chan_dump[b] : nullptr,
+                                         c.chan_dump && c.chan_dump[b] ? c.chan_index[b] : 0, p.B, p.Np, p.npad, 1, F, c.s));
         if (is_tap) {
             const int st = v1 ? b - (h->nblocks - 4) : b / h->bps;
             Planes tp = c.pl(p.tap[st]);

@@ -188,6 +188,10 @@ int run_encoder_swin(const Ctx& c, void* const taps_f32[4]) {
             CHK(OPLC(mdpt_launch_ln_res, x, resid, h->V(n + ".norm2.weight"), h->V(n + ".norm2.bias"), 1e-5f, resid, xn.hi, xn.lo, rows, F, c.s, Fp, fc2_part));
             if (c.block_dump && c.block_dump[blk_index - 1])  // block output tokens [B, N_s, F_s] (image_encoder_model.py:213-225)
                 CHK(hipMemcpyAsync(c.block_dump[blk_index - 1], resid, (size_t)rows * F * 4, hipMemcpyDeviceToDevice, c.s));
+            if (c.norm_wanted(blk_index - 1))  // per-token norms / one channel of the same tokens: fp32 [B, gh_s, gw_s]
+                CHK(OPLC(mdpt_launch_row_norm, resid, c.norm_dump ? (float*)c.norm_dump[blk_index - 1] : nullptr,
+                                             c.chan_dump ? (float*)c.chan_dump[blk_index - 1] : nullptr,
+                                             c.chan_dump && c.chan_dump[blk_index - 1] ? c.chan_index[blk_index - 1] : 0, p.B, g.N, g.N, 0, F, c.s));
         }
         Planes tp = c.pl(p.tap[s]);
         CHK(OPLC(mdpt_launch_f32_to_planes, resid, tp.hi, tp.lo, (size_t)rows, F, Fp, c.s));

@@ -933,7 +933,57 @@ __global__ __launch_bounds__(256) void mask_cutout_kernel(const MaskTable t, dou
     }
 }
 
+// Block norm tiles (experiments/block_norm_visualization.py:137-147 BlockData.__init__, then the nearest-neighbour enlargement of :207-233):
+// one workgroup per (map, image) of the table - maps are token grids, a few thousand floats at most. Pass 1: the map's own min / max (a NaN
+// pins both to NaN, as numpy's min / max do) -> minmax[(map, image)] = {min, max}. Pass 2, in fp32 as numpy computes it, one IEEE operation per
+// step and nothing contracted: u8 = rint(((n - min) / (max - min)) * 255), rint rounding halves to even like np.round; written at the oh x ow
+// tile's pixels (y, x) from map cell (y / fy, x / fx) for the whole factors fy = oh / ih, fx = ow / iw. A value that is not a number (a
+// constant map's 0 / 0, a map holding a NaN: every value of it) gives 0, where the reference's uint8 conversion is undefined.
+__global__ __launch_bounds__(256) void block_norm_tiles_kernel(const PostRunTable t, unsigned char* __restrict__ out, float* __restrict__ minmax) {
+    const int b = blockIdx.x;
+    int j;
+    const PostRun& img = seg_image(t, b, j);
+    const int ih = img.ih, iw = img.iw, oh = img.oh, ow = img.ow;
+    const int n = ih * iw;
+    const float* in = (const float*)img.in + (size_t)j * n;
+    float lo = INFINITY, hi = -INFINITY;
+    bool saw_nan = false;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float v = in[i];
+        saw_nan |= v != v;
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+    __shared__ unsigned smm[2];
+    block_minmax_part(lo, hi, saw_nan, true, smm);  // (n >= 1: thread 0 always holds a value)
+    __syncthreads();
+    const float mn = ord2f(smm[0]), mx = ord2f(smm[1]);
+    if (threadIdx.x == 0) {
+        minmax[2 * (size_t)b] = mn;
+        minmax[2 * (size_t)b + 1] = mx;
+    }
+    const float range = __fsub_rn(mx, mn);
+    const int fy = oh / ih, fx = ow / iw;
+    unsigned char* dst = out + img.off + (size_t)j * oh * ow;
+    for (int i = threadIdx.x; i < oh * ow; i += 256) {
+        const int y = i / ow, x = i - y * ow;
+        const float v = __fmul_rn(__fdiv_rn(__fsub_rn(in[(y / fy) * iw + x / fx], mn), range), 255.0f);
+        dst[i] = v == v ? (unsigned char)(int)rintf(v) : (unsigned char)0;
+    }
+}
+
 }  // namespace
+
+int mdpt_launch_post_block_norm_tiles(const PostRunTable& t, unsigned char* out, float* minmax, hipStream_t stream) {
+    int B;
+    size_t max_in, max_out;
+    if (!table_extent(t, B, max_in, max_out) || max_in > (1u << 24) || max_out > (1u << 24)) return (int)hipErrorInvalidValue;
+    for (int r = 0; r < t.n; ++r)
+        if (t.run[r].oh % t.run[r].ih || t.run[r].ow % t.run[r].iw) return (int)hipErrorInvalidValue;
+    MdptProfScope prof("block_norm_tiles_kernel", 0.0, stream);
+    hipLaunchKernelGGL(block_norm_tiles_kernel, dim3(B), dim3(256), 0, stream, t, out, minmax);
+    return (int)hipGetLastError();
+}
 
 int mdpt_launch_post_minmax(const float* in, size_t n, float* minmax_out, unsigned* scratch2, hipStream_t stream) {
     hipLaunchKernelGGL(minmax_init_kernel, dim3(1), dim3(1), 0, stream, scratch2);

@@ -315,6 +315,76 @@ class ImageEncoder(_Stage):
         return tuple(eng.as_output(o) for o in outs)
 
 
+    def _block_features(self) -> list[int]:
+        """features per token of every block's output, in block order (SwinV2: stage-major, the stage's width)"""
+        cfg = self.__dict__["_owner"].config
+        blocks = self.__dict__.get("_block_probes") or []
+        if "features_per_stage" in cfg:
+            return [int(cfg["features_per_stage"][st]) for _, st in blocks]
+        return [int(cfg["features_per_token"])] * len(blocks)
+
+    def _check_channels(self, channels) -> list[int] | None:
+        """The `channels` argument of block_norms -> one channel index per block (host-side checks only, nothing touches a GPU)."""
+        if channels is None:
+            return None
+        feats = self._block_features()
+        if isinstance(channels, (int, np.integer)) and not isinstance(channels, bool):
+            channels = [int(channels)] * len(feats)
+        if isinstance(channels, (str, bytes)) or not hasattr(channels, "__len__"):
+            raise TypeError(f"block_norms: channels must be an int or one int per block, got {type(channels)}")
+        if len(channels) != len(feats):
+            raise ValueError(f"block_norms: {len(feats)} blocks but {len(channels)} channel indices")
+        out = []
+        for i, (ch, f) in enumerate(zip(channels, feats)):
+            if isinstance(ch, bool) or not isinstance(ch, (int, np.integer)):
+                raise TypeError(f"block_norms: channel index of block {i} must be an int, got {type(ch)}")
+            if not 0 <= int(ch) < f:
+                raise ValueError(f"block_norms: channel index {int(ch)} of block {i} is outside [0, {f})")
+            out.append(int(ch))
+        return out
+
+    def block_norms(self, patch_tokens: Tensor, patch_grid_hw: tuple[int, int], channels=None):
+        """The encoder pass of forward() that also writes the L2 norm of every patch token of every block's output: -> (taps, norms), or
+        (taps, norms, channel_maps) with `channels` (an int for every block, or one int per block). taps is what forward() returns; norms is
+        one fp32 [B, h, w] tensor per block in block order (the order the reference's ModelOutputCapture lists them; SwinV2 stage-major with
+        h, w = the grid >> stage), views into one allocation: block_tensor.norm(dim=-1) with the cls token dropped and reshaped to the patch
+        grid (experiments/block_norm_visualization.py:133-147), taken on the fp32 residual stream whatever the model dtype. channel_maps is
+        the same for tensor[..., channel] (the script's "Channel" view). No block tensor is exported (mdpt_encoder_block_norms) and no
+        forward hook fires or is needed."""
+        chans = self._check_channels(channels)
+        eng = self._engine()
+        x = eng.as_input(patch_tokens, 3)
+        gh, gw = int(patch_grid_hw[0]), int(patch_grid_hw[1])
+        b = x.shape[0]
+        assert x.shape[1] == gh * gw and x.shape[2] == eng.F, f"tokens {tuple(x.shape)} do not match grid {gh}x{gw}, F={eng.F}"
+        blocks = self.__dict__.get("_block_probes") or []
+        if eng.swin:
+            outs = [torch.empty((b, (gh >> s) * (gw >> s), eng.stage_features[s]), device=x.device, dtype=torch.float32) for s in range(4)]
+            size_hw = (gh * eng.P, gw * eng.P)
+            grids = [(gh >> st, gw >> st) for _, st in blocks]
+        else:
+            outs = [torch.empty((b, gh * gw + 1, eng.F), device=x.device, dtype=torch.float32) for _ in range(4)]
+            size_hw = ((gh + gh % 2) * eng.P, (gw + gw % 2) * eng.P)
+            grids = [(gh, gw)] * len(blocks)
+
+        def planes():  # one allocation, block l's [B, h, w] plane after the planes of the blocks before it
+            flat = torch.empty(sum(b * h * w for h, w in grids), device=x.device, dtype=torch.float32)
+            views, at = [], 0
+            for h, w in grids:
+                views.append(flat[at:at + b * h * w].view(b, h, w))
+                at += b * h * w
+            return views, (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
+
+        norms, narr = planes()
+        cmaps, carr, cidx = None, None, None
+        if chans is not None:
+            cmaps, carr = planes()
+            cidx = (ctypes.c_int32 * len(chans))(*chans)
+        eng.call_checked("mdpt_encoder_block_norms", x, b, gh, gw, eng.ptr_array(outs), narr, cidx, carr, size_hw=size_hw, batch=b)
+        taps = tuple(eng.as_output(o) for o in outs)
+        return (taps, norms) if chans is None else (taps, norms, cmaps)
+
+
 class ReassembleModel(_Stage):
     """4 token stages -> 4 image-like maps. reference v2_depthanything/reassembly_model.py:21-310."""
 
@@ -837,6 +907,17 @@ class DPTModel(nn.Module):
                 raise RuntimeError(str(e)) from None  # the reference raises RuntimeError for odd grids too
             raise
         return out
+
+    def block_norms(self, image_rgb_normalized_bchw: Tensor, channels=None):
+        """[B,3,H,W] normalised RGB -> (norms, patch_grid_hw), or (norms, channel_maps, patch_grid_hw) with `channels`: patch_embed followed by
+        imgencoder.block_norms under inference_mode - the capture step of the reference's experiments/block_norm_visualization.py:287-301 for a
+        whole batch, without exporting a single block tensor. norms: one fp32 [B, h, w] map per block (see ImageEncoder.block_norms);
+        postprocess.block_norm_display turns them into the script's tiles."""
+        self.imgencoder._check_channels(channels)  # (before anything touches the device)
+        with torch.inference_mode():
+            tokens, hw = self.patch_embed(image_rgb_normalized_bchw)
+            out = self.imgencoder.block_norms(tokens, hw, channels)
+        return (*out[1:], hw)
 
     def inference(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True) -> Tensor:
         """prepare_image + forward under inference_mode -> [1,H,W] (dpt_model.py:87-109)."""

@@ -187,6 +187,7 @@ SYMBOLS = {
     "mdpt_encoder_probe": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _VP4, _VP4, _VP, _SZ, _VP]),
     "mdpt_attn_probe_shape": (ctypes.c_int, [_VP, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
     "mdpt_encoder_probe_blocks": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _VP4, _VP, _VP, _VP, _SZ, _VP]),
+    "mdpt_encoder_block_norms": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _VP4, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "mdpt_fusion_block": (ctypes.c_int, [_VP, _I, _VP, _VP, _I, _I, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_head": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_prepare_image": (ctypes.c_int, [_VP, _I, _I, _VP, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _I, _VP]),
@@ -216,6 +217,7 @@ SYMBOLS = {
     "mdpt_post_pack_u24_alpha": (ctypes.c_int, [_VP, _I, _SZ, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP]),
     "mdpt_post_mask_display": (ctypes.c_int, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _D, _D, _I, _VP, _I, _I, _VP, _VP, _VP]),
     "mdpt_post_mask_cutout_images": (ctypes.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _D, _VP, _VP, _VP, _I, _D, _D, _I, _VP, _VP, _VP]),
+    "mdpt_post_block_norm_tiles": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

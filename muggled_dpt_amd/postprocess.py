@@ -4,7 +4,8 @@ display tail of its video / image demos per image (histogram_equalization :107-1
 depth_to_color, the whole per-frame loop of run_video.py:348-361 over a batch), the still-image demo's display loop and save path
 (depth_to_display / depth_for_saving, run_image.py:185-195, 323-358, with the plane fit of demo_helpers/plane_fit.py) and the 3D viewer's
 edge alpha (depth_edge_mask / pack_depth_u24_frames, run_3dviewer.py:455-505, 576-593), and the depth masking demo's display and cutouts
-(depth_mask_display / depth_mask_images, experiments/depth_masking.py).
+(depth_mask_display / depth_mask_images, experiments/depth_masking.py), and the tiles of its block norm viewer (block_norm_display,
+experiments/block_norm_visualization.py).
 
 Every function takes the CUDA tensor the model returned and launches HIP kernels (libmdpt: mdpt_post_*) on the current torch
 stream; results stay on the device (the reference's convert_to_uint8 does the same, postprocess.py:85-87). min / max never visit
@@ -786,3 +787,70 @@ def depth_mask_images(predictions, images_bgr, plane_removal: float = 0.0, thres
             int(bool(invert)), bgra.data_ptr(), mask.data_ptr())
     del staged  # (the caching allocator reuses it in stream order only)
     return [(bgra[4 * o:4 * (o + ih * iw)].view(ih, iw, 4), mask[o:o + ih * iw].view(ih, iw)) for o, (ih, iw) in zip(offs, hws)]
+
+
+# ---- block norm tiles: the reference's experiments/block_norm_visualization.py
+
+
+def _block_maps(maps, what: str) -> list:
+    """a list of [B,h,w] maps (sizes may differ between maps) or one [L,B,h,w] tensor -> list of [B,h,w] tensors, shapes checked (host-side only)"""
+    if isinstance(maps, torch.Tensor):
+        if maps.dim() != 4:
+            raise RuntimeError(f"{what} expects a list of [B,h,w] maps or one [L,B,h,w] tensor, got {tuple(maps.shape)}")
+        maps = list(maps.unbind(0))
+    elif not isinstance(maps, (list, tuple)):
+        raise TypeError(f"{what} expects a list of [B,h,w] maps or one [L,B,h,w] tensor, got {type(maps)}")
+    if len(maps) == 0:
+        raise ValueError(f"{what} got no maps")
+    for m in maps:
+        if not isinstance(m, torch.Tensor):
+            raise TypeError(f"{what} expects tensors, got {type(m)}")
+        if m.dim() != 3 or m.numel() == 0:
+            raise RuntimeError(f"{what} expects [B,h,w] maps, got {tuple(m.shape)}")
+    if len({m.shape[0] for m in maps}) != 1:
+        raise ValueError(f"{what}: the maps differ in batch size: {[m.shape[0] for m in maps]}")
+    return list(maps)
+
+
+def block_norm_display(maps, max_token_hw=None, lut=None):
+    """Per-block token maps -> display tiles, BlockData.__init__ and the tile enlargement of the reference's experiments/block_norm_visualization.py
+    (:137-147, :207-233) for every block and image at once. maps: a list of fp32 [B,h_l,w_l] CUDA maps - the norms or channel planes
+    DPTModel.block_norms returns - or one [L,B,h,w] tensor. -> (tiles, minmax):
+      tiles   uint8 [L,B,H,W], or [L,B,H,W,3] BGR through the colormap LUT `lut` (as apply_colormap takes it) when one is given; (H, W) =
+              max_token_hw, by default the largest map. Every (block, image) is normalised by its OWN min / max in fp32 exactly as numpy does it,
+              u8 = round_half_even(((n - min) / (max - min)) * 255) with a true division, and a smaller map is enlarged by the nearest index
+              dst // factor. Only whole factors are taken (all SwinV2's stages produce; every nearest rule, cv2.INTER_NEAREST_EXACT included,
+              agrees there): any other ratio raises ValueError.
+      minmax  fp32 [L,B,2], each map's {min, max}: the norm range of the script's hover label.
+    A constant map (the reference divides 0 / 0) and a map holding a NaN (whose min and max are NaN, and are reported as such) give an all-zero
+    tile: the reference's NaN -> uint8 conversion is undefined. One launch per 32 maps whatever B is (one more for the colormap); nothing is read
+    back."""
+    what = "block_norm_display"
+    ms = _block_maps(maps, what)
+    hws = [(int(m.shape[1]), int(m.shape[2])) for m in ms]
+    if max_token_hw is None:
+        th, tw = max(h for h, _ in hws), max(w for _, w in hws)
+    else:
+        th, tw = int(max_token_hw[0]), int(max_token_hw[1])
+    if th <= 0 or tw <= 0:
+        raise ValueError(f"{what}: bad tile size {max_token_hw}")
+    for l, (h, w) in enumerate(hws):
+        if th % h or tw % w:
+            raise ValueError(f"{what}: map {l} is {h}x{w}, which does not divide the {th}x{tw} tile by whole factors")
+    if any(m.device.type != "cuda" for m in ms):
+        raise RuntimeError(f"{what}: expected CUDA tensors (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+    if len({m.device for m in ms}) != 1:
+        raise RuntimeError(f"{what}: the maps are on different devices")
+    ms = [m.detach().to(torch.float32).contiguous() for m in ms]
+    dev = ms[0].device
+    cmap = _cmap_tensor(lut, dev)
+    n_maps, b = len(ms), ms[0].shape[0]
+    ptrs, hw_arr = _ptrs_hw([m.data_ptr() for m in ms], hws)
+    tiles = torch.empty((n_maps, b, th, tw), device=dev, dtype=torch.uint8)
+    minmax = torch.empty((n_maps, b, 2), device=dev, dtype=torch.float32)
+    _launch(dev, "mdpt_post_block_norm_tiles", ptrs.ctypes.data, hw_arr.ctypes.data, n_maps, b, th, tw, tiles.data_ptr(), minmax.data_ptr())
+    if cmap is None:
+        return tiles, minmax
+    out = torch.empty((n_maps, b, th, tw, 3), device=dev, dtype=torch.uint8)
+    _launch(dev, "mdpt_post_colorize", tiles.data_ptr(), n_maps * b, th * tw, None, cmap.data_ptr(), 3, out.data_ptr())
+    return out, minmax

@@ -9,6 +9,9 @@ For one image, --display saves the still-image demo's BGR frame (postprocess.dep
 --high_contrast as in run_image.py) and --u24 the 3D viewer's BGRA 24-bit frame with its edge alpha (postprocess.pack_depth_u24_frames).
 For one image or several, --cutout DIR saves the depth masking demo's results at each image's own size (postprocess.depth_mask_images:
 --mask MIN MAX, --invert_mask and --remove_plane as in experiments/depth_masking.py): <name>_mask.npy (uint8) and <name>_cutout.npy (BGRA).
+For one image or several, --block_norms DIR saves the per-token L2 norms of every transformer block's output (DPTModel.block_norms, the capture step
+of experiments/block_norm_visualization.py without exporting a block tensor): <name>_blocknorms.npy, fp32 [L, h, w], or an object array of L maps
+when the blocks' grids differ (SwinV2).
 
   python tools/mdpt_run_image.py --synthetic vits --size 518 --fp32
   python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i image.npy -o depth_u8.npy
@@ -47,6 +50,7 @@ def main():
     ap.add_argument("--mask", type=float, nargs=2, default=(0.0, 1.0), metavar=("MIN", "MAX"), help="depth masking: keep pixels whose depth is in MIN..MAX")
     ap.add_argument("--invert_mask", action="store_true", help="depth masking: keep the pixels outside the --mask range instead")
     ap.add_argument("--cutout", default=None, metavar="DIR", help="save every image's depth mask and BGRA cutout (.npy) at its own size into DIR")
+    ap.add_argument("--block_norms", default=None, metavar="DIR", help="save every image's per-block token norm maps (.npy) into DIR")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mdpt_run_image needs an MI355X: no GPU visible (there is no CPU fallback)")
@@ -87,6 +91,7 @@ def main():
         np.save(args.u24, pack_depth_u24_frames(depth, is_metric=bool(cfg.get("is_metric", False)))[0].cpu().numpy())
         print("saved", args.u24)
     save_cutouts(args, args.image_path or ["synthetic.npy"], [img], [depth])
+    save_block_norms(model, args, args.image_path or ["synthetic.npy"], [img])
 
 
 def save_cutouts(args, paths, images, depths):
@@ -101,6 +106,32 @@ def save_cutouts(args, paths, images, depths):
         np.save(stem + "_mask.npy", mask.cpu().numpy())
         np.save(stem + "_cutout.npy", cutout.cpu().numpy())
         print("saved", stem + "_mask.npy", stem + "_cutout.npy")
+
+
+def save_block_norms(model, args, paths, images):
+    """--block_norms: one DPTModel.block_norms call per group of images that share a model tensor size"""
+    if not args.block_norms:
+        return
+    os.makedirs(args.block_norms, exist_ok=True)
+    groups = {}
+    for k, img in enumerate(images):
+        x = model.prepare_image_bgr(img, args.size, not args.use_aspect_ratio)
+        groups.setdefault(tuple(x.shape[2:]), []).append((k, x))
+    for members in groups.values():
+        for at in range(0, len(members), args.batch_size):
+            chunk = members[at:at + args.batch_size]
+            norms, _ = model.block_norms(torch.cat([x for _, x in chunk]))
+            host = [n.cpu().numpy() for n in norms]
+            for row, (k, _) in enumerate(chunk):
+                maps = [h[row] for h in host]
+                if len({m.shape for m in maps}) == 1:
+                    arr = np.stack(maps)
+                else:
+                    arr = np.empty(len(maps), dtype=object)
+                    arr[:] = maps
+                out = os.path.join(args.block_norms, os.path.splitext(os.path.basename(paths[k]))[0] + "_blocknorms.npy")
+                np.save(out, arr, allow_pickle=True)
+                print("saved", out)
 
 
 def run_images(model, args, t0):
@@ -126,6 +157,7 @@ def run_images(model, args, t0):
             np.save(out, g[0, :, :, 0].cpu().numpy())
             print("saved", out)
     save_cutouts(args, args.image_path, images, depths)
+    save_block_norms(model, args, args.image_path, images)
 
 
 if __name__ == "__main__":
