@@ -1,5 +1,5 @@
-// libmdpt: the C ABI of include/mdpt.h (entry points only; inventory / plan: mdpt_inventory.cpp, stage drivers: mdpt_stages.cpp,
-// test hooks: mdpt_debug.cpp).
+// libmdpt: the model half of the C ABI of include/mdpt.h (entry points only; inventory / plan: mdpt_inventory.cpp, stage drivers: mdpt_stages.cpp,
+// test hooks: mdpt_debug.cpp, depth post-processing: mdpt_post.cpp).
 #include "mdpt_internal.h"
 
 // =====================================================================================================================
@@ -226,7 +226,7 @@ int mdpt_weight_shape(const mdpt_handle* h, int index, int32_t* ndim, int64_t sh
 
 int mdpt_bind_weight(mdpt_handle* h, const char* name, const void* dev_ptr, int32_t dtype, int32_t ndim, const int64_t* shape) {
     if (!h || !name || !dev_ptr || !shape) return fail(MDPT_E_INVALID, "null argument");
-    if (dtype != MDPT_DTYPE_F32 && dtype != MDPT_DTYPE_BF16 && dtype != MDPT_DTYPE_F16) return fail(MDPT_E_INVALID, "bad dtype %d for \"%s\"", dtype, name);
+    if (!tensor_dtype_ok(dtype)) return fail(MDPT_E_INVALID, "bad dtype %d for \"%s\"", dtype, name);
     auto it = h->spec_index.find(name);
     if (it == h->spec_index.end()) return fail(MDPT_E_INVALID, "unexpected parameter \"%s\" (not part of this model config)", name);
     WeightSpec& s = h->specs[it->second];
@@ -427,6 +427,23 @@ static int ensure_side_stream(mdpt_handle* h, hipStream_t s0, void* scratch) {
     return 0;
 }
 
+// Joins the side stream back into the caller's stream after a fork (forward_batch's second half batch, forward_body's reassembly branches),
+// with `rc` the status of whatever was queued in between - ALSO when that failed:
+//  - batch split: whatever happens after the fork, the side stream is joined back into the caller's stream before returning: kernels already
+//    queued there keep using the second half of the workspace and the caller's tensors, which the caller may free or reuse on its
+//    own stream as soon as this call returns (also on the error path);
+//  - unsplit (small-batch) forward: reassembly branches run on the side stream beside the encoder (run_encoder, Ctx::tap_stream); whatever
+//    happens in between, the side stream is joined back into the caller's stream before anything else is queued or returned.
+// Returns rc if that is an error, the join's status otherwise.
+static int join_side_stream(mdpt_handle* h, hipStream_t caller, int rc) {
+    const hipError_t ej = hipEventRecord(h->ev_join, h->side_stream);
+    const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(caller, h->ev_join, 0) : ej;
+    if (ew != hipSuccess) hipStreamSynchronize(h->side_stream);  // last resort: never leave the side stream running un-joined
+    if (rc != 0) return rc;
+    CHK(ew);
+    return 0;
+}
+
 static inline size_t dtype_bytes(int dt) { return dt == MDPT_DTYPE_F32 ? 4 : 2; }
 
 // mdpt_forward and mdpt_forward_bgr_batch / _frames: the source is either an image tensor (image_bchw) or, when bgr != NULL, B uint8 frames the
@@ -464,17 +481,11 @@ static int forward_batch(mdpt_handle* h, const void* image_bchw, const Ctx::BgrS
                 c1.bgr.ptr += (size_t)B0 * bgr->ih * bgr->iw * 3;
             }
         }
-        // Whatever happens after the fork, the side stream is joined back into the caller's stream before returning: kernels already
-        // queued there keep using the second half of the workspace and the caller's tensors, which the caller may free or reuse on its
-        // own stream as soon as this call returns (also on the error path).
         int rc = forward_one(h, c0, image_bchw, image_dtype, depth_bhw, depth_dtype);
         if (rc == 0) rc = forward_one(h, c1, bgr ? nullptr : (const char*)image_bchw + in_stride * B0, image_dtype, (char*)depth_bhw + out_stride * B0, depth_dtype);
-        const hipError_t ej = hipEventRecord(h->ev_join, h->side_stream);
-        const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(s0, h->ev_join, 0) : ej;
-        if (ew != hipSuccess) hipStreamSynchronize(h->side_stream);  // last resort: never leave the side stream running un-joined
+        rc = join_side_stream(h, s0, rc);  // (also on the error path)
         h->has_last = false;  // taps live in two half-batch plans: mdpt_export_tap is for unsplit (small) batches
         if (rc != 0) return rc;
-        CHK(ew);
         if (h->grid_cache && h->dbg_block < 0) { h->cache_store(0, c0.ws, B0, H, W); h->cache_store(1, c1.ws, B1, H, W); }
         return 0;
     }
@@ -488,11 +499,23 @@ static int forward_batch(mdpt_handle* h, const void* image_bchw, const Ctx::BgrS
     return 0;
 }
 
+static int check_interp(int interpolation) {
+    if (!interp_ok(interpolation))
+        return fail(MDPT_E_UNSUPPORTED, "interpolation %d: antialiased resize exists for bilinear and bicubic only (as in torch)", interpolation);
+    return 0;
+}
+
+// what every uint8 BGR source of the fused im2col shares; the caller adds where the frames are (packed: ptr, ih, iw; a table: frames, frames_hw)
+static void fill_bgr_source(Ctx::BgrSource& src, int image_dtype, int interpolation, const float rgb_mean[3], const float rgb_std[3]) {
+    src.round_dtype = image_dtype; src.interp = interpolation;
+    for (int i = 0; i < 3; ++i) { src.mean[i] = rgb_mean[i]; src.inv_std[i] = 1.0f / rgb_std[i]; }  // patch_embed.py:38-39,62
+}
+
 int mdpt_forward(mdpt_handle* h, const void* image_bchw, int32_t image_dtype, int32_t B, int32_t H, int32_t W, void* depth_bhw,
                  int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !image_bchw || !depth_bhw) return fail(MDPT_E_INVALID, "null argument");
     for (int dt : {image_dtype, depth_dtype})
-        if (dt != MDPT_DTYPE_F32 && dt != MDPT_DTYPE_BF16 && dt != MDPT_DTYPE_F16) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
+        if (!tensor_dtype_ok(dt)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
     return forward_batch(h, image_bchw, nullptr, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
 }
 
@@ -503,14 +526,13 @@ int mdpt_forward_bgr_batch(mdpt_handle* h, const void* bgr_u8_bhwc, int32_t B, i
                            size_t workspace_bytes, void* stream) {
     if (!h || !bgr_u8_bhwc || !depth_bhw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
     for (int dt : {image_dtype, depth_dtype})
-        if (dt != MDPT_DTYPE_F32 && dt != MDPT_DTYPE_BF16 && dt != MDPT_DTYPE_F16) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
-    if (interpolation != MDPT_INTERP_BILINEAR && interpolation != MDPT_INTERP_BICUBIC)
-        return fail(MDPT_E_UNSUPPORTED, "interpolation %d: antialiased resize exists for bilinear and bicubic only (as in torch)", interpolation);
+        if (!tensor_dtype_ok(dt)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
+    CHK(check_interp(interpolation));
     if (in_h <= 0 || in_w <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d", in_h, in_w);
     if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);  // (the im2col kernel's grid y is the frame index)
     Ctx::BgrSource src;
-    src.ptr = (const unsigned char*)bgr_u8_bhwc; src.ih = in_h; src.iw = in_w; src.round_dtype = image_dtype; src.interp = interpolation;
-    for (int i = 0; i < 3; ++i) { src.mean[i] = rgb_mean[i]; src.inv_std[i] = 1.0f / rgb_std[i]; }  // patch_embed.py:38-39,62
+    fill_bgr_source(src, image_dtype, interpolation, rgb_mean, rgb_std);
+    src.ptr = (const unsigned char*)bgr_u8_bhwc; src.ih = in_h; src.iw = in_w;
     return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
 }
 
@@ -520,17 +542,16 @@ int mdpt_forward_bgr_frames(mdpt_handle* h, const void* const* frames_u8_hwc, co
                             size_t workspace_bytes, void* stream) {
     if (!h || !frames_u8_hwc || !frames_hw || !depth_bhw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
     for (int dt : {image_dtype, depth_dtype})
-        if (dt != MDPT_DTYPE_F32 && dt != MDPT_DTYPE_BF16 && dt != MDPT_DTYPE_F16) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
-    if (interpolation != MDPT_INTERP_BILINEAR && interpolation != MDPT_INTERP_BICUBIC)
-        return fail(MDPT_E_UNSUPPORTED, "interpolation %d: antialiased resize exists for bilinear and bicubic only (as in torch)", interpolation);
+        if (!tensor_dtype_ok(dt)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
+    CHK(check_interp(interpolation));
     if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
     for (int b = 0; b < B; ++b) {
         if (!frames_u8_hwc[b]) return fail(MDPT_E_INVALID, "null argument (frame %d)", b);
         if (frames_hw[2 * b] <= 0 || frames_hw[2 * b + 1] <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d (frame %d)", frames_hw[2 * b], frames_hw[2 * b + 1], b);
     }
     Ctx::BgrSource src;
-    src.frames = frames_u8_hwc; src.frames_hw = frames_hw; src.round_dtype = image_dtype; src.interp = interpolation;
-    for (int i = 0; i < 3; ++i) { src.mean[i] = rgb_mean[i]; src.inv_std[i] = 1.0f / rgb_std[i]; }  // patch_embed.py:38-39,62
+    fill_bgr_source(src, image_dtype, interpolation, rgb_mean, rgb_std);
+    src.frames = frames_u8_hwc; src.frames_hw = frames_hw;
     return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
 }
 
@@ -576,17 +597,12 @@ static int forward_body(mdpt_handle* h, const Ctx& c, const void* image_bchw, in
     // loses or ties (its K-split decoder convs own the encoder's partial-sum planes and stand down on the side stream) - hence the rule
     const bool overlap = h->overlap_reasm == 2 || (h->overlap_reasm == 1 && !h->latency_mode && h->F >= 1024);
     if (!c.split && overlap && h->dbg_block < 0) {
-        // unsplit (small-batch) forward: reassembly branches run on the side stream beside the encoder (run_encoder, Ctx::tap_stream); whatever
-        // happens in between, the side stream is joined back into the caller's stream before anything else is queued or returned
+        // unsplit (small-batch) forward: reassembly branches run on the side stream beside the encoder, joined before the fusion is queued
         CHK(ensure_side_stream(h, c.s, c.ws + c.p.probe));
         Ctx ce = c;
         ce.tap_stream = h->side_stream; ce.tap_event = h->ev_fork;
-        const int rc = run_encoder(ce, nullptr);
-        const hipError_t ej = hipEventRecord(h->ev_join, h->side_stream);
-        const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(c.s, h->ev_join, 0) : ej;
-        if (ew != hipSuccess) hipStreamSynchronize(h->side_stream);
+        const int rc = join_side_stream(h, c.s, run_encoder(ce, nullptr));  // (also on the error path)
         if (rc != 0) return rc;
-        CHK(ew);
         Ctx cf = c;
         cf.a1_done = true;
         CHK(run_fusion(cf, true));
@@ -628,15 +644,21 @@ int mdpt_patch_embed(mdpt_handle* h, const void* image_bchw, int32_t B, int32_t 
     return 0;
 }
 
-int mdpt_encoder(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4], void* workspace,
-                 size_t workspace_bytes, void* stream) {
+// The encoder pass behind mdpt_encoder, mdpt_encoder_probe[_blocks] and mdpt_encoder_block_norms: PatchEmbed tokens in, the four stage outputs
+// out, plus whatever per-block dumps are asked for (each array may be NULL: Ctx::attn_dump ... chan_dump)
+static int encoder_with_dumps(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4], void* const* attn_out,
+                              void* const* block_out, void* const* norm_out, const int32_t* channel_index, void* const* channel_out, void* workspace,
+                              size_t workspace_bytes, void* stream) {
     if (!h || !tokens_bnf || !stage_out) return fail(MDPT_E_INVALID, "null argument");
     for (int i = 0; i < 4; ++i)
         if (!stage_out[i]) return fail(MDPT_E_INVALID, "null stage output %d", i);
     if (gh <= 0 || gw <= 0) return fail(MDPT_E_INVALID, "bad grid");
     Ctx c;
-    if (h->swin) {  // tokens = PatchEmbed output [B, gh*gw, F0]; stage s output is [B, (gh>>s)*(gw>>s), F_s]
-        CHK(make_ctx(h, B, gh * h->P, gw * h->P, workspace, workspace_bytes, stream, &c));
+    const int ph = h->swin ? gh : rup(gh, 2), pw = h->swin ? gw : rup(gw, 2);  // (ViT / BEiT plans exist for even grids only)
+    CHK(make_ctx(h, B, ph * h->P, pw * h->P, workspace, workspace_bytes, stream, &c));
+    c.attn_dump = attn_out; c.block_dump = block_out;
+    c.norm_dump = norm_out; c.chan_dump = channel_out; c.chan_index = channel_index;
+    if (h->swin) {  // tokens = PatchEmbed output [B, gh*gw, F0]; stage s output is [B, (gh>>s)*(gw>>s), F_s]; dumps in stage-major block order
         const size_t n = (size_t)B * gh * gw * h->F;
         Planes xn = c.pl(c.p.sw.xn);
         CHK(hipMemcpyAsync(c.at<float>(c.p.sw.resid[0]), tokens_bnf, n * 4, hipMemcpyDeviceToDevice, c.s));
@@ -646,7 +668,6 @@ int mdpt_encoder(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, 
         h->has_last = false;
         return 0;
     }
-    CHK(make_ctx(h, B, rup(gh, 2) * h->P, rup(gw, 2) * h->P, workspace, workspace_bytes, stream, &c));
     // the encoder itself does not need an even grid: re-derive token counts for the true grid
     c.p.gh = gh; c.p.gw = gw; c.p.Np = gh * gw; c.p.N = c.p.Np + 1;
     if (rup(c.p.N, 8) > c.p.npad) return fail(MDPT_E_INVALID, "internal: plan too small");
@@ -664,6 +685,11 @@ int mdpt_encoder(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, 
     return 0;
 }
 
+int mdpt_encoder(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4], void* workspace,
+                 size_t workspace_bytes, void* stream) {
+    return encoder_with_dumps(h, tokens_bnf, B, gh, gw, stage_out, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
 // mdpt_encoder + explicit attention weights of selected blocks (enable_optimizations=False semantics of the reference: the
 // nn.Softmax output of every block is observable, experiments/attention_visualization.py:325-332). attn_out has num_blocks
 // entries; a non-null entry receives that block's softmax(q k^T / sqrt(d) [+ bias]) as fp32 [B, heads, N, N].
@@ -675,47 +701,6 @@ int mdpt_encoder_probe(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_
 
 // ... and / or the output tokens of selected blocks (what a forward hook on a TransformerBlock sees: demo_helpers/model_capture.py:54-59
 // used by experiments/block_norm_visualization.py:282)
-// (the pass behind mdpt_encoder_probe_blocks and mdpt_encoder_block_norms: mdpt_encoder plus whatever dumps are asked for)
-static int encoder_with_dumps(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4], void* const* attn_out,
-                              void* const* block_out, void* const* norm_out, const int32_t* channel_index, void* const* channel_out, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    if (!h || !tokens_bnf || !stage_out) return fail(MDPT_E_INVALID, "null argument");
-    for (int i = 0; i < 4; ++i)
-        if (!stage_out[i]) return fail(MDPT_E_INVALID, "null stage output %d", i);
-    if (gh <= 0 || gw <= 0) return fail(MDPT_E_INVALID, "bad grid");
-    Ctx c;
-    if (h->swin) {  // as mdpt_encoder, plus the window-attention weights of the listed blocks (stage-major block order)
-        CHK(make_ctx(h, B, gh * h->P, gw * h->P, workspace, workspace_bytes, stream, &c));
-        c.attn_dump = attn_out; c.block_dump = block_out;
-        c.norm_dump = norm_out; c.chan_dump = channel_out; c.chan_index = channel_index;
-        const size_t n = (size_t)B * gh * gw * h->F;
-        Planes xn = c.pl(c.p.sw.xn);
-        CHK(hipMemcpyAsync(c.at<float>(c.p.sw.resid[0]), tokens_bnf, n * 4, hipMemcpyDeviceToDevice, c.s));
-        CHK(swin_zero_pad_planes(c, B * gh * gw));
-        CHK(OPLC(mdpt_launch_f32_to_planes, (const float*)tokens_bnf, xn.hi, xn.lo, (size_t)B * gh * gw, h->F, rup(h->F, 64), c.s));
-        CHK(run_encoder_swin(c, stage_out));
-        h->has_last = false;
-        return 0;
-    }
-    CHK(make_ctx(h, B, rup(gh, 2) * h->P, rup(gw, 2) * h->P, workspace, workspace_bytes, stream, &c));
-    c.p.gh = gh; c.p.gw = gw; c.p.Np = gh * gw; c.p.N = c.p.Np + 1;
-    if (rup(c.p.N, 8) > c.p.npad) return fail(MDPT_E_INVALID, "internal: plan too small");
-    c.p.npad = rup(c.p.N, 8); c.p.npadv = rup(c.p.N, 64);
-    c.attn_dump = attn_out; c.block_dump = block_out;
-    c.norm_dump = norm_out; c.chan_dump = channel_out; c.chan_index = channel_index;
-    if (is_beit(h)) {
-        CHK(OPLC(mdpt_launch_memset_f32, c.at<float>(c.p.pos), 0.0f, (size_t)c.p.Np * h->F, c.s));
-    } else {
-        CHK(run_pos(c));
-    }
-    CHK(OPLC(mdpt_launch_init_tokens, c.at<float>(c.p.resid), h->V("imgencoder.cls_token"), is_beit(h) ? nullptr : h->V("imgencoder.posenc.cls_embedding"),
-                                B, c.p.N, c.p.npad, h->F, c.s));
-    CHK(OPLC(mdpt_launch_tokens_to_resid, (const float*)tokens_bnf, c.at<float>(c.p.pos), c.at<float>(c.p.resid), B, c.p.Np, c.p.npad, h->F, c.s));
-    CHK(run_encoder(c, stage_out));
-    h->has_last = false;
-    return 0;
-}
-
 int mdpt_encoder_probe_blocks(mdpt_handle* h, const void* tokens_bnf, int32_t B, int32_t gh, int32_t gw, void* const stage_out[4],
                               void* const* attn_out, void* const* block_out, void* workspace, size_t workspace_bytes, void* stream) {
     return encoder_with_dumps(h, tokens_bnf, B, gh, gw, stage_out, attn_out, block_out, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
@@ -786,6 +771,21 @@ int mdpt_reassemble(mdpt_handle* h, const void* const stage_in[4], int32_t B, in
     return 0;
 }
 
+// What the stage-level calls and tap 8 return of a fused map: the level's output at workspace offset `src` ([B, sh, sw, Cp] NHWC) upsampled x2 into
+// `tmp` and written as fp32 NCHW [B, C, 2sh, 2sw] to `out`. as16: the map is the 16-bit output of the last projection (head_upsamples_bf16), upsampled
+// with the head's own arithmetic (up_bf16.h) into 16-bit elements; otherwise fp32 throughout. `tmp` is the caller's choice: mdpt_debug_read sees it.
+static int fused_to_nchw(const Ctx& c, size_t src, bool as16, void* tmp, int B, int sh, int sw, void* out) {
+    const mdpt_handle* h = c.h;
+    if (as16) {
+        CHK(OPLC(mdpt_launch_upsample_bf16, c.at<op_t>(src), (op_t*)tmp, B, sh, sw, 2 * sh, 2 * sw, h->Cp, c.s));
+        CHK(OPLC(mdpt_launch_nhwc_to_nchw, nullptr, (const op_t*)tmp, nullptr, (float*)out, B, 2 * sh, 2 * sw, h->C, h->Cp, c.s));
+        return 0;
+    }
+    CHK(OPLC(mdpt_launch_upsample, c.at<float>(src), nullptr, nullptr, (float*)tmp, B, sh, sw, 2 * sh, 2 * sw, h->Cp, c.s));
+    CHK(OPLC(mdpt_launch_nhwc_to_nchw, (const float*)tmp, nullptr, nullptr, (float*)out, B, 2 * sh, 2 * sw, h->C, h->Cp, c.s));
+    return 0;
+}
+
 int mdpt_fusion(mdpt_handle* h, const void* const maps_in[4], int32_t B, int32_t gh, int32_t gw, void* fused_out, void* workspace,
                 size_t workspace_bytes, void* stream) {
     if (!h || !maps_in || !fused_out) return fail(MDPT_E_INVALID, "null argument");
@@ -798,21 +798,12 @@ int mdpt_fusion(mdpt_handle* h, const void* const maps_in[4], int32_t B, int32_t
         Planes rb = c.pl(p.r_bf[i]);
         CHK(OPLC(mdpt_launch_nchw_to_nhwc, (const float*)maps_in[i], c.at<float>(p.r_f32[i]), rb.hi, rb.lo, 1, B, sh[i], sw[i], h->C, h->Cp, c.s, rb.lo ? rb.f8 : 0, rb.f8_a8));
     }
-    if (head_upsamples_bf16(h)) {
-        // single-pass head: the fused forward hands the head the 16-bit output of the last projection and upsamples THAT (run_fusion(c, true) +
-        // up_bf16.h arithmetic, inside head conv 1 or stand-alone: same bits). The stage-level call returns exactly that map, so a pipeline
-        // driven sub-module by sub-module (hooks registered, simple_examples/internal_features.py) predicts the same bits as DPTModel.forward
-        CHK(run_fusion(c, true));
-        Planes fu = c.pl(p.fused);
-        CHK(OPLC(mdpt_launch_upsample_bf16, c.at<op_t>(p.flo[0]), fu.hi, B, sh[0], sw[0], 2 * sh[0], 2 * sw[0], h->Cp, c.s));
-        CHK(OPLC(mdpt_launch_nhwc_to_nchw, nullptr, fu.hi, nullptr, (float*)fused_out, B, 8 * gh, 8 * gw, h->C, h->Cp, c.s));
-        h->has_last = false;
-        return 0;
-    }
-    CHK(run_fusion(c));
-    float* tmp = c.at<float>(p.scratch);
-    CHK(OPLC(mdpt_launch_upsample, c.at<float>(p.flo[0]), nullptr, nullptr, tmp, B, sh[0], sw[0], 2 * sh[0], 2 * sw[0], h->Cp, c.s));
-    CHK(OPLC(mdpt_launch_nhwc_to_nchw, tmp, nullptr, nullptr, (float*)fused_out, B, 8 * gh, 8 * gw, h->C, h->Cp, c.s));
+    // single-pass head: the fused forward hands the head the 16-bit output of the last projection and upsamples THAT (run_fusion(c, true) +
+    // up_bf16.h arithmetic, inside head conv 1 or stand-alone: same bits). The stage-level call returns exactly that map, so a pipeline
+    // driven sub-module by sub-module (hooks registered, simple_examples/internal_features.py) predicts the same bits as DPTModel.forward
+    const bool to_head16 = head_upsamples_bf16(h);
+    CHK(run_fusion(c, to_head16));
+    CHK(fused_to_nchw(c, p.flo[0], to_head16, to_head16 ? (void*)c.pl(p.fused).hi : c.at<void>(p.scratch), B, sh[0], sw[0], fused_out));
     h->has_last = false;
     return 0;
 }
@@ -869,15 +860,7 @@ int mdpt_fusion_block(mdpt_handle* h, int32_t index, const void* reasm_in, const
         g.ldc = h->Cp;
         CHK(OPLC(mdpt_launch_gemm, g, c.s));
     }
-    float* tmp = c.at<float>(p.scratch);
-    if (to_head16) {
-        CHK(OPLC(mdpt_launch_upsample_bf16, c.at<op_t>(p.flo[0]), (op_t*)tmp, B, sh, sw, 2 * sh, 2 * sw, h->Cp, c.s));
-        CHK(OPLC(mdpt_launch_nhwc_to_nchw, nullptr, (const op_t*)tmp, nullptr, (float*)out, B, 2 * sh, 2 * sw, h->C, h->Cp, c.s));
-        h->has_last = false;
-        return 0;
-    }
-    CHK(OPLC(mdpt_launch_upsample, c.at<float>(p.flo[i]), nullptr, nullptr, tmp, B, sh, sw, 2 * sh, 2 * sw, h->Cp, c.s));
-    CHK(OPLC(mdpt_launch_nhwc_to_nchw, tmp, nullptr, nullptr, (float*)out, B, 2 * sh, 2 * sw, h->C, h->Cp, c.s));
+    CHK(fused_to_nchw(c, p.flo[i], to_head16, c.at<void>(p.scratch), B, sh, sw, out));
     h->has_last = false;
     return 0;
 }
@@ -913,14 +896,8 @@ int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspac
         const int i = which - 4;
         CHK(OPLC(mdpt_launch_nhwc_to_nchw, c.at<float>(p.r_f32[i]), nullptr, nullptr, (float*)out_f32, p.B, sh[i], sw[i], h->C, h->Cp, c.s));
     } else if (which == 8) {
-        float* tmp = c.at<float>(p.scratch);
-        if (head_upsamples_bf16(h)) {  // the forward left the last projection as a bf16 map (run_fusion(c, true)): same upsample as the head's
-            CHK(OPLC(mdpt_launch_upsample_bf16, c.at<op_t>(p.flo[0]), (op_t*)tmp, p.B, sh[0], sw[0], 2 * sh[0], 2 * sw[0], h->Cp, c.s));
-            CHK(OPLC(mdpt_launch_nhwc_to_nchw, nullptr, (const op_t*)tmp, nullptr, (float*)out_f32, p.B, 8 * p.gh, 8 * p.gw, h->C, h->Cp, c.s));
-        } else {
-            CHK(OPLC(mdpt_launch_upsample, c.at<float>(p.flo[0]), nullptr, nullptr, tmp, p.B, sh[0], sw[0], 2 * sh[0], 2 * sw[0], h->Cp, c.s));
-            CHK(OPLC(mdpt_launch_nhwc_to_nchw, tmp, nullptr, nullptr, (float*)out_f32, p.B, 8 * p.gh, 8 * p.gw, h->C, h->Cp, c.s));
-        }
+        // (single-pass head: the forward left the last projection as a bf16 map, run_fusion(c, true): same upsample as the head's)
+        CHK(fused_to_nchw(c, p.flo[0], head_upsamples_bf16(h), c.at<void>(p.scratch), p.B, sh[0], sw[0], out_f32));
     } else {
         return fail(MDPT_E_INVALID, "unknown tap %d", which);
     }
@@ -931,333 +908,11 @@ int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspac
 int mdpt_prepare_image(const void* bgr_u8_hwc, int32_t in_h, int32_t in_w, void* out_chw, int32_t out_dtype, int32_t out_h, int32_t out_w,
                        const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* stream) {
     if (!bgr_u8_hwc || !out_chw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
-    if (out_dtype != MDPT_DTYPE_F32 && out_dtype != MDPT_DTYPE_BF16 && out_dtype != MDPT_DTYPE_F16) return fail(MDPT_E_INVALID, "bad tensor dtype %d", out_dtype);
-    if (interpolation != MDPT_INTERP_BILINEAR && interpolation != MDPT_INTERP_BICUBIC)
-        return fail(MDPT_E_UNSUPPORTED, "interpolation %d: antialiased resize exists for bilinear and bicubic only (as in torch)", interpolation);
+    if (!tensor_dtype_ok(out_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", out_dtype);
+    CHK(check_interp(interpolation));
     if (in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d -> %dx%d", in_h, in_w, out_h, out_w);
     const float inv_std[3] = {1.0f / rgb_std[0], 1.0f / rgb_std[1], 1.0f / rgb_std[2]};  // patch_embed.py:38-39,62
     CHK(mdpt_launch_prepare_image_bf16((const unsigned char*)bgr_u8_hwc, out_chw, out_dtype, in_h, in_w, out_h, out_w, rgb_mean, inv_std, interpolation, (hipStream_t)stream));
-    return 0;
-}
-
-// ---- depth post-processing (demo_helpers/postprocess.py, run_3dviewer.py:576-590)
-int mdpt_post_minmax(const void* in_f32, size_t count, void* minmax_out, void* scratch8, void* stream) {
-    if (!in_f32 || !minmax_out || !scratch8 || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
-    CHK(mdpt_launch_post_minmax((const float*)in_f32, count, (float*)minmax_out, (unsigned*)scratch8, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_scale_prediction(const void* in_bhw_f32, int32_t B, int32_t in_h, int32_t in_w, void* out_bhw_f32, int32_t out_h,
-                               int32_t out_w, void* minmax_out, void* scratch8, void* stream) {
-    if (!in_bhw_f32 || !out_bhw_f32 || (minmax_out && !scratch8)) return fail(MDPT_E_INVALID, "null argument");
-    if (B <= 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0) return fail(MDPT_E_INVALID, "bad size %dx%dx%d -> %dx%d", B, in_h, in_w, out_h, out_w);
-    CHK(mdpt_launch_post_scale((const float*)in_bhw_f32, (float*)out_bhw_f32, B, in_h, in_w, out_h, out_w, (float*)minmax_out,
-                               (unsigned*)scratch8, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_normalize(const void* in_f32, size_t count, const void* minmax, void* out, int32_t mode, int32_t lossy, void* stream) {
-    if (!in_f32 || !out || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
-    if (mode < MDPT_POST_F32 || mode > MDPT_POST_U24) return fail(MDPT_E_INVALID, "unknown post-processing mode %d", mode);
-    CHK(mdpt_launch_post_normalize((const float*)in_f32, (const float*)minmax, out, count, mode, lossy, (hipStream_t)stream));
-    return 0;
-}
-
-// ---- per-image display tail (run_video.py:348-361 per frame, over a batch; demo_helpers/postprocess.py:107-145, toadui/colormaps.py:237-259)
-static bool post_dtype_ok(int dt) { return dt == MDPT_DTYPE_F32 || dt == MDPT_DTYPE_BF16 || dt == MDPT_DTYPE_F16; }
-
-// the one-run image table of a uniform batch: B images of ih x iw (-> oh x ow) packed from `in`, outputs packed from element 0
-static PostRunTable uniform_table(const void* in, int B, int ih, int iw, int oh, int ow) {
-    PostRunTable t{};
-    t.n = 1;
-    t.run[0] = PostRun{in, 0, ih, iw, oh, ow, B};
-    return t;
-}
-
-// a uint8 / map count as the ih x iw of one table entry (1 x count)
-static bool count_as_hw(size_t count, int& ih, int& iw) {
-    if (count == 0 || count > (size_t)INT32_MAX) return false;
-    ih = 1;
-    iw = (int)count;
-    return true;
-}
-
-int mdpt_post_minmax_seg(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t in_h, int32_t in_w, void* out_bhw_f32, int32_t out_h, int32_t out_w,
-                         void* parts, void* hist_clear, void* stream) {
-    if (!in_bhw || !parts) return fail(MDPT_E_INVALID, "null argument");
-    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
-    if (B <= 0 || B > 65535 || in_h <= 0 || in_w <= 0 || (out_bhw_f32 && (out_h <= 0 || out_w <= 0)))
-        return fail(MDPT_E_INVALID, "bad size %dx%dx%d -> %dx%d", B, in_h, in_w, out_h, out_w);
-    const PostRunTable t = uniform_table(in_bhw, B, in_h, in_w, out_bhw_f32 ? out_h : in_h, out_bhw_f32 ? out_w : in_w);
-    CHK(mdpt_launch_post_seg_minmax(t, in_dtype, (float*)out_bhw_f32, (unsigned*)parts, (unsigned*)hist_clear, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_u8_hist_seg(const void* in_bhw, int32_t in_dtype, int32_t B, size_t count, const void* parts, int32_t reverse, void* out_u8, void* hist,
-                          void* stream) {
-    if (!in_bhw || !parts || !out_u8 || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
-    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
-    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
-    int ih, iw;
-    if (!count_as_hw(count, ih, iw)) return fail(MDPT_E_INVALID, "bad image size %zu", count);
-    CHK(mdpt_launch_post_seg_u8(uniform_table(in_bhw, B, ih, iw, ih, iw), in_dtype, (const unsigned*)parts, reverse != 0, (unsigned char*)out_u8,
-                                (unsigned*)hist, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_histogram(const void* in_u8, int32_t B, size_t count, void* hist, void* stream) {
-    if (!in_u8 || !hist || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
-    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
-    CHK(mdpt_launch_post_hist((const unsigned char*)in_u8, B, count, (unsigned*)hist, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_equalize_lut(const void* hist, int32_t B, const void* bin_of_value, int32_t min_value, int32_t max_value, void* lut_out, void* stream) {
-    if (!hist || !lut_out) return fail(MDPT_E_INVALID, "null argument");
-    if (B <= 0) return fail(MDPT_E_INVALID, "bad batch %d", B);
-    if (bin_of_value && (min_value < 0 || max_value > 255 || max_value <= min_value))
-        return fail(MDPT_E_INVALID, "bad equalization range [%d, %d]", min_value, max_value);
-    CHK(mdpt_launch_post_eq_lut((const unsigned*)hist, B, (const int*)bin_of_value, min_value, max_value, (unsigned char*)lut_out, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_colorize(const void* in_u8, int32_t B, size_t count, const void* eq_lut, const void* cmap_bgr, int32_t channels, void* out, void* stream) {
-    if (!in_u8 || !out || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
-    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
-    if (channels != 1 && channels != 3) return fail(MDPT_E_INVALID, "channels must be 1 or 3, got %d", channels);
-    int ih, iw;
-    if (!count_as_hw(count, ih, iw)) return fail(MDPT_E_INVALID, "bad image size %zu", count);
-    CHK(mdpt_launch_post_colorize(uniform_table(in_u8, B, ih, iw, ih, iw), (const unsigned char*)eq_lut, (const unsigned char*)cmap_bgr, channels,
-                                  (unsigned char*)out, (hipStream_t)stream));
-    return 0;
-}
-
-// ---- still-image display tail (run_image.py:185-195, 323-343, 350-358) and the viewer's edge alpha (run_3dviewer.py:455-505, 576-593)
-static int check_batch_hw(int32_t B, int32_t H, int32_t W) {
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0) return fail(MDPT_E_INVALID, "bad size %dx%dx%d", B, H, W);
-    return 0;
-}
-
-int mdpt_post_display_prep(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t in_h, int32_t in_w, void* out_bhw, int32_t out_h, int32_t out_w,
-                           void* parts, void* hist_clear, void* stream) {
-    if (!in_bhw || !out_bhw || !parts) return fail(MDPT_E_INVALID, "null argument");
-    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
-    CHK(check_batch_hw(B, in_h, in_w));
-    CHK(check_batch_hw(B, out_h, out_w));
-    CHK(mdpt_launch_post_display_prep(in_bhw, in_dtype, B, in_h, in_w, out_bhw, out_h, out_w, (unsigned*)parts, (unsigned*)hist_clear, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_plane_fit(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* sample_xy, int32_t num_samples,
-                        int32_t xy_per_image, void* coef_out, void* stream) {
-    if (!in_bhw || !sample_xy || !coef_out) return fail(MDPT_E_INVALID, "null argument");
-    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
-    CHK(check_batch_hw(B, H, W));
-    if (num_samples <= 0) return fail(MDPT_E_INVALID, "bad sample count %d", num_samples);
-    CHK(mdpt_launch_post_plane_fit(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const int*)sample_xy, num_samples,
-                                   xy_per_image ? (size_t)num_samples * 2 : 0, (double*)coef_out, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_plane_eval(const void* coef, int32_t B, int32_t H, int32_t W, void* out_f32, void* stream) {
-    if (!coef || !out_f32) return fail(MDPT_E_INVALID, "null argument");
-    CHK(check_batch_hw(B, H, W));
-    CHK(mdpt_launch_post_plane_eval((const double*)coef, B, H, W, (float*)out_f32, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_plane_minmax(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* coef, double factor,
-                           void* vparts, void* stream) {
-    if (!in_bhw || !parts || !coef || !vparts) return fail(MDPT_E_INVALID, "null argument");
-    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
-    CHK(check_batch_hw(B, H, W));
-    CHK(mdpt_launch_post_plane_minmax(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const double*)coef, factor, (double*)vparts, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_threshold(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* coef, double factor,
-                        const void* vparts, double thresh_min, double thresh_max, int32_t mode, int32_t reverse, void* out, void* hist, void* stream) {
-    if (!in_bhw || !parts || !coef || !vparts || !out) return fail(MDPT_E_INVALID, "null argument");
-    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
-    CHK(check_batch_hw(B, H, W));
-    if (mode != MDPT_POST_F32 && mode != MDPT_POST_U8) return fail(MDPT_E_INVALID, "threshold mode must be MDPT_POST_F32 or MDPT_POST_U8, got %d", mode);
-    if (mode == MDPT_POST_U8 && reverse) return fail(MDPT_E_INVALID, "the uint8 threshold pass does not reverse (255 - x follows the equalization)");
-    if (!(thresh_min <= thresh_max)) return fail(MDPT_E_INVALID, "threshold out of order: [%g, %g]", thresh_min, thresh_max);
-    const double delta = thresh_max - thresh_min > 0.001 ? thresh_max - thresh_min : 0.001;  // run_image.py:329
-    CHK(mdpt_launch_post_threshold(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const double*)coef, factor, (const double*)vparts, thresh_min, delta,
-                                   mode, reverse != 0, out, mode == MDPT_POST_U8 ? (unsigned*)hist : nullptr, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_edge_mag(const void* in_bhw_f32, int32_t B, int32_t H, int32_t W, const void* parts, const float* blur_weights, int32_t blur_ksize,
-                       void* mag_f32, void* mag_max, void* stream) {
-    if (!in_bhw_f32 || !blur_weights || !mag_f32 || !mag_max) return fail(MDPT_E_INVALID, "null argument");
-    CHK(check_batch_hw(B, H, W));
-    if (blur_ksize < 1 || blur_ksize > 15 || blur_ksize % 2 == 0) return fail(MDPT_E_INVALID, "blur kernel size must be odd, 1..15, got %d", blur_ksize);
-    const int pad = blur_ksize / 2, min_side = pad + 1 > 2 ? pad + 1 : 2;  // reflect padding needs pad < side (blur pad, Sobel pad 1)
-    if (H < min_side || W < min_side) return fail(MDPT_E_INVALID, "map %dx%d is too small for reflect padding (sides of at least %d)", H, W, min_side);
-    CHK(mdpt_launch_post_edge_mag((const float*)in_bhw_f32, B, H, W, (const unsigned*)parts, blur_weights, blur_ksize, (float*)mag_f32, (unsigned*)mag_max,
-                                  (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_edge_mask(const void* mag_f32, const void* mag_max, int32_t B, size_t count, void* out_u8, void* stream) {
-    if (!mag_f32 || !mag_max || !out_u8 || count == 0) return fail(MDPT_E_INVALID, "null argument / empty input");
-    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
-    CHK(mdpt_launch_post_edge_mask((const float*)mag_f32, (const unsigned*)mag_max, B, count, (unsigned char*)out_u8, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_pack_u24_alpha(const void* in_bhw_f32, int32_t B, size_t count, const void* parts, int32_t lossy, const void* mag_f32, const void* mag_max,
-                             const void* mask_u8, int32_t mask_per_image, void* out_bgra, void* stream) {
-    if (!in_bhw_f32 || !out_bgra || count == 0 || (mag_f32 && !mag_max)) return fail(MDPT_E_INVALID, "null argument / empty input");
-    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
-    if (mag_f32 && mask_u8) return fail(MDPT_E_INVALID, "alpha is either the edge mask or the caller's mask");
-    CHK(mdpt_launch_post_pack_u24((const float*)in_bhw_f32, B, count, (const unsigned*)parts, lossy != 0, (const float*)mag_f32, (const unsigned*)mag_max,
-                                  (const unsigned char*)mask_u8, mask_per_image ? count : 0, (unsigned char*)out_bgra, (hipStream_t)stream));
-    return 0;
-}
-
-// ---- the same for images of different sizes: one run per image, MDPT_POST_RUNS images per launch; per-image buffers advance by the images before
-static int check_images(const void* const* in, const int32_t* hw, int32_t B, const char* what) {
-    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
-    for (int i = 0; i < B; ++i) {
-        if (in && !in[i]) return fail(MDPT_E_INVALID, "null argument (%s %d)", what, i);
-        if (hw[2 * i] <= 0 || hw[2 * i + 1] <= 0) return fail(MDPT_E_INVALID, "bad %s size %dx%d (image %d)", what, hw[2 * i], hw[2 * i + 1], i);
-    }
-    return 0;
-}
-
-int mdpt_post_minmax_images(const void* const* in, const int32_t* in_hw, int32_t in_dtype, int32_t B, void* out_f32, const int32_t* out_hw, void* parts,
-                            void* hist_clear, void* stream) {
-    if (!in || !in_hw || !parts || (out_f32 && !out_hw)) return fail(MDPT_E_INVALID, "null argument");
-    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
-    CHK(check_images(in, in_hw, B, "input"));
-    if (out_f32) CHK(check_images(nullptr, out_hw, B, "output"));
-    const int32_t* ohw = out_f32 ? out_hw : in_hw;
-    size_t off = 0;
-    for (int b0 = 0; b0 < B; b0 += MDPT_POST_RUNS) {
-        PostRunTable t{};
-        t.n = B - b0 < MDPT_POST_RUNS ? B - b0 : MDPT_POST_RUNS;
-        for (int r = 0; r < t.n; ++r) {
-            const int i = b0 + r;
-            t.run[r] = PostRun{in[i], off, in_hw[2 * i], in_hw[2 * i + 1], ohw[2 * i], ohw[2 * i + 1], 1};
-            off += (size_t)ohw[2 * i] * ohw[2 * i + 1];
-        }
-        CHK(mdpt_launch_post_seg_minmax(t, in_dtype, (float*)out_f32, (unsigned*)parts + (size_t)b0 * MDPT_POST_SEG_PARTS * 2,
-                                        hist_clear ? (unsigned*)hist_clear + (size_t)b0 * 256 : nullptr, (hipStream_t)stream));
-    }
-    return 0;
-}
-
-int mdpt_post_u8_hist_images(const void* const* in, const int32_t* hw, int32_t in_dtype, int32_t B, const void* parts, int32_t reverse, void* out_u8,
-                             void* hist, void* stream) {
-    if (!in || !hw || !parts || !out_u8) return fail(MDPT_E_INVALID, "null argument");
-    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
-    CHK(check_images(in, hw, B, "input"));
-    size_t off = 0;
-    for (int b0 = 0; b0 < B; b0 += MDPT_POST_RUNS) {
-        PostRunTable t{};
-        t.n = B - b0 < MDPT_POST_RUNS ? B - b0 : MDPT_POST_RUNS;
-        for (int r = 0; r < t.n; ++r) {
-            const int i = b0 + r;
-            t.run[r] = PostRun{in[i], off, hw[2 * i], hw[2 * i + 1], hw[2 * i], hw[2 * i + 1], 1};
-            off += (size_t)hw[2 * i] * hw[2 * i + 1];
-        }
-        CHK(mdpt_launch_post_seg_u8(t, in_dtype, (const unsigned*)parts + (size_t)b0 * MDPT_POST_SEG_PARTS * 2, reverse != 0, (unsigned char*)out_u8,
-                                    hist ? (unsigned*)hist + (size_t)b0 * 256 : nullptr, (hipStream_t)stream));
-    }
-    return 0;
-}
-
-int mdpt_post_colorize_images(const void* in_u8, const int32_t* hw, int32_t B, const void* eq_lut, const void* cmap_bgr, int32_t channels, void* out,
-                              void* stream) {
-    if (!in_u8 || !hw || !out) return fail(MDPT_E_INVALID, "null argument");
-    if (channels != 1 && channels != 3) return fail(MDPT_E_INVALID, "channels must be 1 or 3, got %d", channels);
-    CHK(check_images(nullptr, hw, B, "input"));
-    size_t off = 0;
-    for (int b0 = 0; b0 < B; b0 += MDPT_POST_RUNS) {
-        PostRunTable t{};
-        t.n = B - b0 < MDPT_POST_RUNS ? B - b0 : MDPT_POST_RUNS;
-        for (int r = 0; r < t.n; ++r) {
-            const int i = b0 + r;
-            t.run[r] = PostRun{(const unsigned char*)in_u8 + off, off, hw[2 * i], hw[2 * i + 1], hw[2 * i], hw[2 * i + 1], 1};
-            off += (size_t)hw[2 * i] * hw[2 * i + 1];
-        }
-        CHK(mdpt_launch_post_colorize(t, eq_lut ? (const unsigned char*)eq_lut + (size_t)b0 * 256 : nullptr, (const unsigned char*)cmap_bgr, channels,
-                                      (unsigned char*)out, (hipStream_t)stream));
-    }
-    return 0;
-}
-
-// ---- depth masking (experiments/depth_masking.py:189-199, 314-332 display; :341-361 save)
-static int check_mask_window(double thresh_min, double thresh_max) {
-    if (!(0.0 <= thresh_min && thresh_min <= thresh_max && thresh_max <= 1.0))
-        return fail(MDPT_E_INVALID, "threshold must be (min, max) with 0 <= min <= max <= 1, got [%g, %g]", thresh_min, thresh_max);
-    return 0;
-}
-
-int mdpt_post_mask_display(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* coef, double factor,
-                           const void* vparts, double thresh_min, double thresh_max, int32_t invert, const void* images_bgr, int32_t image_h, int32_t image_w,
-                           void* mask_out, void* composite_out, void* stream) {
-    if (!in_bhw || !parts || !coef || !vparts || !images_bgr || !mask_out || !composite_out) return fail(MDPT_E_INVALID, "null argument");
-    if (!post_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
-    CHK(check_batch_hw(B, H, W));
-    CHK(check_batch_hw(B, image_h, image_w));
-    CHK(check_mask_window(thresh_min, thresh_max));
-    CHK(mdpt_launch_post_mask_display(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const double*)coef, factor, (const double*)vparts, thresh_min,
-                                      thresh_max, invert != 0, (const unsigned char*)images_bgr, image_h, image_w, (unsigned char*)mask_out,
-                                      (unsigned char*)composite_out, (hipStream_t)stream));
-    return 0;
-}
-
-int mdpt_post_mask_cutout_images(const void* const* maps, const int32_t* map_hw, int32_t map_dtype, const void* const* parts, const void* const* coef,
-                                 const void* const* vparts, double factor, const void* const* images, const int32_t* image_hw, const int64_t* out_offsets,
-                                 int32_t B, double thresh_min, double thresh_max, int32_t invert, void* out_bgra, void* out_mask, void* stream) {
-    if (!maps || !map_hw || !parts || !coef || !vparts || !images || !image_hw || !out_offsets || !out_bgra || !out_mask)
-        return fail(MDPT_E_INVALID, "null argument");
-    if (((uintptr_t)out_bgra & 3) != 0) return fail(MDPT_E_INVALID, "the BGRA output must be 4-byte aligned");
-    if (!post_dtype_ok(map_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", map_dtype);
-    CHK(check_mask_window(thresh_min, thresh_max));
-    CHK(check_images(maps, map_hw, B, "map"));
-    CHK(check_images(images, image_hw, B, "image"));
-    for (int k = 0; k < B; ++k) {
-        if (!parts[k] || !coef[k] || !vparts[k]) return fail(MDPT_E_INVALID, "null argument (statistics of image %d)", k);
-        if (out_offsets[k] < 0) return fail(MDPT_E_INVALID, "bad output offset %lld (image %d)", (long long)out_offsets[k], k);
-    }
-    for (int b0 = 0; b0 < B; b0 += MDPT_MASK_IMAGES) {
-        MaskTable t{};
-        t.n = B - b0 < MDPT_MASK_IMAGES ? B - b0 : MDPT_MASK_IMAGES;
-        t.dt = map_dtype;
-        for (int r = 0; r < t.n; ++r) {
-            const int k = b0 + r;
-            t.im[r] = MaskImage{maps[k], (const unsigned*)parts[k], (const double*)coef[k], (const double*)vparts[k], (const unsigned char*)images[k],
-                                (size_t)out_offsets[k], map_hw[2 * k], map_hw[2 * k + 1], image_hw[2 * k], image_hw[2 * k + 1]};
-        }
-        CHK(mdpt_launch_post_mask_cutout(t, factor, thresh_min, thresh_max, invert != 0, (unsigned char*)out_bgra, (unsigned char*)out_mask,
-                                         (hipStream_t)stream));
-    }
-    return 0;
-}
-
-// ---- block norm tiles (experiments/block_norm_visualization.py:137-147, 207-233)
-int mdpt_post_block_norm_tiles(const void* const* maps, const int32_t* map_hw, int32_t L, int32_t B, int32_t H, int32_t W, void* tiles_u8, void* minmax_f32,
-                               void* stream) {
-    if (!maps || !map_hw || !tiles_u8 || !minmax_f32) return fail(MDPT_E_INVALID, "null argument");
-    CHK(check_batch_hw(B, H, W));
-    if (L <= 0 || (size_t)H * W > ((size_t)1 << 24)) return fail(MDPT_E_INVALID, "bad map count %d / tile size %dx%d", L, H, W);
-    CHK(check_images(maps, map_hw, L, "map"));
-    for (int l = 0; l < L; ++l)
-        if (H % map_hw[2 * l] || W % map_hw[2 * l + 1])
-            return fail(MDPT_E_INVALID, "map %d (%dx%d) does not divide the tile size %dx%d", l, map_hw[2 * l], map_hw[2 * l + 1], H, W);
-    const int per_launch = 65535 / B < MDPT_POST_RUNS ? 65535 / B : MDPT_POST_RUNS;  // (maps per launch: a launch holds at most 65535 images)
-    for (int l0 = 0; l0 < L; l0 += per_launch) {
-        PostRunTable t{};
-        t.n = L - l0 < per_launch ? L - l0 : per_launch;
-        for (int r = 0; r < t.n; ++r)
-            t.run[r] = PostRun{maps[l0 + r], (size_t)(l0 + r) * B * H * W, map_hw[2 * (l0 + r)], map_hw[2 * (l0 + r) + 1], H, W, B};
-        CHK(mdpt_launch_post_block_norm_tiles(t, (unsigned char*)tiles_u8, (float*)minmax_f32 + (size_t)l0 * B * 2, (hipStream_t)stream));
-    }
     return 0;
 }
 

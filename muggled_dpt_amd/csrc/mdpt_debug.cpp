@@ -239,7 +239,7 @@ int mdpt_allgather(void* comm, const void* send_dev, void* recv_dev, size_t coun
         if (!fn) return fail(MDPT_E_STATE, "ncclAllGather not found in librccl.so");
     }
     // ncclDataType_t: ncclFloat16 = 6, ncclFloat32 = 7, ncclBfloat16 = 9 (rccl.h)
-    if (dtype != MDPT_DTYPE_F32 && dtype != MDPT_DTYPE_BF16 && dtype != MDPT_DTYPE_F16) return fail(MDPT_E_INVALID, "bad dtype %d", dtype);
+    if (!tensor_dtype_ok(dtype)) return fail(MDPT_E_INVALID, "bad dtype %d", dtype);
     const int nccl_type = dtype == MDPT_DTYPE_F32 ? 7 : (dtype == MDPT_DTYPE_BF16 ? 9 : 6);
     const int rc = fn(send_dev, recv_dev, count_per_rank, nccl_type, comm, stream);
     if (rc != 0) return fail(MDPT_E_STATE, "ncclAllGather failed with code %d", rc);

@@ -1,7 +1,8 @@
 // libmdpt internals shared by the host-side translation units (not part of the C ABI, which is include/mdpt.h):
 //   mdpt_inventory.cpp  parameter inventory (reference key names), packed-weight layout, activation workspace plan
 //   mdpt_stages.cpp     launch sequences of the five stages (patch embed, encoder, reassemble, fusion, head) for all families
-//   mdpt_api.cpp        the C entry points
+//   mdpt_api.cpp        the C entry points of the model: handle lifecycle, forward, stage entry points, probes
+//   mdpt_post.cpp       the depth post-processing entry points (mdpt_post_*: no handle, no plan, no workspace)
 //   mdpt_debug.cpp      test / measurement hooks and the RCCL wrapper
 //
 // libmdpt: C ABI (include/mdpt.h) + host-side orchestration of the DPT forward path on one MI355X.
@@ -64,6 +65,10 @@ int fail(int code, const char* fmt, ...);  // records the message for mdpt_last_
             return e_;                                                                                              \
         }                                                                                                           \
     } while (0)
+
+// argument checks shared by the entry points (the caller reports: "bad tensor dtype %d" / the resize's message, mdpt_api.cpp check_interp)
+inline bool tensor_dtype_ok(int dt) { return dt == MDPT_DTYPE_F32 || dt == MDPT_DTYPE_BF16 || dt == MDPT_DTYPE_F16; }
+inline bool interp_ok(int interp) { return interp == MDPT_INTERP_BILINEAR || interp == MDPT_INTERP_BICUBIC; }
 
 inline int rup(int v, int m) { return (v + m - 1) / m * m; }
 inline size_t rup256(size_t v) { return (v + 255) & ~(size_t)255; }

@@ -23,9 +23,14 @@ from torch import Tensor
 from . import native
 
 
+def _need_cuda(tensors, what: str, expected: str = "expected a CUDA tensor") -> None:
+    """There is no CPU implementation: anything among `tensors` that is not a CUDA tensor raises."""
+    if not all(isinstance(t, torch.Tensor) and t.device.type == "cuda" for t in tensors):
+        raise RuntimeError(f"{what}: {expected} (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+
+
 def _dev_f32(t, what: str) -> Tensor:
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise RuntimeError(f"{what}: expected a CUDA tensor (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+    _need_cuda([t], what)
     return t.detach().to(torch.float32).contiguous()
 
 
@@ -114,8 +119,7 @@ def remove_inf_tensor(data: Tensor, inf_replacement_value: float = 0.0, in_place
 
 
 def _dev_u8(t, what: str) -> Tensor:
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise RuntimeError(f"{what}: expected a CUDA tensor (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+    _need_cuda([t], what)
     if t.dtype != torch.uint8 or t.dim() not in (2, 3) or t.numel() == 0:
         raise TypeError(f"{what}: expected a uint8 HxW or BxHxW tensor, got {t.dtype} {tuple(t.shape)}")
     return t.detach().contiguous()
@@ -201,16 +205,7 @@ def depth_to_color(prediction: Tensor, target_wh: tuple[int, int] | None = None,
     scale_prediction (target_wh given) -> convert_to_uint8 -> 255 - x (reverse) -> histogram_equalization (high_contrast) -> colormap (lut; gray
     when None). Image b's frame equals that composition on prediction[b:b+1] bit for bit (its own min / max and histogram). Four launches at
     most: resize + per-image min/max (also clears the histogram), uint8 + histogram, LUT, equalize-and-colormap as one lookup."""
-    if not isinstance(prediction, torch.Tensor) or prediction.device.type != "cuda":
-        raise RuntimeError("depth_to_color: expected a CUDA tensor (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
-    x = prediction.detach()
-    if x.dim() == 2:
-        x = x[None]
-    if x.dim() != 3 or x.numel() == 0:
-        raise RuntimeError(f"depth_to_color expects BxHxW, got {tuple(prediction.shape)}")
-    if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        x = x.to(torch.float32)
-    x = x.contiguous()
+    x = _batch_maps(prediction, "depth_to_color")
     dev = x.device
     cmap = _cmap_tensor(lut, dev)
     b, h, w = x.shape
@@ -261,8 +256,7 @@ def _prediction_list(predictions, what: str) -> list[Tensor]:
         raise TypeError(f"{what} expects a list of depth tensors or a BxHxW tensor, got {type(predictions)}")
     if not maps:
         raise ValueError(f"{what} got no predictions")
-    if any(m.device.type != "cuda" for m in maps):
-        raise RuntimeError(f"{what}: expected CUDA tensors (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+    _need_cuda(maps, what, "expected CUDA tensors")
     if len({m.device for m in maps}) != 1 or len({m.dtype for m in maps}) != 1:
         raise RuntimeError(f"{what}: all predictions must share one device and one dtype")
     if any(m.numel() == 0 for m in maps):
@@ -408,8 +402,7 @@ def _sample_table(sample_xy, b: int, h: int, w: int, samples_per_side: int, jitt
 
 def _batch_maps(prediction, what: str) -> Tensor:
     """a [B,h,w] (or [h,w]) CUDA depth tensor -> contiguous [B,h,w] in fp32 / bf16 / fp16"""
-    if not isinstance(prediction, torch.Tensor) or prediction.device.type != "cuda":
-        raise RuntimeError(f"{what}: expected a CUDA tensor (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+    _need_cuda([prediction], what)
     x = prediction.detach()
     if x.dim() == 2:
         x = x[None]
@@ -609,8 +602,7 @@ def pack_depth_u24_frames(predictions: Tensor, is_metric: bool = False, lossy: b
 
 def _display_photos(images_bgr, b: int, what: str) -> Tensor:
     """uint8 [B,ih,iw,3] (or [ih,iw,3] for one map) CUDA photos of the display batch"""
-    if not isinstance(images_bgr, torch.Tensor) or images_bgr.device.type != "cuda":
-        raise RuntimeError(f"{what}: images_bgr must be a uint8 CUDA tensor (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+    _need_cuda([images_bgr], what, "images_bgr must be a uint8 CUDA tensor")
     x = images_bgr.detach()
     if x.dim() == 3:
         x = x[None]
@@ -837,8 +829,7 @@ def block_norm_display(maps, max_token_hw=None, lut=None):
     for l, (h, w) in enumerate(hws):
         if th % h or tw % w:
             raise ValueError(f"{what}: map {l} is {h}x{w}, which does not divide the {th}x{tw} tile by whole factors")
-    if any(m.device.type != "cuda" for m in ms):
-        raise RuntimeError(f"{what}: expected CUDA tensors (muggled_dpt_amd post-processing runs on the MI355X only, no CPU fallback)")
+    _need_cuda(ms, what, "expected CUDA tensors")
     if len({m.device for m in ms}) != 1:
         raise RuntimeError(f"{what}: the maps are on different devices")
     ms = [m.detach().to(torch.float32).contiguous() for m in ms]
