@@ -3,6 +3,7 @@
 // conversion. All are coalesced 8/16-byte-per-lane streaming kernels; none reshapes work into a GEMM.
 
 #include "mdpt_kernels.h"
+#include "dt_io.h"
 #include "up_bf16.h"
 #include "mdpt_prof.h"
 #include "ln_row.h"
@@ -88,13 +89,6 @@ __global__ __launch_bounds__(256) void ksplit_finish_kernel(const float* __restr
 // patchify: NCHW fp32 -> rows [B*Np][Kp] with k = c*P*P + ky*P + kx (the conv weight's own flatten
 // order, patch_embed.py:56-62,92), zero padded to Kp. One thread = 4 consecutive k.
 // ---------------------------------------------------------------------------------------------------
-// one element of a tensor that crosses the C ABI in the caller's dtype (MDPT_DT_*): images, raw weights
-__device__ __forceinline__ float ld_typed(const void* p, size_t i, int dt) {
-    if (dt == MDPT_DT_BF16) return (float)((const __bf16*)p)[i];
-    if (dt == MDPT_DT_F16) return (float)((const _Float16*)p)[i];
-    return ((const float*)p)[i];
-}
-
 // `poison` (mdpt_forward, may be null): word b is set when image b holds a NaN / inf - the reference's forward turns such an image's whole depth
 // map into NaN (the value reaches every token through the attention), while here the saturating fp16 converts and the v_max ReLUs would hide it;
 // poison_depth_kernel below writes the NaN map at the end of the forward.
@@ -118,7 +112,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(const void* __restrict__ 
             if (k < K) {
                 const int c = k / (P * P), rem = k - c * P * P;
                 const int ky = rem / P, kx = rem - ky * P;
-                val = ld_typed(img, (((size_t)b * 3 + c) * H + (py * P + ky)) * W + (px * P + kx), img_dt);
+                val = ld_dt(img, (((size_t)b * 3 + c) * H + (py * P + ky)) * W + (px * P + kx), img_dt);
             }
             v[e] = val;
         }
@@ -138,12 +132,7 @@ __global__ __launch_bounds__(256) void poison_depth_kernel(void* __restrict__ de
     const int b = blockIdx.y;
     if (!poison[b]) return;
     const float qnan = __uint_as_float(0x7FC00000u);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t o = (size_t)b * hw + i;
-        if (dt == MDPT_DT_BF16) ((__bf16*)depth)[o] = (__bf16)qnan;
-        else if (dt == MDPT_DT_F16) ((_Float16*)depth)[o] = (_Float16)qnan;
-        else ((float*)depth)[o] = qnan;
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += (size_t)gridDim.x * blockDim.x) st_dt(depth, (size_t)b * hw + i, qnan, dt);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -349,8 +338,8 @@ __global__ __launch_bounds__(1024) void weight_scale_kernel(const void* __restri
     const size_t total = (size_t)N * K;
     for (size_t idx = threadIdx.x; idx < total; idx += 1024) {
         const int n = (int)(idx / K), k = (int)(idx - (size_t)n * K);
-        float v = ld_typed(src, (size_t)n * src_ld + src_col0 + k, sdt);
-        if (row_scale) v *= ld_typed(row_scale, n, rdt);
+        float v = ld_dt(src, (size_t)n * src_ld + src_col0 + k, sdt);
+        if (row_scale) v *= ld_dt(row_scale, n, rdt);
         v = fabsf(v);
         if (v == v && v <= 3.0e38f) mx = fmaxf(mx, v);  // (NaN / inf entries do not steer the scale: they propagate as they are)
     }
@@ -376,20 +365,20 @@ __device__ __forceinline__ float pack_value(const void* __restrict__ src, int sd
                                             int src_col0, const void* __restrict__ row_scale, int rdt, const float* __restrict__ wscale) {
     float v = 0.0f;
     if (kind == MDPT_PACK_LINEAR) {
-        if (nrow < N && kcol < K) v = ld_typed(src, (size_t)nrow * src_ld + src_col0 + kcol, sdt);
-        if (row_scale && nrow < N) v *= ld_typed(row_scale, nrow, rdt);
+        if (nrow < N && kcol < K) v = ld_dt(src, (size_t)nrow * src_ld + src_col0 + kcol, sdt);
+        if (row_scale && nrow < N) v *= ld_dt(row_scale, nrow, rdt);
         if (wscale) v *= wscale[0];  // power of two: exact (weight_scale_kernel)
     } else if (kind == MDPT_PACK_CONV3) {
         // src [N=Cout][K=Cin][3][3]; Kp = 9*Cinp (Cinp % CB == 0); kcol = (cb * 9 + tap) * CB + c with ci = cb * CB + c: the nine taps of
         // a channel block are consecutive K tiles (the halo-staged conv kernel stages a block's input patch once for all of them)
         const int blk = kcol / (9 * CB), rem = kcol - blk * (9 * CB);
         const int tap = rem / CB, ci = blk * CB + (rem - tap * CB);
-        if (nrow < N && ci < K) v = ld_typed(src, ((size_t)nrow * K + ci) * 9 + tap, sdt);
+        if (nrow < N && ci < K) v = ld_dt(src, ((size_t)nrow * K + ci) * 9 + tap, sdt);
     } else {
         // ConvTranspose2d weight [Cin=K][Cout=N][ksz][ksz]; rows = (ky*ksz+kx)*Coutp + co with Np = ksz*ksz*Coutp
         const int coutp = Np / (ksz * ksz);
         const int kidx = nrow / coutp, co = nrow - kidx * coutp;
-        if (co < N && kcol < K) v = ld_typed(src, ((size_t)kcol * N + co) * (ksz * ksz) + kidx, sdt);
+        if (co < N && kcol < K) v = ld_dt(src, ((size_t)kcol * N + co) * (ksz * ksz) + kidx, sdt);
     }
     return v;
 }
@@ -407,7 +396,7 @@ __global__ __launch_bounds__(256) void pack_weight_kernel(const void* __restrict
             const int el = (int)(idx & 7), n = (int)((idx >> 3) & 31), chunk = (int)(idx >> 8);
             const int cinp = Kp / 9, k = chunk * 8 + el;
             const int tap = k / cinp, ci = k - tap * cinp;
-            if (n < N && ci < K) v = ld_typed(src, ((size_t)n * K + ci) * 9 + tap, sdt);
+            if (n < N && ci < K) v = ld_dt(src, ((size_t)n * K + ci) * 9 + tap, sdt);
         } else {
             v = pack_value<64>(src, sdt, kind, nrow, kcol, N, K, Np, ksz, src_ld, src_col0, row_scale, rdt, wscale);
         }
@@ -474,7 +463,7 @@ __global__ __launch_bounds__(256) void pack_weight_f8_kernel(const void* __restr
 __global__ __launch_bounds__(256) void pad_copy_kernel(const void* __restrict__ src, int sdt, float* dst, int n, int np, const void* __restrict__ scale, int cdt, float mul) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < np) {
-        float v = i < n ? (scale ? ld_typed(src, i, sdt) * ld_typed(scale, i, cdt) : ld_typed(src, i, sdt)) : 0.0f;
+        float v = i < n ? (scale ? ld_dt(src, i, sdt) * ld_dt(scale, i, cdt) : ld_dt(src, i, sdt)) : 0.0f;
         if (mul != 1.0f) v *= mul;
         dst[i] = v;
     }

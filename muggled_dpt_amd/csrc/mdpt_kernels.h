@@ -193,6 +193,19 @@ struct BgrRunTable { BgrRun run[MDPT_BGR_RUNS]; int n; };
 struct PostRun { const void* in; size_t off; int ih, iw, oh, ow, count; };
 struct PostRunTable { PostRun run[MDPT_POST_RUNS]; int n; };
 
+// the one-run image table of a uniform batch: B images of ih x iw (-> oh x ow) packed from `in`, outputs packed from element 0
+inline PostRunTable uniform_table(const void* in, int B, int ih, int iw, int oh, int ow) {
+    PostRunTable t{};
+    t.n = 1;
+    t.run[0] = PostRun{in, 0, ih, iw, oh, ow, B};
+    return t;
+}
+
+// a prepared uniform batch of the still-image display tail with its statistics, by value: maps [B, h, w] of dtype dt from `in`, parts = [B,
+// MDPT_POST_SEG_PARTS, 2] ordered {min, max} partials, coef = [B, 4] fp64 plane {nx, ny, nz, d}, factor = the share of the plane to remove, vparts =
+// [B, MDPT_POST_SEG_PARTS, 2] fp64 {min, max} partials of the plane-removed map (null for the kernel that computes them)
+struct PlaneMap { const void* in; int dt, B, h, w; const unsigned* parts; const double* coef; double factor; const double* vparts; };
+
 // photo table of the depth-masking cutout (postprocess.hip mask_cutout_kernel), by value: photo k is img (ih x iw x 3 BGR bytes), cut out by its
 // prepared map (h x w, dtype dt of the table) with that map's min/max partials, plane coef and plane-removed min/max partials; its outputs start at
 // pixel `off` of the packed BGRA / mask outputs (blockIdx.y = photo)
@@ -224,17 +237,15 @@ int mdpt_launch_post_hist(const unsigned char* in, int B, size_t n, unsigned* hi
 int mdpt_launch_post_eq_lut(const unsigned* hist, int B, const int* bin_of, int vmin, int vmax, unsigned char* lut, hipStream_t stream);
 int mdpt_launch_post_colorize(const PostRunTable& t, const unsigned char* eq, const unsigned char* cmap, int channels, unsigned char* out,
                               hipStream_t stream);
-// still-image display tail and edge alpha (uniform batches): vparts = [B, MDPT_POST_SEG_PARTS, 2] fp64 {min, max} partials of the plane-removed
-// map, coef = [B, 4] fp64 plane {nx, ny, nz, d}, mag = [B, h, w] fp32 Sobel magnitude, mag_max = [B] fp32 bits (cleared by the edge launcher)
+// still-image display tail and edge alpha (uniform batches): PlaneMap above, mag = [B, h, w] fp32 Sobel magnitude, mag_max = [B] fp32 bits (cleared
+// by the edge launcher)
 int mdpt_launch_post_display_prep(const void* in, int dt, int B, int ih, int iw, void* out, int oh, int ow, unsigned* parts, unsigned* hist_clear,
                                   hipStream_t stream);
 int mdpt_launch_post_plane_fit(const void* in, int dt, int B, int h, int w, const unsigned* parts, const int* xy, int N, size_t xy_stride, double* coef,
                                hipStream_t stream);
 int mdpt_launch_post_plane_eval(const double* coef, int B, int h, int w, float* out, hipStream_t stream);
-int mdpt_launch_post_plane_minmax(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, double* vparts,
-                                  hipStream_t stream);
-int mdpt_launch_post_threshold(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, const double* vparts,
-                               double tmin, double delta, int mode, int reverse, void* out, unsigned* hist, hipStream_t stream);
+int mdpt_launch_post_plane_minmax(const PlaneMap& m, double* vparts, hipStream_t stream);
+int mdpt_launch_post_threshold(const PlaneMap& m, double tmin, double delta, int mode, int reverse, void* out, unsigned* hist, hipStream_t stream);
 int mdpt_launch_post_edge_mag(const float* in, int B, int h, int w, const unsigned* parts, const float* blur_w, int ksize, float* mag, unsigned* mag_max,
                               hipStream_t stream);
 int mdpt_launch_post_edge_mask(const float* mag, const unsigned* mag_max, int B, size_t n, unsigned char* out, hipStream_t stream);
@@ -242,9 +253,8 @@ int mdpt_launch_post_pack_u24(const float* in, int B, size_t n, const unsigned* 
                               const unsigned char* mask, size_t mask_stride, unsigned char* out, hipStream_t stream);
 // depth masking (experiments/depth_masking.py): the display mask + checker composite of a uniform batch (images [B, ih, iw, 3]) and the
 // per-photo cutout at each photo's own size
-int mdpt_launch_post_mask_display(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, const double* vparts,
-                                  double tmin, double tmax, int invert, const unsigned char* img, int ih, int iw, unsigned char* mask, unsigned char* comp,
-                                  hipStream_t stream);
+int mdpt_launch_post_mask_display(const PlaneMap& m, double tmin, double tmax, int invert, const unsigned char* img, int ih, int iw, unsigned char* mask,
+                                  unsigned char* comp, hipStream_t stream);
 int mdpt_launch_post_mask_cutout(const MaskTable& t, double factor, double tmin, double tmax, int invert, unsigned char* bgra, unsigned char* mask,
                                  hipStream_t stream);
 // block norm tiles (experiments/block_norm_visualization.py): run r of the table = the B = count fp32 maps [ih, iw] of one block, each normalised by

@@ -29,14 +29,6 @@ int mdpt_post_normalize(const void* in_f32, size_t count, const void* minmax, vo
 
 // ---- per-image display tail (run_video.py:348-361 per frame, over a batch; demo_helpers/postprocess.py:107-145, toadui/colormaps.py:237-259)
 
-// the one-run image table of a uniform batch: B images of ih x iw (-> oh x ow) packed from `in`, outputs packed from element 0
-static PostRunTable uniform_table(const void* in, int B, int ih, int iw, int oh, int ow) {
-    PostRunTable t{};
-    t.n = 1;
-    t.run[0] = PostRun{in, 0, ih, iw, oh, ow, B};
-    return t;
-}
-
 // a uint8 / map count as the ih x iw of one table entry (1 x count)
 static bool count_as_hw(size_t count, int& ih, int& iw) {
     if (count == 0 || count > (size_t)INT32_MAX) return false;
@@ -101,6 +93,11 @@ static int check_batch_hw(int32_t B, int32_t H, int32_t W) {
     return 0;
 }
 
+static PlaneMap plane_map(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t H, int32_t W, const void* parts, const void* coef, double factor,
+                          const void* vparts) {
+    return PlaneMap{in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const double*)coef, factor, (const double*)vparts};
+}
+
 int mdpt_post_display_prep(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t in_h, int32_t in_w, void* out_bhw, int32_t out_h, int32_t out_w,
                            void* parts, void* hist_clear, void* stream) {
     if (!in_bhw || !out_bhw || !parts) return fail(MDPT_E_INVALID, "null argument");
@@ -134,7 +131,7 @@ int mdpt_post_plane_minmax(const void* in_bhw, int32_t in_dtype, int32_t B, int3
     if (!in_bhw || !parts || !coef || !vparts) return fail(MDPT_E_INVALID, "null argument");
     if (!tensor_dtype_ok(in_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", in_dtype);
     CHK(check_batch_hw(B, H, W));
-    CHK(mdpt_launch_post_plane_minmax(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const double*)coef, factor, (double*)vparts, (hipStream_t)stream));
+    CHK(mdpt_launch_post_plane_minmax(plane_map(in_bhw, in_dtype, B, H, W, parts, coef, factor, nullptr), (double*)vparts, (hipStream_t)stream));
     return 0;
 }
 
@@ -147,8 +144,8 @@ int mdpt_post_threshold(const void* in_bhw, int32_t in_dtype, int32_t B, int32_t
     if (mode == MDPT_POST_U8 && reverse) return fail(MDPT_E_INVALID, "the uint8 threshold pass does not reverse (255 - x follows the equalization)");
     if (!(thresh_min <= thresh_max)) return fail(MDPT_E_INVALID, "threshold out of order: [%g, %g]", thresh_min, thresh_max);
     const double delta = thresh_max - thresh_min > 0.001 ? thresh_max - thresh_min : 0.001;  // run_image.py:329
-    CHK(mdpt_launch_post_threshold(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const double*)coef, factor, (const double*)vparts, thresh_min, delta,
-                                   mode, reverse != 0, out, mode == MDPT_POST_U8 ? (unsigned*)hist : nullptr, (hipStream_t)stream));
+    CHK(mdpt_launch_post_threshold(plane_map(in_bhw, in_dtype, B, H, W, parts, coef, factor, vparts), thresh_min, delta, mode, reverse != 0, out,
+                                   mode == MDPT_POST_U8 ? (unsigned*)hist : nullptr, (hipStream_t)stream));
     return 0;
 }
 
@@ -263,9 +260,9 @@ int mdpt_post_mask_display(const void* in_bhw, int32_t in_dtype, int32_t B, int3
     CHK(check_batch_hw(B, H, W));
     CHK(check_batch_hw(B, image_h, image_w));
     CHK(check_mask_window(thresh_min, thresh_max));
-    CHK(mdpt_launch_post_mask_display(in_bhw, in_dtype, B, H, W, (const unsigned*)parts, (const double*)coef, factor, (const double*)vparts, thresh_min,
-                                      thresh_max, invert != 0, (const unsigned char*)images_bgr, image_h, image_w, (unsigned char*)mask_out,
-                                      (unsigned char*)composite_out, (hipStream_t)stream));
+    CHK(mdpt_launch_post_mask_display(plane_map(in_bhw, in_dtype, B, H, W, parts, coef, factor, vparts), thresh_min, thresh_max, invert != 0,
+                                      (const unsigned char*)images_bgr, image_h, image_w, (unsigned char*)mask_out, (unsigned char*)composite_out,
+                                      (hipStream_t)stream));
     return 0;
 }
 

@@ -4,6 +4,7 @@
 // full-resolution fp32 map. min/max travel through a 2-float device buffer (no sync).
 
 #include "mdpt_kernels.h"
+#include "dt_io.h"
 #include "mdpt_prof.h"
 
 namespace {
@@ -22,26 +23,56 @@ __global__ void minmax_init_kernel(unsigned* mm) {
     mm[1] = 0u;           // running max
 }
 
-// torch's .min() / .max() PROPAGATE NaN (normalize_01 of a map with a NaN gives an all-NaN map) while fminf / fmaxf drop it: a thread
-// that saw a NaN says so, and the block then pins the running min to ordered 0 and the running max to ordered ~0, both of which
-// ord2f() maps back to NaN bit patterns.
-__device__ __forceinline__ void block_minmax(float lo, float hi, bool saw_nan, unsigned* mm) {
+// The block's (256 threads) min / max of every thread's (lo, hi), whether any thread saw a NaN and whether any holds a pixel at all: valid on
+// thread 0. T = float or double. The trailing barrier lets a kernel call it (or read what a publisher below stored in LDS) more than once.
+template <typename T>
+struct BlockMinMax { T lo, hi; bool any_nan, any_px; };
+
+template <typename T>
+__device__ __forceinline__ BlockMinMax<T> block_minmax_reduce(T lo, T hi, bool saw_nan, bool any) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, o));
-        hi = fmaxf(hi, __shfl_xor(hi, o));
+        lo = fmin(lo, __shfl_xor(lo, o));
+        hi = fmax(hi, __shfl_xor(hi, o));
     }
-    const bool wave_nan = __any(saw_nan);
-    __shared__ float slo[4], shi[4];
-    __shared__ int snan[4];
+    BlockMinMax<T> r{lo, hi, __any(saw_nan) != 0, __any(any) != 0};
+    __shared__ T slo[4], shi[4];
+    __shared__ int snan[4], sany[4];
     const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { slo[wave] = lo; shi[wave] = hi; snan[wave] = wave_nan; }
+    if ((threadIdx.x & 63) == 0) { slo[wave] = r.lo; shi[wave] = r.hi; snan[wave] = r.any_nan; sany[wave] = r.any_px; }
     __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < 4; ++w) { r.lo = fmin(r.lo, slo[w]); r.hi = fmax(r.hi, shi[w]); r.any_nan |= snan[w] != 0; r.any_px |= sany[w] != 0; }
+    __syncthreads();
+    return r;
+}
+
+// torch's .min() / .max() PROPAGATE NaN (normalize_01 of a map with a NaN gives an all-NaN map) while fminf / fmaxf drop it: a thread
+// that saw a NaN says so, and the block then pins its min to ordered 0 and its max to ordered ~0, both of which ord2f() maps back to NaN bit
+// patterns. Three publishers of the block's result: atomics on a running ordered {min, max} ...
+__device__ __forceinline__ void block_minmax(float lo, float hi, bool saw_nan, unsigned* mm) {
+    const BlockMinMax<float> r = block_minmax_reduce(lo, hi, saw_nan, true);
     if (threadIdx.x == 0) {
-        bool any_nan = wave_nan;
-        for (int w = 1; w < 4; ++w) { lo = fminf(lo, slo[w]); hi = fmaxf(hi, shi[w]); any_nan |= snan[w] != 0; }
-        atomicMin(mm + 0, any_nan ? 0u : f2ord(lo));
-        atomicMax(mm + 1, any_nan ? 0xffffffffu : f2ord(hi));
+        atomicMin(mm + 0, r.any_nan ? 0u : f2ord(r.lo));
+        atomicMax(mm + 1, r.any_nan ? 0xffffffffu : f2ord(r.hi));
+    }
+}
+
+// ... a store of the ordered {min, max} (the partials of the per-image kernels; a share without pixels is neutral) ...
+__device__ __forceinline__ void block_minmax_part(float lo, float hi, bool saw_nan, bool any, unsigned* part) {
+    const BlockMinMax<float> r = block_minmax_reduce(lo, hi, saw_nan, any);
+    if (threadIdx.x == 0) {
+        part[0] = r.any_nan ? 0u : (r.any_px ? f2ord(r.lo) : 0xffffffffu);
+        part[1] = r.any_nan ? 0xffffffffu : (r.any_px ? f2ord(r.hi) : 0u);
+    }
+}
+
+// ... and a store of the fp64 {min, max} (a NaN pins NaN, numpy's min / max propagate it; a share without pixels keeps {inf, -inf}: neutral)
+__device__ __forceinline__ void block_minmax_f64(double lo, double hi, bool saw_nan, double* part) {
+    const BlockMinMax<double> r = block_minmax_reduce(lo, hi, saw_nan, true);
+    if (threadIdx.x == 0) {
+        part[0] = r.any_nan ? NAN : r.lo;
+        part[1] = r.any_nan ? NAN : r.hi;
     }
 }
 
@@ -62,8 +93,24 @@ __global__ void minmax_finish_kernel(const unsigned* mm, float* out) {
     out[1] = ord2f(mm[1]);
 }
 
-// F.interpolate(x[:, None], size=(oh, ow), mode="bilinear") (align_corners=False, no antialias): src = max(0, s*(dst+0.5)-0.5)
-// Optionally folds the min/max reduction of the OUTPUT into the same pass (for convert_to_uint8(scale_prediction(x))).
+// F.interpolate(x[:, None], size=(oh, ow), mode="bilinear") (align_corners=False, no antialias) of image `base` (ih x iw, dtype dt) at output pixel
+// (oy, ox), sy = ih / oh, sx = iw / ow: src = max(0, s*(dst+0.5)-0.5); rounded to dt (the map scale_prediction returns).
+// scale_bilinear_kernel's arithmetic as the compiler contracts it there (its gfx950 code: fma for the source position, one fma and one
+// product per row, two products and an add across the rows), spelled out with _rn intrinsics so that no contraction choice here can differ
+__device__ __forceinline__ float bilinear_at(const void* in, size_t base, int dt, int ih, int iw, float sy, float sx, int oy, int ox) {
+    const float fy = fmaxf(__fmaf_rn(sy, (float)oy + 0.5f, -0.5f), 0.0f), fx = fmaxf(__fmaf_rn(sx, (float)ox + 0.5f, -0.5f), 0.0f);
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + (y0 < ih - 1), x1 = x0 + (x0 < iw - 1);
+    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    const float p00 = ld_dt(in, base + (size_t)y0 * iw + x0, dt), p01 = ld_dt(in, base + (size_t)y0 * iw + x1, dt);
+    const float p10 = ld_dt(in, base + (size_t)y1 * iw + x0, dt), p11 = ld_dt(in, base + (size_t)y1 * iw + x1, dt);
+    const float top = __fmaf_rn(p01, lx, __fmul_rn(p00, 1.0f - lx)), bot = __fmaf_rn(p10, 1.0f - lx, __fmul_rn(p11, lx));
+    return round_dt(__fadd_rn(__fmul_rn(1.0f - ly, top), __fmul_rn(ly, bot)), dt);
+}
+
+// scale_prediction of a uniform fp32 batch, left to the compiler's contraction (bilinear_at restates it; tests/test_gpu_display_tail.py keeps the
+// two in step). Optionally folds the min/max reduction of the OUTPUT into the same pass (for
+// convert_to_uint8(scale_prediction(x))).
 __global__ __launch_bounds__(256) void scale_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int ih, int iw,
                                                              int oh, int ow, unsigned* mm) {
     const float sy = (float)ih / (float)oh, sx = (float)iw / (float)ow;
@@ -88,8 +135,28 @@ __global__ __launch_bounds__(256) void scale_bilinear_kernel(const float* __rest
     if (mm) block_minmax(lo, hi, saw_nan, mm);
 }
 
-// mode 0: fp32 (x - min) / (max - min); mode 1: u8 = trunc(255 * norm) (Tensor.byte()); mode 2: BGRA u8 = 24-bit
-// round-half-even(16777215 * norm) split into bytes (B = low, G = mid, R = high; alpha left 0), lossy: high byte only.
+// x, or (x - lo) / range with have_range: normalize_01 in fp32
+__device__ __forceinline__ float norm01(float x, float lo, float range, bool have_range) { return have_range ? (x - lo) / range : x; }
+
+// the same for an integer output: a NaN (max == min: 0 / 0; NaN anywhere in the map) becomes 0 - converting NaN to an integer is undefined in C and
+// implementation-defined in torch's .byte(); values are clamped to the representable range before the conversion
+__device__ __forceinline__ float norm_clamp01(float x, float lo, float range, bool have_range) {
+    const float v = norm01(x, lo, range, have_range);
+    return v == v ? fminf(fmaxf(v, 0.0f), 1.0f) : 0.0f;
+}
+
+// BGRA of v in [0, 1]: the 24-bit round-half-even(16777215 v) split into bytes (B = low, G = mid, R = high; lossy: high byte only), A = alpha
+__device__ __forceinline__ uchar4 u24_px(float v, int lossy, unsigned char alpha) {
+    const int q = (int)rintf(16777215.0f * v);
+    uchar4 px;
+    px.x = lossy ? 0 : (unsigned char)(q & 255);
+    px.y = lossy ? 0 : (unsigned char)((q >> 8) & 255);
+    px.z = (unsigned char)((q >> 16) & 255);
+    px.w = alpha;
+    return px;
+}
+
+// mode 0: fp32 (x - min) / (max - min); mode 1: u8 = trunc(255 * norm) (Tensor.byte()); mode 2: BGRA u8 = u24_px(norm), alpha left 0.
 // minmax == null: the input is used as is (metric models skip normalize_01, run_3dviewer.py:577-578).
 template <int MODE>
 __global__ __launch_bounds__(256) void normalize_kernel(const float* __restrict__ in, const float* __restrict__ minmax, void* out, size_t n,
@@ -97,32 +164,17 @@ __global__ __launch_bounds__(256) void normalize_kernel(const float* __restrict_
     const float lo = minmax ? minmax[0] : 0.0f, hi = minmax ? minmax[1] : 1.0f;
     const float range = hi - lo;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float v = minmax ? (in[i] - lo) / range : in[i];
-        if (MODE == 0) {
-            ((float*)out)[i] = v;  // NaN (NaN input, or max == min) propagates like the reference's fp32 result
-            continue;
-        }
-        // integer outputs: a NaN (max == min: 0 / 0; NaN anywhere in the map) becomes 0 - converting NaN to an integer is undefined in
-        // C and implementation-defined in torch's .byte(); values are clamped to the representable range before the conversion
-        v = v == v ? fminf(fmaxf(v, 0.0f), 1.0f) : 0.0f;
-        if (MODE == 1) {
-            ((unsigned char*)out)[i] = (unsigned char)(int)(255.0f * v);
-        } else {
-            const int q = (int)rintf(16777215.0f * v);
-            uchar4 px;
-            px.x = lossy ? 0 : (unsigned char)(q & 255);
-            px.y = lossy ? 0 : (unsigned char)((q >> 8) & 255);
-            px.z = (unsigned char)((q >> 16) & 255);
-            px.w = 0;
-            ((uchar4*)out)[i] = px;
-        }
+        // (mode 0: a NaN - NaN input, or max == min - propagates like the reference's fp32 result)
+        if (MODE == 0) ((float*)out)[i] = norm01(in[i], lo, range, minmax != nullptr);
+        else if (MODE == 1) ((unsigned char*)out)[i] = (unsigned char)(int)(255.0f * norm_clamp01(in[i], lo, range, minmax != nullptr));
+        else ((uchar4*)out)[i] = u24_px(norm_clamp01(in[i], lo, range, minmax != nullptr), lossy, 0);
     }
 }
 
 // ---- per-image display tail (the per-frame loop of the reference's run_video.py:348-361 over a batch): segmented min/max, uint8 + histogram,
 // equalization LUT, colormap. Every image of the batch gets its own min/max, histogram and LUT; nothing crosses from one image to another.
 // Segmented min/max: grid (SEG_PARTS = MDPT_POST_SEG_PARTS, B); block (x, b) leaves the ordered {min, max} of its share of image b in parts[(b PARTS + x) 2 ..],
-// the next kernel reduces the PARTS entries of its image (no atomics, no buffer to clear first). A NaN pins {0, ~0} like block_minmax.
+// the next kernel reduces the PARTS entries of its image (no atomics, no buffer to clear first). A NaN pins {0, ~0} (block_minmax_part).
 // Every kernel here takes a PostRunTable (mdpt_kernels.h) by value: blockIdx.y = image b of the table, image j of run r; the uniform batch of
 // the mdpt_post_*_seg / mdpt_post_colorize entry points is one run, images of different sizes (mdpt_post_*_images) one run each.
 constexpr int SEG_PARTS = 64;
@@ -135,100 +187,11 @@ __device__ __forceinline__ const PostRun& seg_image(const PostRunTable& t, int b
     return t.run[r];
 }
 
-__device__ __forceinline__ float ld_dt(const void* p, size_t i, int dt) {
-    if (dt == MDPT_DT_BF16) return (float)((const __bf16*)p)[i];
-    if (dt == MDPT_DT_F16) return (float)((const _Float16*)p)[i];
-    return ((const float*)p)[i];
-}
-
-// the value of the map once stored in dtype dt (scale_prediction returns its map in the prediction's dtype, postprocess.py:22-29)
-__device__ __forceinline__ float round_dt(float v, int dt) {
-    if (dt == MDPT_DT_BF16) return (float)(__bf16)v;
-    if (dt == MDPT_DT_F16) return (float)(_Float16)v;
-    return v;
-}
-
-__device__ __forceinline__ void block_minmax_part(float lo, float hi, bool saw_nan, bool any, unsigned* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, o));
-        hi = fmaxf(hi, __shfl_xor(hi, o));
-    }
-    const bool wave_nan = __any(saw_nan), wave_any = __any(any);
-    __shared__ float slo[4], shi[4];
-    __shared__ int snan[4], sany[4];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { slo[wave] = lo; shi[wave] = hi; snan[wave] = wave_nan; sany[wave] = wave_any; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        bool any_nan = wave_nan, any_px = wave_any;
-        for (int w = 1; w < 4; ++w) { lo = fminf(lo, slo[w]); hi = fmaxf(hi, shi[w]); any_nan |= snan[w] != 0; any_px |= sany[w] != 0; }
-        part[0] = any_nan ? 0u : (any_px ? f2ord(lo) : 0xffffffffu);  // a share without pixels is neutral
-        part[1] = any_nan ? 0xffffffffu : (any_px ? f2ord(hi) : 0u);
-    }
-}
-
-// F.interpolate(bilinear) of image `base` (ih x iw, dtype dt) at output pixel (oy, ox), rounded to dt (the map scale_prediction returns).
-// scale_bilinear_kernel's arithmetic as the compiler contracts it there (its gfx950 code: fma for the source position, one fma and one
-// product per row, two products and an add across the rows), spelled out with _rn intrinsics so that no contraction choice here can differ
-__device__ __forceinline__ float bilinear_at(const void* in, size_t base, int dt, int ih, int iw, float sy, float sx, int oy, int ox) {
-    const float fy = fmaxf(__fmaf_rn(sy, (float)oy + 0.5f, -0.5f), 0.0f), fx = fmaxf(__fmaf_rn(sx, (float)ox + 0.5f, -0.5f), 0.0f);
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < ih - 1), x1 = x0 + (x0 < iw - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
-    const float p00 = ld_dt(in, base + (size_t)y0 * iw + x0, dt), p01 = ld_dt(in, base + (size_t)y0 * iw + x1, dt);
-    const float p10 = ld_dt(in, base + (size_t)y1 * iw + x0, dt), p11 = ld_dt(in, base + (size_t)y1 * iw + x1, dt);
-    const float top = __fmaf_rn(p01, lx, __fmul_rn(p00, 1.0f - lx)), bot = __fmaf_rn(p10, 1.0f - lx, __fmul_rn(p11, lx));
-    return round_dt(__fadd_rn(__fmul_rn(1.0f - ly, top), __fmul_rn(ly, bot)), dt);
-}
-
-// out == null: min/max of each input image. Otherwise F.interpolate(bilinear) of each image to its oh x ow (the arithmetic of scale_bilinear_kernel),
-// rounded to the input's dtype, stored as fp32 at its place of the packed out, min/max of that. hist_clear != null: zero the [B,256] histogram the
-// next kernel accumulates into.
-__global__ __launch_bounds__(256) void seg_scale_minmax_kernel(const PostRunTable t, int in_dt, float* __restrict__ out, unsigned* __restrict__ parts,
-                                                               unsigned* __restrict__ hist_clear) {
-    const int b = blockIdx.y;
-    if (hist_clear && blockIdx.x == 0) hist_clear[(size_t)b * 256 + threadIdx.x] = 0u;
-    int j;
-    const PostRun& img = seg_image(t, b, j);
-    const void* in = img.in;
-    const int ih = img.ih, iw = img.iw, oh = img.oh, ow = img.ow;
-    const bool scale = out != nullptr;
-    const size_t n = scale ? (size_t)oh * ow : (size_t)ih * iw;
-    const size_t in_base = (size_t)j * ih * iw, out_base = img.off + (size_t)j * oh * ow;
-    const float sy = (float)ih / (float)oh, sx = (float)iw / (float)ow;
-    float lo = INFINITY, hi = -INFINITY;
-    bool saw_nan = false, any = false;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float v;
-        if (scale) {
-            v = bilinear_at(in, in_base, in_dt, ih, iw, sy, sx, (int)(i / ow), (int)(i % ow));
-            out[out_base + i] = v;
-        } else {
-            v = ld_dt(in, in_base + i, in_dt);
-        }
-        any = true;
-        saw_nan |= v != v;
-        lo = fminf(lo, v);
-        hi = fmaxf(hi, v);
-    }
-    block_minmax_part(lo, hi, saw_nan, any, parts + ((size_t)b * SEG_PARTS + blockIdx.x) * 2);
-}
-
-// (255 * normalize_01(image b)).byte() with image b's own min/max (normalize_kernel<1>'s arithmetic), optionally 255 - x, and (hist != null) image
-// b's 256-bin histogram of the result: LDS-private bins, one integer atomic per non-empty bin and block into hist[b, :]. Image b has ih x iw
-// elements; its result goes to its place of the packed out.
-__global__ __launch_bounds__(256) void seg_u8_hist_kernel(const PostRunTable t, int in_dt, const unsigned* __restrict__ parts, int reverse,
-                                                          unsigned char* __restrict__ out, unsigned* __restrict__ hist) {
-    const int b = blockIdx.y;
-    int j;
-    const PostRun& img = seg_image(t, b, j);
-    const void* in = img.in;
-    const size_t n = (size_t)img.ih * img.iw;
-    __shared__ unsigned bins[256];
+// image b's {min, max} from its SEG_PARTS partials; a block-wide call (its barrier also publishes what the caller wrote to LDS before), every
+// thread gets the pair
+__device__ __forceinline__ void seg_range(const unsigned* __restrict__ parts, int b, float& lo, float& hi) {
     __shared__ unsigned smm[2];
-    bins[threadIdx.x] = 0u;
-    if (threadIdx.x < 64) {
+    if (threadIdx.x < SEG_PARTS) {
         unsigned mn = parts[((size_t)b * SEG_PARTS + threadIdx.x) * 2], mx = parts[((size_t)b * SEG_PARTS + threadIdx.x) * 2 + 1];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -238,20 +201,94 @@ __global__ __launch_bounds__(256) void seg_u8_hist_kernel(const PostRunTable t, 
         if (threadIdx.x == 0) { smm[0] = mn; smm[1] = mx; }
     }
     __syncthreads();
-    const float lo = ord2f(smm[0]), hi = ord2f(smm[1]);
+    lo = ord2f(smm[0]);
+    hi = ord2f(smm[1]);
+}
+
+// image b's fp64 {min, max - min} of its plane-removed values from its SEG_PARTS vparts (plane_minmax_kernel; a NaN partial pins NaN; one lane
+// per partial); block-wide like seg_range
+__device__ __forceinline__ void seg_vrange(const double* __restrict__ vparts, int b, double& vlo, double& vrange) {
+    __shared__ double svr[2];
+    if (threadIdx.x < SEG_PARTS) {
+        double a = vparts[((size_t)b * SEG_PARTS + threadIdx.x) * 2], z = vparts[((size_t)b * SEG_PARTS + threadIdx.x) * 2 + 1];
+        const bool any_nan = __any(a != a || z != z);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            a = fmin(a, __shfl_xor(a, o));
+            z = fmax(z, __shfl_xor(z, o));
+        }
+        if (threadIdx.x == 0) {
+            svr[0] = any_nan ? NAN : a;
+            svr[1] = any_nan ? NAN : z;
+        }
+    }
+    __syncthreads();
+    vlo = svr[0];
+    vrange = svr[1] - svr[0];
+}
+
+// the block's LDS-private 256-bin histogram into hist[b, :]: one integer atomic per non-empty bin
+__device__ __forceinline__ void hist_flush(const unsigned* bins, unsigned* __restrict__ hist, int b) {
+    __syncthreads();
+    if (bins[threadIdx.x]) atomicAdd(hist + (size_t)b * 256 + threadIdx.x, bins[threadIdx.x]);
+}
+
+// Per image of the table, its min/max partials and (hist_clear != null) the zeroing of the [B,256] histogram the next kernel accumulates into.
+// DISPLAY false - out == null: min/max of the input image. Otherwise scale_prediction of it to its oh x ow (bilinear_at: rounded to the input's
+// dtype), stored as fp32 at its place of the packed out, min/max of that.
+// DISPLAY true - remove_inf_tensor(scale_prediction(x)): the resize is an identity copy when the size does not change, as torch's upsample does (a
+// bilinear tap on an inf neighbour would give NaN), +-inf -> 0, stored in the input's dtype; min/max of the result.
+template <bool DISPLAY>
+__global__ __launch_bounds__(256) void seg_scale_minmax_kernel(const PostRunTable t, int in_dt, void* __restrict__ out, unsigned* __restrict__ parts,
+                                                               unsigned* __restrict__ hist_clear) {
+    const int b = blockIdx.y;
+    if (hist_clear && blockIdx.x == 0) hist_clear[(size_t)b * 256 + threadIdx.x] = 0u;
+    int j;
+    const PostRun& img = seg_image(t, b, j);
+    const void* in = img.in;
+    const int ih = img.ih, iw = img.iw, oh = img.oh, ow = img.ow;
+    const bool store = DISPLAY || out != nullptr, resize = store && !(DISPLAY && ih == oh && iw == ow);
+    const size_t n = store ? (size_t)oh * ow : (size_t)ih * iw;
+    const size_t in_base = (size_t)j * ih * iw, out_base = img.off + (size_t)j * oh * ow;
+    const float sy = (float)ih / (float)oh, sx = (float)iw / (float)ow;
+    float lo = INFINITY, hi = -INFINITY;
+    bool saw_nan = false, any = false;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float v = resize ? bilinear_at(in, in_base, in_dt, ih, iw, sy, sx, (int)(i / ow), (int)(i % ow)) : ld_dt(in, in_base + i, in_dt);
+        if (DISPLAY && isinf(v)) v = 0.0f;
+        if (DISPLAY) st_dt(out, out_base + i, v, in_dt);
+        else if (store) ((float*)out)[out_base + i] = v;
+        any = true;
+        saw_nan |= v != v;
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+    block_minmax_part(lo, hi, saw_nan, any, parts + ((size_t)b * SEG_PARTS + blockIdx.x) * 2);
+}
+
+// (255 * normalize_01(image b)).byte() with image b's own min/max (normalize_kernel<1>'s arithmetic), optionally 255 - x, and (hist != null) image
+// b's 256-bin histogram of the result: LDS-private bins, flushed per block into hist[b, :]. Image b has ih x iw
+// elements; its result goes to its place of the packed out.
+__global__ __launch_bounds__(256) void seg_u8_hist_kernel(const PostRunTable t, int in_dt, const unsigned* __restrict__ parts, int reverse,
+                                                          unsigned char* __restrict__ out, unsigned* __restrict__ hist) {
+    const int b = blockIdx.y;
+    int j;
+    const PostRun& img = seg_image(t, b, j);
+    const void* in = img.in;
+    const size_t n = (size_t)img.ih * img.iw;
+    __shared__ unsigned bins[256];
+    bins[threadIdx.x] = 0u;
+    float lo, hi;
+    seg_range(parts, b, lo, hi);  // (publishes the zeroed bins too)
     const float range = hi - lo;
     const size_t base = (size_t)j * n, obase = img.off + (size_t)j * n;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float v = (ld_dt(in, base + i, in_dt) - lo) / range;
-        v = v == v ? fminf(fmaxf(v, 0.0f), 1.0f) : 0.0f;
-        int q = (int)(255.0f * v);
+        int q = (int)(255.0f * norm_clamp01(ld_dt(in, base + i, in_dt), lo, range, true));
         if (reverse) q = 255 - q;
         out[obase + i] = (unsigned char)q;
         if (hist) atomicAdd(&bins[q], 1u);
     }
-    if (!hist) return;
-    __syncthreads();
-    if (bins[threadIdx.x]) atomicAdd(hist + (size_t)b * 256 + threadIdx.x, bins[threadIdx.x]);
+    if (hist) hist_flush(bins, hist, b);
 }
 
 // 256-bin histogram per image of a uint8 batch, accumulated into hist[b, :] (same privatisation as above)
@@ -262,8 +299,7 @@ __global__ __launch_bounds__(256) void seg_hist_kernel(const unsigned char* __re
     __syncthreads();
     const size_t base = (size_t)b * n;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) atomicAdd(&bins[in[base + i]], 1u);
-    __syncthreads();
-    if (bins[threadIdx.x]) atomicAdd(hist + (size_t)b * 256 + threadIdx.x, bins[threadIdx.x]);
+    hist_flush(bins, hist, b);
 }
 
 // Equalization LUT of image b (one block, thread t = entry t), the reference's histogram_equalization (demo_helpers/postprocess.py:107-145):
@@ -345,6 +381,9 @@ inline int grid_for(size_t total) {
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
+// the x extent of a (blocks, images) grid
+inline int grid_seg(size_t n) { return grid_for(n) < 256 ? grid_for(n) : 256; }
+
 // images of a table (at most 65535, the grid's y) and the largest of their sizes (in: ih iw, out: oh ow); false: a malformed table
 inline bool table_extent(const PostRunTable& t, int& B, size_t& max_in, size_t& max_out) {
     B = 0;
@@ -361,31 +400,9 @@ inline bool table_extent(const PostRunTable& t, int& B, size_t& max_in, size_t& 
 }
 
 // ---- still-image display tail (the reference's run_image.py:185-195, 323-343, 350-358) and the 3D viewer's edge alpha (run_3dviewer.py:455-505).
-// Every kernel takes a uniform batch: image b is [h, w] at element b h w; grids are (parts, B) or one block per image. The arithmetic whose order the
+// Every kernel takes a uniform batch: image b is [h, w] at element b h w; grids are (parts, B) or one block per image. The prepared map comes from
+// seg_scale_minmax_kernel<true> (its display form); the kernels after the plane fit take it with its statistics as one PlaneMap (mdpt_kernels.h). The arithmetic whose order the
 // reference fixes (numpy's fp64, torch's per-op rounding) is written out with contraction off.
-
-__device__ __forceinline__ void st_dt(void* p, size_t i, float v, int dt) {
-    if (dt == MDPT_DT_BF16) ((__bf16*)p)[i] = (__bf16)v;
-    else if (dt == MDPT_DT_F16) ((_Float16*)p)[i] = (_Float16)v;
-    else ((float*)p)[i] = v;
-}
-
-// image b's {min, max} from its SEG_PARTS partials (seg_u8_hist_kernel's reduction); a block-wide call, every thread gets the pair
-__device__ __forceinline__ void seg_range(const unsigned* __restrict__ parts, int b, float& lo, float& hi) {
-    __shared__ unsigned smm[2];
-    if (threadIdx.x < 64) {
-        unsigned mn = parts[((size_t)b * SEG_PARTS + threadIdx.x) * 2], mx = parts[((size_t)b * SEG_PARTS + threadIdx.x) * 2 + 1];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn = min(mn, (unsigned)__shfl_xor((int)mn, o));
-            mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
-        }
-        if (threadIdx.x == 0) { smm[0] = mn; smm[1] = mx; }
-    }
-    __syncthreads();
-    lo = ord2f(smm[0]);
-    hi = ord2f(smm[1]);
-}
 
 // normalize_01 of a map stored in dtype dt as torch evaluates it in that dtype: (x - min) and (max - min) each rounded to dt, then the quotient
 __device__ __forceinline__ float norm01_dt(float x, float lo, float hi, int dt) {
@@ -424,29 +441,6 @@ __device__ __forceinline__ void block_sum_f64(double (&v)[K]) {
     __syncthreads();
     for (int k = 0; k < K; ++k) v[k] = ((s[0][k] + s[1][k]) + s[2][k]) + s[3][k];
     __syncthreads();
-}
-
-// remove_inf_tensor(scale_prediction(x)) per image: the bilinear resize of scale_prediction (an identity copy when the size does not change, as
-// torch's upsample does), rounded to the input dtype, +-inf -> 0, stored in that dtype; and the image's min/max partials of the result
-__global__ __launch_bounds__(256) void disp_prep_kernel(const void* __restrict__ in, int dt, int ih, int iw, void* __restrict__ out, int oh, int ow,
-                                                        unsigned* __restrict__ parts, unsigned* __restrict__ hist_clear) {
-    const int b = blockIdx.y;
-    if (hist_clear && blockIdx.x == 0) hist_clear[(size_t)b * 256 + threadIdx.x] = 0u;
-    const bool same = ih == oh && iw == ow;
-    const size_t n = (size_t)oh * ow, in_base = (size_t)b * ih * iw;
-    const float sy = (float)ih / (float)oh, sx = (float)iw / (float)ow;
-    float lo = INFINITY, hi = -INFINITY;
-    bool saw_nan = false, any = false;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float v = same ? ld_dt(in, in_base + i, dt) : bilinear_at(in, in_base, dt, ih, iw, sy, sx, (int)(i / ow), (int)(i % ow));
-        if (isinf(v)) v = 0.0f;
-        st_dt(out, (size_t)b * n + i, v, dt);
-        any = true;
-        saw_nan |= v != v;
-        lo = fminf(lo, v);
-        hi = fmaxf(hi, v);
-    }
-    block_minmax_part(lo, hi, saw_nan, any, parts + ((size_t)b * SEG_PARTS + blockIdx.x) * 2);
 }
 
 // the eigenvector of the smallest eigenvalue of a symmetric 3x3 matrix, by cyclic Jacobi with a fixed number of sweeps (quadratic convergence:
@@ -536,78 +530,64 @@ __global__ __launch_bounds__(256) void plane_eval_kernel(const double* __restric
         out[(size_t)b * n + i] = (float)plane_at(c, (int)(i % w), (int)(i / w));
 }
 
-// v = dn - factor * plane in fp64 (numpy: the fp32 map minus the fp64 plane), dn = normalize_01(image b) in dtype dt
-__device__ __forceinline__ double plane_removed(float x, float lo, float hi, int dt, const double* c, double factor, size_t i, int w) {
+// v = dn - factor * plane in fp64 at pixel (x, y) of the map at element `base` (numpy: the fp32 map minus the fp64 plane), dn = normalize_01(map)
+// in dtype dt; c = the map's plane
+__device__ __forceinline__ double plane_removed(const void* map, size_t base, int dt, int w, int x, int y, float lo, float hi, const double* c,
+                                                double factor) {
 #pragma clang fp contract(off)
-    return (double)norm01_dt(x, lo, hi, dt) - plane_at(c, (int)(i % w), (int)(i / w)) * factor;
+    return (double)norm01_dt(ld_dt(map, base + (size_t)y * w + x, dt), lo, hi, dt) - plane_at(c, x, y) * factor;
 }
 
-// per-image fp64 {min, max} partials of v: vparts[b][part] (a share without pixels is neutral; a NaN pins NaN, numpy's min / max propagate it)
-__global__ __launch_bounds__(256) void plane_minmax_kernel(const void* __restrict__ in, int dt, int h, int w, const unsigned* __restrict__ parts,
-                                                           const double* __restrict__ coef, double factor, double* __restrict__ vparts) {
-    const int b = blockIdx.y;
-    float lo, hi;
-    seg_range(parts, b, lo, hi);
+// n = normalize_01(v) in fp64 with v's {min, max - min}: the value the threshold display windows and the depth masks compare
+__device__ __forceinline__ double plane_norm(const void* map, size_t base, int dt, int w, int x, int y, float lo, float hi, const double* c, double factor,
+                                             double vlo, double vrange) {
+#pragma clang fp contract(off)
+    return (plane_removed(map, base, dt, w, x, y, lo, hi, c, factor) - vlo) / vrange;
+}
+
+// image b's plane in registers (the pointers of a PlaneMap carry no __restrict__: read through them after a store or a barrier, the plane is
+// loaded again, per lane)
+struct Plane { double c[4]; };
+__device__ __forceinline__ Plane plane_of(const double* coef, int b) {
     const double* c = coef + (size_t)b * 4;
-    const size_t n = (size_t)h * w, base = (size_t)b * n;
+    return Plane{{c[0], c[1], c[2], c[3]}};
+}
+
+// per-image fp64 {min, max} partials of v: vparts[b][part] (block_minmax_f64)
+__global__ __launch_bounds__(256) void plane_minmax_kernel(const PlaneMap m, double* __restrict__ vparts) {
+    const int b = blockIdx.y;
+    const Plane plane = plane_of(m.coef, b);
+    float lo, hi;
+    seg_range(m.parts, b, lo, hi);
+    const size_t n = (size_t)m.h * m.w, base = (size_t)b * n;
     double vlo = INFINITY, vhi = -INFINITY;
     bool saw_nan = false;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const double v = plane_removed(ld_dt(in, base + i, dt), lo, hi, dt, c, factor, i, w);
+        const double v = plane_removed(m.in, base, m.dt, m.w, (int)(i % m.w), (int)(i / m.w), lo, hi, plane.c, m.factor);
         saw_nan |= v != v;
         vlo = fmin(vlo, v);
         vhi = fmax(vhi, v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        vlo = fmin(vlo, __shfl_xor(vlo, o));
-        vhi = fmax(vhi, __shfl_xor(vhi, o));
-    }
-    const bool wave_nan = __any(saw_nan);
-    __shared__ double slo[4], shi[4];
-    __shared__ int snan[4];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { slo[wave] = vlo; shi[wave] = vhi; snan[wave] = wave_nan; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        bool any_nan = false;
-        for (int k = 0; k < 4; ++k) { vlo = fmin(vlo, slo[k]); vhi = fmax(vhi, shi[k]); any_nan |= snan[k] != 0; }
-        double* o = vparts + ((size_t)b * SEG_PARTS + blockIdx.x) * 2;
-        o[0] = any_nan ? NAN : vlo;
-        o[1] = any_nan ? NAN : vhi;
-    }
+    block_minmax_f64(vlo, vhi, saw_nan, vparts + ((size_t)b * SEG_PARTS + blockIdx.x) * 2);
 }
 
-// t = clip((normalize_01(v) - tmin) / delta, 0, 1) in fp64 (run_image.py:331-333, 355-356). Mode 1 (MDPT_POST_U8): round-half-even(255 t) -> uint8
+// t = clip((n - tmin) / delta, 0, 1) in fp64 (run_image.py:331-333, 355-356). Mode 1 (MDPT_POST_U8): round-half-even(255 t) -> uint8
 // (a NaN -> 0), and (hist != null) its 256-bin histogram into hist[b]; mode 0 (MDPT_POST_F32): t, or 1 - t with reverse, -> fp32.
 template <int MODE>
-__global__ __launch_bounds__(256) void threshold_kernel(const void* __restrict__ in, int dt, int h, int w, const unsigned* __restrict__ parts,
-                                                        const double* __restrict__ coef, double factor, const double* __restrict__ vparts,
-                                                        double tmin, double delta, int reverse, void* __restrict__ out, unsigned* __restrict__ hist) {
+__global__ __launch_bounds__(256) void threshold_kernel(const PlaneMap m, double tmin, double delta, int reverse, void* __restrict__ out,
+                                                        unsigned* __restrict__ hist) {
 #pragma clang fp contract(off)
     const int b = blockIdx.y;
+    const Plane plane = plane_of(m.coef, b);
     __shared__ unsigned bins[256];
-    __shared__ double svr[2];
     bins[threadIdx.x] = 0u;
-    if (threadIdx.x == 0) {
-        double vlo = INFINITY, vhi = -INFINITY;
-        bool any_nan = false;
-        for (int k = 0; k < SEG_PARTS; ++k) {
-            const double a = vparts[((size_t)b * SEG_PARTS + k) * 2], z = vparts[((size_t)b * SEG_PARTS + k) * 2 + 1];
-            any_nan |= a != a || z != z;
-            vlo = fmin(vlo, a);
-            vhi = fmax(vhi, z);
-        }
-        svr[0] = any_nan ? NAN : vlo;
-        svr[1] = any_nan ? NAN : vhi;
-    }
     float lo, hi;
-    seg_range(parts, b, lo, hi);  // (its __syncthreads also publishes bins and svr)
-    const double vlo = svr[0], vrange = svr[1] - svr[0];
-    const double* c = coef + (size_t)b * 4;
-    const size_t n = (size_t)h * w, base = (size_t)b * n;
+    double vlo, vrange;
+    seg_range(m.parts, b, lo, hi);  // (publishes the zeroed bins too)
+    seg_vrange(m.vparts, b, vlo, vrange);
+    const size_t n = (size_t)m.h * m.w, base = (size_t)b * n;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const double v = (plane_removed(ld_dt(in, base + i, dt), lo, hi, dt, c, factor, i, w) - vlo) / vrange;
+        const double v = plane_norm(m.in, base, m.dt, m.w, (int)(i % m.w), (int)(i / m.w), lo, hi, plane.c, m.factor, vlo, vrange);
         double t = (v - tmin) / delta;
         t = t != t ? t : (t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t));
         if (MODE == 1) {
@@ -618,9 +598,7 @@ __global__ __launch_bounds__(256) void threshold_kernel(const void* __restrict__
             ((float*)out)[base + i] = (float)(reverse ? 1.0 - t : t);
         }
     }
-    if (MODE != 1 || !hist) return;
-    __syncthreads();
-    if (bins[threadIdx.x]) atomicAdd(hist + (size_t)b * 256 + threadIdx.x, bins[threadIdx.x]);
+    if (MODE == 1 && hist) hist_flush(bins, hist, b);
 }
 
 // ---- edge alpha (run_3dviewer.py:455-505): blur = conv(x, gauss, reflect pad p), (dx, dy) = conv(blur, sobel, reflect pad 1), mag = sqrt(dx^2 + dy^2)
@@ -632,7 +610,7 @@ struct EdgeBlur { float w[(2 * EDGE_MAX_PAD + 1) * (2 * EDGE_MAX_PAD + 1)]; int 
 // the blurred tile with a 1-pixel halo (each at the reflected blurred coordinate, so the Sobel halo reflects on the blurred map as torch pads it),
 // then the Sobel magnitude -> mag[b] (blur and Sobel in fp64: the Sobel differences neighbouring blurred values of up to ~k^2 times the map, which
 // leaves fp32 sums a few 1e-3 of a byte off at 1080p; fp64 keeps the bytes off the reference's only at rounding ties), and the image's max through an atomicMax on the bits of the (non-negative) fp32 magnitudes. parts != null:
-// the map is normalize_01(x) in fp32 first (normalize_kernel's arithmetic).
+// the map is normalize_01(x) in fp32 first (norm01).
 __global__ __launch_bounds__(256) void edge_mag_kernel(const float* __restrict__ in, int h, int w, const unsigned* __restrict__ parts, const EdgeBlur blur,
                                                        float* __restrict__ mag, unsigned* __restrict__ mag_max) {
     constexpr int BT = EDGE_TILE + 2, RMAX = BT + 2 * EDGE_MAX_PAD;
@@ -648,7 +626,7 @@ __global__ __launch_bounds__(256) void edge_mag_kernel(const float* __restrict__
     for (int e = t; e < R * R; e += 256) {
         const int vy = y0 - 1 - p + e / R, vx = x0 - 1 - p + e % R;
         const float v = img[(size_t)reflect_idx(vy, h) * w + reflect_idx(vx, w)];
-        sx[e] = parts ? (v - lo) / range : v;
+        sx[e] = norm01(v, lo, range, parts != nullptr);
     }
     __syncthreads();
     for (int e = t; e < BT * BT; e += 256) {
@@ -692,7 +670,7 @@ __global__ __launch_bounds__(256) void edge_mask_kernel(const float* __restrict_
         out[(size_t)b * n + i] = edge_byte(mag[(size_t)b * n + i], mx);
 }
 
-// pack_depth_u24 per image (normalize_kernel<2>'s arithmetic with image b's min/max from parts; parts == null: metric, as is) with the alpha byte
+// pack_depth_u24 per image (norm_clamp01 with image b's min/max from parts; parts == null: metric, as is; then u24_px) with the alpha byte
 // in the same pass: the edge byte of mag (mag != null), the caller's mask (mask != null; per image or one for all), or 0
 __global__ __launch_bounds__(256) void pack_u24_kernel(const float* __restrict__ in, size_t n, const unsigned* __restrict__ parts, int lossy,
                                                        const float* __restrict__ mag, const unsigned* __restrict__ mag_max,
@@ -704,20 +682,13 @@ __global__ __launch_bounds__(256) void pack_u24_kernel(const float* __restrict__
     const float mx = mag ? __uint_as_float(mag_max[b]) : 0.0f;
     const size_t base = (size_t)b * n;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float v = parts ? (in[base + i] - lo) / range : in[base + i];
-        v = v == v ? fminf(fmaxf(v, 0.0f), 1.0f) : 0.0f;
-        const int q = (int)rintf(16777215.0f * v);
-        uchar4 px;
-        px.x = lossy ? 0 : (unsigned char)(q & 255);
-        px.y = lossy ? 0 : (unsigned char)((q >> 8) & 255);
-        px.z = (unsigned char)((q >> 16) & 255);
-        px.w = mag ? edge_byte(mag[base + i], mx) : (mask ? mask[(size_t)b * mask_stride + i] : (unsigned char)0);
-        out[base + i] = px;
+        const unsigned char alpha = mag ? edge_byte(mag[base + i], mx) : (mask ? mask[(size_t)b * mask_stride + i] : (unsigned char)0);
+        out[base + i] = u24_px(norm_clamp01(in[base + i], lo, range, parts != nullptr), lossy, alpha);
     }
 }
 
 // ---- depth masking (the reference's experiments/depth_masking.py: display :189-199, 314-332; save :341-361). n = normalize_01(normalize_01(x) - f plane)
-// in fp64 (threshold_kernel's value before its window), mask = 255 where tmin <= n <= tmax (a NaN compares false: 0), 255 - mask with invert.
+// in fp64 (plane_norm), mask = 255 where tmin <= n <= tmax (a NaN compares false: 0), 255 - mask with invert.
 // cv2.resize(INTER_LINEAR) is restated per axis: p = float((d + 0.5) scale - 0.5) with scale = 1 / (out / in) in fp64 (cv2's own form), s = floor(p),
 // a = p - s in fp32; s < 0 -> s = 0, a = 0; s >= in - 1 -> s = in - 1, a = 0. CV_64F: weights (1 - a, a) in fp32, sums in fp64, rows first, then
 // across them. CV_8U: weights round(2048 w), integer sums, (v + 2^21) >> 22: cv2's scalar fixed-point path (its SIMD / IPP paths may round 1 off).
@@ -742,45 +713,6 @@ __device__ __forceinline__ double lerp_cv64(double v0, double v1, float a) {
     return a == 0.0f ? v0 : v0 * (double)(1.0f - a) + v1 * (double)a;
 }
 
-// the photo's statistics, block-wide: the map's fp32 {min, max} from its parts and the fp64 {min, max - min} of its plane-removed values from its
-// vparts (threshold_kernel's reduction: a NaN partial pins NaN; one lane per partial)
-__device__ __forceinline__ void mask_stats(const unsigned* __restrict__ parts, const double* __restrict__ vparts, float& lo, float& hi, double& vlo,
-                                           double& vrange) {
-    __shared__ unsigned smm[2];
-    __shared__ double svr[2];
-    if (threadIdx.x < SEG_PARTS) {
-        unsigned mn = parts[threadIdx.x * 2], mx = parts[threadIdx.x * 2 + 1];
-        double a = vparts[threadIdx.x * 2], z = vparts[threadIdx.x * 2 + 1];
-        const bool any_nan = __any(a != a || z != z);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn = min(mn, (unsigned)__shfl_xor((int)mn, o));
-            mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
-            a = fmin(a, __shfl_xor(a, o));
-            z = fmax(z, __shfl_xor(z, o));
-        }
-        if (threadIdx.x == 0) {
-            smm[0] = mn;
-            smm[1] = mx;
-            svr[0] = any_nan ? NAN : a;
-            svr[1] = any_nan ? NAN : z;
-        }
-    }
-    __syncthreads();
-    lo = ord2f(smm[0]);
-    hi = ord2f(smm[1]);
-    vlo = svr[0];
-    vrange = svr[1] - svr[0];
-}
-
-// n at pixel (x, y) of the map at element `base` (plane_removed's arithmetic, then threshold_kernel's normalisation)
-__device__ __forceinline__ double mask_n(const void* map, size_t base, int dt, int w, int x, int y, float lo, float hi, const double* c, double factor,
-                                         double vlo, double vrange) {
-#pragma clang fp contract(off)
-    const double v = (double)norm01_dt(ld_dt(map, base + (size_t)y * w + x, dt), lo, hi, dt) - plane_at(c, x, y) * factor;
-    return (v - vlo) / vrange;
-}
-
 __device__ __forceinline__ unsigned mask_byte(double n, double tmin, double tmax, int invert) {
     return ((n >= tmin && n <= tmax) != (invert != 0)) ? 255u : 0u;
 }
@@ -803,15 +735,17 @@ __device__ __forceinline__ void bgr_lerp_u8(const unsigned char* __restrict__ sr
 // display (uniform batch, map b at the display size h x w, photo b ih x iw): the mask of n, and the composite - cv2.resize of the photo where the
 // mask is 255, CheckerPattern() where it is 0: A = 169 where ((y - t) mod 64 < 32) == ((x - l) mod 64 < 32), else B = 214, t = max(h - 64, 0) / 2,
 // l = max(w - 64, 0) / 2 (toadui/helpers/checker_pattern.py: 32-px tiles, BORDER_WRAP padding, cropped). MASK_PX pixels of the flat image per thread.
-__global__ __launch_bounds__(256) void mask_display_kernel(const void* __restrict__ map, int dt, int h, int w, const unsigned* __restrict__ parts,
-                                                           const double* __restrict__ coef, double factor, const double* __restrict__ vparts, double tmin,
-                                                           double tmax, int invert, const unsigned char* __restrict__ img, int ih, int iw,
-                                                           unsigned char* __restrict__ mask_out, unsigned char* __restrict__ comp_out) {
+__global__ __launch_bounds__(256) void mask_display_kernel(const PlaneMap m, double tmin, double tmax, int invert, const unsigned char* __restrict__ img,
+                                                           int ih, int iw, unsigned char* __restrict__ mask_out, unsigned char* __restrict__ comp_out) {
     const int b = blockIdx.y;
+    const Plane plane = plane_of(m.coef, b);
+    const int dt = m.dt, h = m.h, w = m.w;
+    const void* map = m.in;
+    const double factor = m.factor;
     float lo, hi;
     double vlo, vrange;
-    mask_stats(parts + (size_t)b * SEG_PARTS * 2, vparts + (size_t)b * SEG_PARTS * 2, lo, hi, vlo, vrange);
-    const double* c = coef + (size_t)b * 4;
+    seg_range(m.parts, b, lo, hi);
+    seg_vrange(m.vparts, b, vlo, vrange);
     const size_t n = (size_t)h * w, base = (size_t)b * n;
     const unsigned char* src = img + (size_t)b * ih * iw * 3;
     const double scale_x = 1.0 / ((double)w / (double)iw), scale_y = 1.0 / ((double)h / (double)ih);
@@ -826,7 +760,7 @@ __global__ __launch_bounds__(256) void mask_display_kernel(const void* __restric
         for (int k = 0; k < MASK_PX; ++k) {
             px[k * 3] = px[k * 3 + 1] = px[k * 3 + 2] = 0;
             if (k >= cnt) continue;
-            const unsigned m = mask_byte(mask_n(map, base, dt, w, x, y, lo, hi, c, factor, vlo, vrange), tmin, tmax, invert);
+            const unsigned m = mask_byte(plane_norm(map, base, dt, w, x, y, lo, hi, plane.c, factor, vlo, vrange), tmin, tmax, invert);
             mword |= m << (8 * k);
             if (m) {
                 bgr_lerp_u8(src, iw, cv_tap(x, scale_x, iw), ty, px + k * 3);
@@ -865,7 +799,8 @@ __global__ __launch_bounds__(256) void mask_cutout_kernel(const MaskTable t, dou
     const MaskImage& im = t.im[blockIdx.y];
     float lo, hi;
     double vlo, vrange;
-    mask_stats(im.parts, im.vparts, lo, hi, vlo, vrange);
+    seg_range(im.parts, 0, lo, hi);
+    seg_vrange(im.vparts, 0, vlo, vrange);
     const int dt = t.dt, h = im.h, w = im.w, ih = im.ih, iw = im.iw;
     const void* map = im.map;
     const double* c = im.coef;
@@ -900,10 +835,10 @@ __global__ __launch_bounds__(256) void mask_cutout_kernel(const MaskTable t, dou
             if (2 * tx.s0 + bx != key_x || 2 * ty.s0 + by != key_y) {
                 key_x = 2 * tx.s0 + bx;
                 key_y = 2 * ty.s0 + by;
-                n00 = mask_n(map, 0, dt, w, tx.s0, ty.s0, lo, hi, c, factor, vlo, vrange);
-                n01 = bx ? mask_n(map, 0, dt, w, tx.s1, ty.s0, lo, hi, c, factor, vlo, vrange) : n00;
-                n10 = by ? mask_n(map, 0, dt, w, tx.s0, ty.s1, lo, hi, c, factor, vlo, vrange) : n00;
-                n11 = bx && by ? mask_n(map, 0, dt, w, tx.s1, ty.s1, lo, hi, c, factor, vlo, vrange) : (bx ? n01 : n10);
+                n00 = plane_norm(map, 0, dt, w, tx.s0, ty.s0, lo, hi, c, factor, vlo, vrange);
+                n01 = bx ? plane_norm(map, 0, dt, w, tx.s1, ty.s0, lo, hi, c, factor, vlo, vrange) : n00;
+                n10 = by ? plane_norm(map, 0, dt, w, tx.s0, ty.s1, lo, hi, c, factor, vlo, vrange) : n00;
+                n11 = bx && by ? plane_norm(map, 0, dt, w, tx.s1, ty.s1, lo, hi, c, factor, vlo, vrange) : (bx ? n01 : n10);
             }
             const double s = lerp_cv64(lerp_cv64(n00, n01, tx.a), lerp_cv64(n10, n11, tx.a), ty.a);
             const unsigned m = mask_byte(s, tmin, tmax, invert);
@@ -1016,7 +951,7 @@ int mdpt_launch_post_seg_minmax(const PostRunTable& t, int in_dt, float* out, un
     size_t max_in, max_out;
     if (!table_extent(t, B, max_in, max_out)) return (int)hipErrorInvalidValue;
     MdptProfScope prof("seg_scale_minmax_kernel", 0.0, stream);
-    hipLaunchKernelGGL(seg_scale_minmax_kernel, dim3(SEG_PARTS, B), dim3(256), 0, stream, t, in_dt, out, parts, hist_clear);
+    hipLaunchKernelGGL(seg_scale_minmax_kernel<false>, dim3(SEG_PARTS, B), dim3(256), 0, stream, t, in_dt, (void*)out, parts, hist_clear);
     return (int)hipGetLastError();
 }
 
@@ -1025,13 +960,13 @@ int mdpt_launch_post_seg_u8(const PostRunTable& t, int in_dt, const unsigned* pa
     size_t n, max_out;
     if (!table_extent(t, B, n, max_out)) return (int)hipErrorInvalidValue;
     MdptProfScope prof("seg_u8_hist_kernel", 0.0, stream);
-    hipLaunchKernelGGL(seg_u8_hist_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, t, in_dt, parts, reverse, out, hist);
+    hipLaunchKernelGGL(seg_u8_hist_kernel, dim3(grid_seg(n), B), dim3(256), 0, stream, t, in_dt, parts, reverse, out, hist);
     return (int)hipGetLastError();
 }
 
 int mdpt_launch_post_hist(const unsigned char* in, int B, size_t n, unsigned* hist, hipStream_t stream) {
     MdptProfScope prof("seg_hist_kernel", 0.0, stream);
-    hipLaunchKernelGGL(seg_hist_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, in, n, hist);
+    hipLaunchKernelGGL(seg_hist_kernel, dim3(grid_seg(n), B), dim3(256), 0, stream, in, n, hist);
     return (int)hipGetLastError();
 }
 
@@ -1047,14 +982,15 @@ int mdpt_launch_post_colorize(const PostRunTable& t, const unsigned char* eq, co
     size_t n, max_out;
     if (!table_extent(t, B, n, max_out)) return (int)hipErrorInvalidValue;
     MdptProfScope prof("colorize_kernel", 0.0, stream);
-    hipLaunchKernelGGL(colorize_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, t, eq, cmap, channels, out);
+    hipLaunchKernelGGL(colorize_kernel, dim3(grid_seg(n), B), dim3(256), 0, stream, t, eq, cmap, channels, out);
     return (int)hipGetLastError();
 }
 
 int mdpt_launch_post_display_prep(const void* in, int dt, int B, int ih, int iw, void* out, int oh, int ow, unsigned* parts, unsigned* hist_clear,
                                   hipStream_t stream) {
-    MdptProfScope prof("disp_prep_kernel", 0.0, stream);
-    hipLaunchKernelGGL(disp_prep_kernel, dim3(SEG_PARTS, B), dim3(256), 0, stream, in, dt, ih, iw, out, oh, ow, parts, hist_clear);
+    MdptProfScope prof("disp_prep_kernel", 0.0, stream);  // (the label the probes and profiles know the display form by)
+    hipLaunchKernelGGL(seg_scale_minmax_kernel<true>, dim3(SEG_PARTS, B), dim3(256), 0, stream, uniform_table(in, B, ih, iw, oh, ow), dt, out, parts,
+                       hist_clear);
     return (int)hipGetLastError();
 }
 
@@ -1068,24 +1004,21 @@ int mdpt_launch_post_plane_fit(const void* in, int dt, int B, int h, int w, cons
 int mdpt_launch_post_plane_eval(const double* coef, int B, int h, int w, float* out, hipStream_t stream) {
     const size_t n = (size_t)h * w;
     MdptProfScope prof("plane_eval_kernel", 0.0, stream);
-    hipLaunchKernelGGL(plane_eval_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, coef, h, w, out);
+    hipLaunchKernelGGL(plane_eval_kernel, dim3(grid_seg(n), B), dim3(256), 0, stream, coef, h, w, out);
     return (int)hipGetLastError();
 }
 
-int mdpt_launch_post_plane_minmax(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, double* vparts,
-                                  hipStream_t stream) {
+int mdpt_launch_post_plane_minmax(const PlaneMap& m, double* vparts, hipStream_t stream) {
     MdptProfScope prof("plane_minmax_kernel", 0.0, stream);
-    hipLaunchKernelGGL(plane_minmax_kernel, dim3(SEG_PARTS, B), dim3(256), 0, stream, in, dt, h, w, parts, coef, factor, vparts);
+    hipLaunchKernelGGL(plane_minmax_kernel, dim3(SEG_PARTS, m.B), dim3(256), 0, stream, m, vparts);
     return (int)hipGetLastError();
 }
 
-int mdpt_launch_post_threshold(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, const double* vparts,
-                               double tmin, double delta, int mode, int reverse, void* out, unsigned* hist, hipStream_t stream) {
-    const size_t n = (size_t)h * w;
-    const dim3 grid(grid_for(n) < 256 ? grid_for(n) : 256, B);
+int mdpt_launch_post_threshold(const PlaneMap& m, double tmin, double delta, int mode, int reverse, void* out, unsigned* hist, hipStream_t stream) {
+    const dim3 grid(grid_seg((size_t)m.h * m.w), m.B);
     MdptProfScope prof("threshold_kernel", 0.0, stream);
-    if (mode == 1) hipLaunchKernelGGL(threshold_kernel<1>, grid, dim3(256), 0, stream, in, dt, h, w, parts, coef, factor, vparts, tmin, delta, reverse, out, hist);
-    else hipLaunchKernelGGL(threshold_kernel<0>, grid, dim3(256), 0, stream, in, dt, h, w, parts, coef, factor, vparts, tmin, delta, reverse, out, hist);
+    if (mode == 1) hipLaunchKernelGGL(threshold_kernel<1>, grid, dim3(256), 0, stream, m, tmin, delta, reverse, out, hist);
+    else hipLaunchKernelGGL(threshold_kernel<0>, grid, dim3(256), 0, stream, m, tmin, delta, reverse, out, hist);
     return (int)hipGetLastError();
 }
 
@@ -1105,25 +1038,23 @@ int mdpt_launch_post_edge_mag(const float* in, int B, int h, int w, const unsign
 
 int mdpt_launch_post_edge_mask(const float* mag, const unsigned* mag_max, int B, size_t n, unsigned char* out, hipStream_t stream) {
     MdptProfScope prof("edge_mask_kernel", 0.0, stream);
-    hipLaunchKernelGGL(edge_mask_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, mag, mag_max, n, out);
+    hipLaunchKernelGGL(edge_mask_kernel, dim3(grid_seg(n), B), dim3(256), 0, stream, mag, mag_max, n, out);
     return (int)hipGetLastError();
 }
 
 int mdpt_launch_post_pack_u24(const float* in, int B, size_t n, const unsigned* parts, int lossy, const float* mag, const unsigned* mag_max,
                               const unsigned char* mask, size_t mask_stride, unsigned char* out, hipStream_t stream) {
     MdptProfScope prof("pack_u24_kernel", 0.0, stream);
-    hipLaunchKernelGGL(pack_u24_kernel, dim3(grid_for(n) < 256 ? grid_for(n) : 256, B), dim3(256), 0, stream, in, n, parts, lossy, mag, mag_max, mask,
+    hipLaunchKernelGGL(pack_u24_kernel, dim3(grid_seg(n), B), dim3(256), 0, stream, in, n, parts, lossy, mag, mag_max, mask,
                        mask_stride, (uchar4*)out);
     return (int)hipGetLastError();
 }
 
-int mdpt_launch_post_mask_display(const void* in, int dt, int B, int h, int w, const unsigned* parts, const double* coef, double factor, const double* vparts,
-                                  double tmin, double tmax, int invert, const unsigned char* img, int ih, int iw, unsigned char* mask, unsigned char* comp,
-                                  hipStream_t stream) {
-    const size_t g = ((size_t)h * w + 256 * MASK_PX - 1) / (256 * MASK_PX);
+int mdpt_launch_post_mask_display(const PlaneMap& m, double tmin, double tmax, int invert, const unsigned char* img, int ih, int iw, unsigned char* mask,
+                                  unsigned char* comp, hipStream_t stream) {
+    const size_t g = ((size_t)m.h * m.w + 256 * MASK_PX - 1) / (256 * MASK_PX);
     MdptProfScope prof("mask_display_kernel", 0.0, stream);
-    hipLaunchKernelGGL(mask_display_kernel, dim3(g > 512 ? 512 : (int)g, B), dim3(256), 0, stream, in, dt, h, w, parts, coef, factor, vparts, tmin, tmax,
-                       invert, img, ih, iw, mask, comp);
+    hipLaunchKernelGGL(mask_display_kernel, dim3(g > 512 ? 512 : (int)g, m.B), dim3(256), 0, stream, m, tmin, tmax, invert, img, ih, iw, mask, comp);
     return (int)hipGetLastError();
 }
 
