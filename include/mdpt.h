@@ -447,6 +447,37 @@ int mdpt_post_mask_cutout_images(const void* const* maps, const int32_t* map_hw,
 int mdpt_post_block_norm_tiles(const void* const* maps, const int32_t* map_hw, int32_t L, int32_t B, int32_t H, int32_t W, void* tiles_u8, void* minmax_f32,
                                void* stream);
 
+/* Depth-to-mesh on the device (additive to ABI v6): the client half of the reference's 3D viewer, its "Save 3D Model" - JavaScript on the CPU there.
+ * frames_bgra = uint8 [B,H,W,4] as mdpt_post_pack_u24_alpha writes them (bytes 0..2 the low / mid / high byte of the 24-bit depth, byte 3 alpha),
+ * 4-byte aligned. Nothing is read back, nothing synchronises.
+ *   mdpt_post_mesh_grid ........... host arithmetic only, 3dviewer/mesh.js:184-200: t = max(target_faces, 2), tv = round(t / 2 + sqrt(t)),
+ *                                   rx = sqrt(tv w / h), ry = rx / (w / h), nx = max(round(rx), 2), ny = max(round(ry), 2) in double, round =
+ *                                   Math.round (halves toward +inf). Vertex (row r, col c) = index c + r nx at (c 2 / (nx - 1) - 1, 1 - r 2 / (ny - 1)).
+ *   mdpt_post_mesh_scratch_bytes .. the device scratch one mdpt_post_mesh call of B images on an nx x ny grid needs
+ *   mdpt_post_mesh ................ per vertex (shaders.js:185-205, 212-252; vertex_xy_f64 = device fp64 [nx ny, 2] replaces the grid's coordinates,
+ *                                   NULL: the grid's own): uv = ((x + 1) / 2, (y + 1) / 2); a bilinear sample of the frame flipped vertically
+ *                                   (index.html:1067-1070) at clamp01(uv) * (W - 1, H - 1), taps floor and min(floor + 1, side - 1); depth taps are
+ *                                   u24 / 2^24, alpha taps the bytes; kept if alpha >= edge_threshold * 255; depth = a + b d (is_metric) or
+ *                                   1 / (a + b d) (index.html:1179-1188); xyz = (depth x x_scale tan_half_fov, depth y y_scale tan_half_fov, -depth).
+ *                                   All of it in fp64, rounded to fp32 once. Faces (mesh.js:207-229): cell (r, c) in vertex order gives
+ *                                   [v, v + nx, v + nx + 1] and [v, v + nx + 1, v + 1]; MDPT_MESH_POINTS: [i] per vertex. Filtering
+ *                                   (mesh.js:330-371): kept vertices keep their order and are renumbered from 0; a face is kept if all its vertices
+ *                                   are, keeps its order and takes the new indices. Outputs are full-capacity slabs with each image's kept entries
+ *                                   packed at the front (the rest is left as it was): xyz_f32 [B, nx ny, 3], uv_f32 [B, nx ny, 2], faces_u32
+ *                                   [B, 2 (nx - 1)(ny - 1), 3] (points: [B, nx ny, 1]), counts_i32 [B, 2] = {kept vertices, kept faces},
+ *                                   bounds_f32 [B, 2, 3] = {min xyz, max xyz} of the kept vertices (save_gltf.js:16-25; none kept: +1e6 / -1e6).
+ *                                   Order-preserving and bit-deterministic; five launches (four for points).
+ * Two deviations: the 24-bit depth VALUE is interpolated (the JavaScript interpolates the three bytes separately and truncates each, which is
+ * garbage across a byte carry such as 0x00FFFF | 0x010000), and real bounds are not clamped to +-1e6. Grids need sides of at least 2 and fewer
+ * than 2^31 vertices and faces. */
+#define MDPT_MESH_TRIANGLES 0
+#define MDPT_MESH_POINTS 1
+int mdpt_post_mesh_grid(int32_t w, int32_t h, double target_faces, int32_t* nx, int32_t* ny);
+int mdpt_post_mesh_scratch_bytes(int32_t B, int32_t nx, int32_t ny, size_t* bytes);
+int mdpt_post_mesh(const void* frames_bgra, int32_t B, int32_t H, int32_t W, int32_t nx, int32_t ny, const void* vertex_xy_f64, double a, double b,
+                   double tan_half_fov, double x_scale, double y_scale, double edge_threshold, int32_t is_metric, int32_t mode, void* xyz_f32,
+                   void* uv_f32, void* faces_u32, void* counts_i32, void* bounds_f32, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

@@ -213,6 +213,19 @@ struct PlaneMap { const void* in; int dt, B, h, w; const unsigned* parts; const 
 struct MaskImage { const void* map; const unsigned* parts; const double* coef; const double* vparts; const unsigned char* img; size_t off; int h, w, ih, iw; };
 struct MaskTable { MaskImage im[MDPT_MASK_IMAGES]; int n, dt; };
 
+// one depth-to-mesh call (postprocess.hip mesh_* kernels), by value: B frames [H, W, 4] of 24-bit depth + alpha bytes, a plane grid of nx x ny
+// vertices (vertex i = c + r nx at (c x_step - 1, 1 - r y_step), or at vertex_xy[i] when the fp64 [nx ny, 2] table is given), the camera of the
+// viewer's vertex shader (depth = a + b d, or 1 / (a + b d) for relative models; alpha_min = edge_threshold * 255) and the scratch planes of the
+// multi-launch compaction: vmap [B, nx ny] (-1 = dropped vertex, else its new index), vcnt / fcnt = per-block kept counts -> exclusive offsets,
+// bord [B, 6] ordered-uint {min xyz, max xyz}
+struct MeshJob {
+    const unsigned* frames; const double* vertex_xy;
+    int B, H, W, nx, ny, is_metric, points;
+    double x_step, y_step, a, b, tan_half_fov, x_scale, y_scale, alpha_min;
+    int* vmap; unsigned* vcnt; unsigned* fcnt; unsigned* bord;
+};
+inline size_t mesh_blocks(size_t n) { return (n + 255) / 256; }  // the compaction's blocks: 256 vertices (or grid cells) each
+
 // the same for every block of the encoder in ONE launch (the LUTs depend on weights and window sizes only, not on activations)
 struct SwinCpbBatch {
     const float* w1[32]; const float* b1[32]; const float* w2[32]; float* lut[32];
@@ -260,6 +273,10 @@ int mdpt_launch_post_mask_cutout(const MaskTable& t, double factor, double tmin,
 // block norm tiles (experiments/block_norm_visualization.py): run r of the table = the B = count fp32 maps [ih, iw] of one block, each normalised by
 // its own min / max to uint8 and enlarged by the whole factors oh / ih, ow / iw into its tile of the packed out; minmax = [images of the table, 2]
 int mdpt_launch_post_block_norm_tiles(const PostRunTable& t, unsigned char* out, float* minmax, hipStream_t stream);
+// depth-to-mesh (the 3D viewer's "Save 3D Model": shaders.js run_vertex_shader_cpu, mesh.js _make_plane_mesh / filter_mesh_vertices): MeshJob above ->
+// the kept vertices (xyz [B, nv, 3], uv [B, nv, 2]) and faces ([B, nf, 3] or, for points, [B, nv, 1]) packed at the front of each image's slab,
+// counts [B, 2] = {kept vertices, kept faces}, bounds [B, 2, 3] = {min xyz, max xyz}. Five launches (four for points), no single-pass scan.
+int mdpt_launch_post_mesh(const MeshJob& m, float* xyz, float* uv, unsigned* faces, int* counts, float* bounds, hipStream_t stream);
 
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);

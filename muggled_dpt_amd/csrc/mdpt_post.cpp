@@ -316,4 +316,74 @@ int mdpt_post_block_norm_tiles(const void* const* maps, const int32_t* map_hw, i
     return 0;
 }
 
+// ---- depth-to-mesh (3dviewer/mesh.js:184-200 grid, shaders.js:163-264 vertices, mesh.js:330-371 filtering, save_gltf.js:16-25 bounds)
+static double js_round(double v) {  // Math.round: halves go toward +inf
+    const double f = floor(v);
+    return v - f >= 0.5 ? f + 1.0 : f;
+}
+
+int mdpt_post_mesh_grid(int32_t w, int32_t h, double target_faces, int32_t* nx, int32_t* ny) {
+    if (!nx || !ny) return fail(MDPT_E_INVALID, "null argument");
+    if (w <= 0 || h <= 0 || !(target_faces == target_faces)) return fail(MDPT_E_INVALID, "bad photo size %dx%d / face target %g", w, h, target_faces);
+    const double t = target_faces > 2.0 ? target_faces : 2.0;
+    const double tv = js_round(0.5 * t + sqrt(t));
+    const double aspect = (double)w / (double)h;
+    const double rx = sqrt(tv * aspect), ry = rx / aspect;
+    const double fx = js_round(rx) > 2.0 ? js_round(rx) : 2.0, fy = js_round(ry) > 2.0 ? js_round(ry) : 2.0;
+    if (fx * fy >= 2147483648.0) return fail(MDPT_E_INVALID, "a grid of %.0f x %.0f vertices is too large (the product must be below 2^31)", fx, fy);
+    *nx = (int32_t)fx;
+    *ny = (int32_t)fy;
+    return 0;
+}
+
+// nx x ny vertices: sides of at least 2, fewer than 2^31 vertices and faces (counts are int32, face indices uint32)
+static int check_mesh_grid(int32_t nx, int32_t ny) {
+    if (nx < 2 || ny < 2) return fail(MDPT_E_INVALID, "a mesh grid needs sides of at least 2, got %dx%d", nx, ny);
+    if ((size_t)nx * (size_t)ny >= ((size_t)1 << 31) || 2 * ((size_t)nx - 1) * ((size_t)ny - 1) >= ((size_t)1 << 31))
+        return fail(MDPT_E_INVALID, "a grid of %dx%d vertices is too large (vertices and faces must each be fewer than 2^31)", nx, ny);
+    return 0;
+}
+
+// the scratch of B images: the vertex map, the two lists of block counts, the ordered bounds - 4-byte words, in MeshJob's order
+static size_t mesh_scratch_words(size_t B, int32_t nx, int32_t ny) {
+    const size_t nv = (size_t)nx * ny, cells = ((size_t)nx - 1) * ((size_t)ny - 1);
+    return B * (nv + mesh_blocks(nv) + mesh_blocks(cells) + 6);
+}
+
+int mdpt_post_mesh_scratch_bytes(int32_t B, int32_t nx, int32_t ny, size_t* bytes) {
+    if (!bytes) return fail(MDPT_E_INVALID, "null argument");
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    CHK(check_mesh_grid(nx, ny));
+    *bytes = 4 * mesh_scratch_words((size_t)B, nx, ny);
+    return 0;
+}
+
+int mdpt_post_mesh(const void* frames_bgra, int32_t B, int32_t H, int32_t W, int32_t nx, int32_t ny, const void* vertex_xy_f64, double a, double b,
+                   double tan_half_fov, double x_scale, double y_scale, double edge_threshold, int32_t is_metric, int32_t mode, void* xyz_f32,
+                   void* uv_f32, void* faces_u32, void* counts_i32, void* bounds_f32, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!frames_bgra || !xyz_f32 || !uv_f32 || !faces_u32 || !counts_i32 || !bounds_f32 || !scratch) return fail(MDPT_E_INVALID, "null argument");
+    if (((uintptr_t)frames_bgra & 3) != 0) return fail(MDPT_E_INVALID, "the BGRA frames must be 4-byte aligned");
+    CHK(check_batch_hw(B, H, W));
+    CHK(check_mesh_grid(nx, ny));
+    if (mode != MDPT_MESH_TRIANGLES && mode != MDPT_MESH_POINTS) return fail(MDPT_E_INVALID, "unknown mesh mode %d", mode);
+    if (!(edge_threshold == edge_threshold)) return fail(MDPT_E_INVALID, "the edge threshold is not a number");
+    if (scratch_bytes < 4 * mesh_scratch_words((size_t)B, nx, ny))
+        return fail(MDPT_E_INVALID, "mesh scratch of %zu bytes, %zu needed (mdpt_post_mesh_scratch_bytes)", scratch_bytes,
+                    4 * mesh_scratch_words((size_t)B, nx, ny));
+    const size_t nv = (size_t)nx * ny, cells = ((size_t)nx - 1) * ((size_t)ny - 1);
+    MeshJob m{};
+    m.frames = (const unsigned*)frames_bgra;
+    m.vertex_xy = (const double*)vertex_xy_f64;
+    m.B = B, m.H = H, m.W = W, m.nx = nx, m.ny = ny, m.is_metric = is_metric != 0, m.points = mode == MDPT_MESH_POINTS;
+    m.x_step = 2.0 / (double)(nx - 1), m.y_step = 2.0 / (double)(ny - 1);  // mesh.js:198
+    m.a = a, m.b = b, m.tan_half_fov = tan_half_fov, m.x_scale = x_scale, m.y_scale = y_scale;
+    m.alpha_min = edge_threshold * 255.0;  // shaders.js:175
+    m.vmap = (int*)scratch;
+    m.vcnt = (unsigned*)scratch + (size_t)B * nv;
+    m.fcnt = m.vcnt + (size_t)B * mesh_blocks(nv);
+    m.bord = m.fcnt + (size_t)B * mesh_blocks(cells);
+    CHK(mdpt_launch_post_mesh(m, (float*)xyz_f32, (float*)uv_f32, (unsigned*)faces_u32, (int*)counts_i32, (float*)bounds_f32, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

@@ -49,6 +49,7 @@ POST_F32, POST_U8, POST_U24 = 0, 1, 2
 POST_SEG_PARTS = 64  # MDPT_POST_SEG_PARTS
 BGR_RUNS, POST_RUNS = 64, 32  # MDPT_BGR_RUNS / MDPT_POST_RUNS (csrc/mdpt_kernels.h): images per launch of a per-image table
 INTERP_BILINEAR, INTERP_BICUBIC = 0, 1
+MESH_TRIANGLES, MESH_POINTS = 0, 1  # MDPT_MESH_*
 
 
 def _hipcc() -> str:
@@ -218,6 +219,9 @@ SYMBOLS = {
     "mdpt_post_mask_display": (ctypes.c_int, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _D, _D, _I, _VP, _I, _I, _VP, _VP, _VP]),
     "mdpt_post_mask_cutout_images": (ctypes.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _D, _VP, _VP, _VP, _I, _D, _D, _I, _VP, _VP, _VP]),
     "mdpt_post_block_norm_tiles": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP]),
+    "mdpt_post_mesh_grid": (ctypes.c_int, [_I, _I, _D, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "mdpt_post_mesh_scratch_bytes": (ctypes.c_int, [_I, _I, _I, ctypes.POINTER(_SZ)]),
+    "mdpt_post_mesh": (ctypes.c_int, [_VP, _I, _I, _I, _I, _I, _VP, _D, _D, _D, _D, _D, _D, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

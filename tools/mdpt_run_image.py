@@ -12,6 +12,9 @@ For one image or several, --cutout DIR saves the depth masking demo's results at
 For one image or several, --block_norms DIR saves the per-token L2 norms of every transformer block's output (DPTModel.block_norms, the capture step
 of experiments/block_norm_visualization.py without exporting a block tensor): <name>_blocknorms.npy, fp32 [L, h, w], or an object array of L maps
 when the blocks' grids differ (SwinV2).
+For one image or several, --mesh DIR saves the 3D viewer's "Save 3D Model" result (postprocess.pack_depth_u24_frames -> depth_frames_to_mesh ->
+mesh_io): <name>.glb with the photo as its texture, or with --mesh_obj <name>.obj plus <name>_image.png; --mesh_faces, --mesh_fov and --mesh_points
+are the viewer's mesh density, FOV and point mode.
 
   python tools/mdpt_run_image.py --synthetic vits --size 518 --fp32
   python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i image.npy -o depth_u8.npy
@@ -51,6 +54,11 @@ def main():
     ap.add_argument("--invert_mask", action="store_true", help="depth masking: keep the pixels outside the --mask range instead")
     ap.add_argument("--cutout", default=None, metavar="DIR", help="save every image's depth mask and BGRA cutout (.npy) at its own size into DIR")
     ap.add_argument("--block_norms", default=None, metavar="DIR", help="save every image's per-block token norm maps (.npy) into DIR")
+    ap.add_argument("--mesh", default=None, metavar="DIR", help="save every image's textured mesh (.glb) into DIR")
+    ap.add_argument("--mesh_faces", type=float, default=None, metavar="N", help="mesh: target number of faces (default: the viewer's 312500)")
+    ap.add_argument("--mesh_fov", type=float, default=None, metavar="DEG", help="mesh: field of view in degrees (default: the viewer's 50)")
+    ap.add_argument("--mesh_obj", action="store_true", help="mesh: write <name>.obj and <name>_image.png instead of <name>.glb")
+    ap.add_argument("--mesh_points", action="store_true", help="mesh: a point cloud (one vertex per face) instead of triangles")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mdpt_run_image needs an MI355X: no GPU visible (there is no CPU fallback)")
@@ -65,7 +73,7 @@ def main():
         cfg, model = make_depthanythingv2_dpt_from_original_state_dict(make_synthetic_original_state_dict(args.synthetic, 0))
     model.to("cuda", torch.float32 if args.fp32 else torch.bfloat16)
     if args.image_path and len(args.image_path) > 1:
-        return run_images(model, args, t0)
+        return run_images(model, args, t0, bool(cfg.get("is_metric", False)))
     if args.image_path:
         img = np.load(args.image_path[0])
     else:
@@ -92,6 +100,7 @@ def main():
         print("saved", args.u24)
     save_cutouts(args, args.image_path or ["synthetic.npy"], [img], [depth])
     save_block_norms(model, args, args.image_path or ["synthetic.npy"], [img])
+    save_meshes(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
 
 
 def save_cutouts(args, paths, images, depths):
@@ -106,6 +115,31 @@ def save_cutouts(args, paths, images, depths):
         np.save(stem + "_mask.npy", mask.cpu().numpy())
         np.save(stem + "_cutout.npy", cutout.cpu().numpy())
         print("saved", stem + "_mask.npy", stem + "_cutout.npy")
+
+
+def save_meshes(args, is_metric, paths, images, depths):
+    """--mesh: inference -> pack_depth_u24_frames -> depth_frames_to_mesh -> the writer, one mesh call per image (photo sizes set the grids)"""
+    if not args.mesh:
+        return
+    from muggled_dpt_amd import mesh_io
+    from muggled_dpt_amd import postprocess as pp
+    os.makedirs(args.mesh, exist_ok=True)
+    for path, img, depth in zip(paths, images, depths):
+        frames = pp.pack_depth_u24_frames(depth, is_metric=is_metric)
+        slabs = pp.depth_frames_to_mesh(frames, (img.shape[1], img.shape[0]), pp.MESH_FOV_DEG if args.mesh_fov is None else args.mesh_fov,
+                                        is_metric=is_metric, target_num_faces=pp.MESH_TARGET_FACES if args.mesh_faces is None else args.mesh_faces,
+                                        mode="points" if args.mesh_points else "triangles")
+        xyz, uv, faces, bounds = pp.mesh_views(*slabs)[0]
+        stem = os.path.join(args.mesh, os.path.splitext(os.path.basename(path))[0])
+        rgb = np.ascontiguousarray(img[:, :, ::-1])  # the photo, top row first: write_glb flips it for glTF's v axis, the .obj's PNG stays upright
+        if args.mesh_obj:
+            mesh_io.write_obj(stem + ".obj", xyz, uv, faces)
+            with open(stem + "_image.png", "wb") as fh:
+                fh.write(mesh_io.encode_png(rgb))
+            print("saved", stem + ".obj", stem + "_image.png", f"({xyz.shape[0]} vertices, {faces.shape[0]} faces)")
+        else:
+            mesh_io.write_glb(stem + ".glb", xyz, uv, faces, rgb, bounds)
+            print("saved", stem + ".glb", f"({xyz.shape[0]} vertices, {faces.shape[0]} faces)")
 
 
 def save_block_norms(model, args, paths, images):
@@ -134,7 +168,7 @@ def save_block_norms(model, args, paths, images):
                 print("saved", out)
 
 
-def run_images(model, args, t0):
+def run_images(model, args, t0, is_metric=False):
     """several images of any sizes: DPTModel.inference_images, then every 8-bit map back at its image's own size"""
     from muggled_dpt_amd.postprocess import depth_to_color_images
     images = [np.load(p) for p in args.image_path]
@@ -158,6 +192,7 @@ def run_images(model, args, t0):
             print("saved", out)
     save_cutouts(args, args.image_path, images, depths)
     save_block_norms(model, args, args.image_path, images)
+    save_meshes(args, is_metric, args.image_path, images, depths)
 
 
 if __name__ == "__main__":
