@@ -93,7 +93,8 @@ int mdpt_create(const mdpt_config* cfg, mdpt_handle** out) {
     h->cache_clear();
     h->side_stream = nullptr;
     h->ev_fork = h->ev_join = nullptr;
-    build_inventory(h);
+    const int rc = build_inventory(h);
+    if (rc != 0) { delete h; return rc; }
     *out = h;
     return 0;
 }
@@ -167,7 +168,7 @@ int mdpt_get_class_f8(const mdpt_handle* h, int32_t op_class, int32_t* on) {
     return 0;
 }
 
-static void rebuild_inventory_keeping_bindings(mdpt_handle* h);
+static int rebuild_inventory_keeping_bindings(mdpt_handle* h);
 
 int mdpt_set_class_passes(mdpt_handle* h, int32_t op_class, int32_t passes) {
     if (!h || op_class < 0 || op_class >= NCLS) return fail(MDPT_E_INVALID, "bad op class %d", op_class);
@@ -177,20 +178,19 @@ int mdpt_set_class_passes(mdpt_handle* h, int32_t op_class, int32_t passes) {
         return fail(MDPT_E_INVALID, "fp8 cross terms (MDPT_PASSES_2F8 / _3F8) exist for the reasm, fusion, fusion_in, fusion_proj and head classes, not for class %d", op_class);
     if (h->np[op_class] == passes) return 0;
     h->np[op_class] = passes;
-    rebuild_inventory_keeping_bindings(h);  // the packed-weight inventory depends on the pass counts (lo planes)
-    return 0;
+    return rebuild_inventory_keeping_bindings(h);  // the packed-weight inventory depends on the pass counts (lo planes)
 }
 
-static void rebuild_inventory_keeping_bindings(mdpt_handle* h) {
-    std::vector<WeightSpec> bound = h->specs;
-    h->specs.clear(); h->spec_index.clear(); h->mats.clear(); h->mat_index.clear(); h->vecs.clear(); h->vec_index.clear();
-    build_inventory(h);
+static int rebuild_inventory_keeping_bindings(mdpt_handle* h) {
+    const std::vector<WeightSpec> bound = h->specs;
+    h->finalized = false;
+    h->has_last = false;
+    CHK(build_inventory(h));
     for (const WeightSpec& b : bound) {
         auto it = h->spec_index.find(b.name);
         if (it != h->spec_index.end()) { h->specs[it->second].ptr = b.ptr; h->specs[it->second].dtype = b.dtype; }
     }
-    h->finalized = false;
-    h->has_last = false;
+    return 0;
 }
 
 int mdpt_set_weight_rounding_compensation(mdpt_handle* h, int32_t on) {
@@ -201,8 +201,7 @@ int mdpt_set_weight_rounding_compensation(mdpt_handle* h, int32_t on) {
     if (h->wrc_on == (on != 0) && (!on || h->wrc_mask == mask)) return 0;
     h->wrc_on = on != 0;
     if (on) h->wrc_mask = mask;
-    rebuild_inventory_keeping_bindings(h);
-    return 0;
+    return rebuild_inventory_keeping_bindings(h);
 }
 
 int mdpt_debug_set_operand_format(int32_t fp16) {
@@ -263,17 +262,9 @@ int mdpt_finalize(mdpt_handle* h, void* packed_dev, size_t bytes, void* stream) 
     for (Mat& m : h->mats) {
         m.hi = (op_t*)(base + m.off_hi);
         m.lo = m.off_lo == SIZE_MAX ? nullptr : (op_t*)(base + m.off_lo);
-        std::string src_name = m.src;
-        int src_ld = 0, src_col0 = 0;
-        const size_t kc = src_name.find("@kc32");
-        if (kc != std::string::npos) src_name = src_name.substr(0, kc);
-        const size_t at = src_name.find("@cls");
-        if (src_name.find(".readout_proj.1.weight") != std::string::npos) {  // [F, 2F] split into token / cls halves
-            src_ld = 2 * h->F;
-            if (at != std::string::npos) { src_col0 = h->F; src_name = src_name.substr(0, at); }
-        }
-        const WeightSpec& sp = h->specs[h->spec_index.at(src_name)];
-        const WeightSpec* rs = m.row_scale.empty() ? nullptr : &h->specs[h->spec_index.at(m.row_scale)];
+        const int src_ld = m.src_ld, src_col0 = m.src_col0;
+        const WeightSpec& sp = h->specs[m.spec];
+        const WeightSpec* rs = m.row_scale < 0 ? nullptr : &h->specs[m.row_scale];
         m.wscale = nullptr;
         if (m.off_scale != SIZE_MAX) {
             float* sc = (float*)(base + m.off_scale);
@@ -294,28 +285,19 @@ int mdpt_finalize(mdpt_handle* h, void* packed_dev, size_t bytes, void* stream) 
     }
     for (Vec& v : h->vecs) {
         v.ptr = (float*)(base + v.off);
-        const size_t at = v.src.find(".attn.qkv.bias@qv");
-        if (at != std::string::npos) {  // [q_bias (heads*d = F), zeros(F), v_bias (F)]: the k projection has no bias
-            const std::string blk = v.src.substr(0, at);
+        const WeightSpec& vs = h->specs[v.spec];
+        if (v.form == VEC_QV_BIAS) {  // [q_bias (heads*d = F), zeros(F), v_bias (F)]: the k projection has no bias
+            const WeightSpec& vb = h->specs[v.spec2];
             const int Fq = v.np / 3;
             CHK(hipMemsetAsync(v.ptr, 0, (size_t)v.np * 4, st));
-            const WeightSpec& qb = h->specs[h->spec_index.at(blk + ".attn.q_bias")];
-            const WeightSpec& vb = h->specs[h->spec_index.at(blk + ".attn.v_bias")];
-            CHK(OPLH(mdpt_launch_pad_copy_f32, qb.ptr, qb.dtype, v.ptr, Fq, Fq, st));
+            CHK(OPLH(mdpt_launch_pad_copy_f32, vs.ptr, vs.dtype, v.ptr, Fq, Fq, st));
             CHK(OPLH(mdpt_launch_pad_copy_f32, vb.ptr, vb.dtype, v.ptr + 2 * Fq, Fq, Fq, st));
-            continue;
+        } else if (v.form == VEC_SCALED) {  // bias * layer scale (see build_inventory)
+            const WeightSpec& sc = h->specs[v.spec2];
+            CHK(OPLH(mdpt_launch_pad_copy_f32, vs.ptr, vs.dtype, v.ptr, v.n, v.np, st, sc.ptr, sc.dtype));
+        } else {  // SwinV2's per-head logit scale is packed times log2(e): the window attention's scores are in log2 units (attention.hip LOG2)
+            CHK(OPLH(mdpt_launch_pad_copy_f32, vs.ptr, vs.dtype, v.ptr, v.n, v.np, st, nullptr, 0, v.form == VEC_LOG2E ? 1.4426950408889634f : 1.0f));
         }
-        const size_t ls = v.src.find("@ls");
-        if (ls != std::string::npos) {  // bias * layer scale (see build_inventory)
-            const WeightSpec& bs = h->specs[h->spec_index.at(v.src.substr(0, ls))];
-            const WeightSpec& sc = h->specs[h->spec_index.at(v.scale)];
-            CHK(OPLH(mdpt_launch_pad_copy_f32, bs.ptr, bs.dtype, v.ptr, v.n, v.np, st, sc.ptr, sc.dtype));
-            continue;
-        }
-        const WeightSpec& vs = h->specs[h->spec_index.at(v.src)];
-        // SwinV2's per-head logit scale is packed times log2(e): the window attention's scores are in log2 units (attention.hip LOG2)
-        const bool ls2 = v.src.size() > 17 && v.src.compare(v.src.size() - 17, 17, ".attn.logit_scale") == 0;
-        CHK(OPLH(mdpt_launch_pad_copy_f32, vs.ptr, vs.dtype, v.ptr, v.n, v.np, st, nullptr, 0, ls2 ? 1.4426950408889634f : 1.0f));
     }
     h->finalized = true;
     h->has_last = false;
@@ -636,8 +618,8 @@ int mdpt_patch_embed(mdpt_handle* h, const void* image_bchw, int32_t B, int32_t 
     const int Np = (H / h->P) * (W / h->P);
     Planes im = c.pl(c.p.im2col);
     CHK(OPLC(mdpt_launch_patchify, image_bchw, MDPT_DTYPE_F32, im.hi, im.lo, B, H, W, h->P, h->Kpatch, c.s));
-    GemmParams g = base_params(c, h->M("patch_embed.proj.weight"), im, B * Np, h->Kpatch);
-    g.bias = h->V("patch_embed.proj.bias");
+    GemmParams g = base_params(c, h->M(h->w.patch), im, B * Np, h->Kpatch);
+    g.bias = h->V(h->w.patch_b);
     g.out_f32 = (float*)tokens_bnf; g.ldc = h->F;
     CHK(OPLC(mdpt_launch_gemm, g, c.s));
     h->has_last = false;
@@ -677,7 +659,7 @@ static int encoder_with_dumps(mdpt_handle* h, const void* tokens_bnf, int32_t B,
     } else {
         CHK(run_pos(c));
     }
-    CHK(OPLC(mdpt_launch_init_tokens, c.at<float>(c.p.resid), h->V("imgencoder.cls_token"), is_beit(h) ? nullptr : h->V("imgencoder.posenc.cls_embedding"),
+    CHK(OPLC(mdpt_launch_init_tokens, c.at<float>(c.p.resid), h->V(h->w.cls_token), is_beit(h) ? nullptr : h->V(h->w.pos_cls),
                                 B, c.p.N, c.p.npad, h->F, c.s));
     CHK(OPLC(mdpt_launch_tokens_to_resid, (const float*)tokens_bnf, c.at<float>(c.p.pos), c.at<float>(c.p.resid), B, c.p.Np, c.p.npad, h->F, c.s));
     CHK(run_encoder(c, stage_out));
@@ -829,9 +811,7 @@ int mdpt_fusion_block(mdpt_handle* h, int32_t index, const void* reasm_in, const
     CHK(make_ctx(h, B, gh * h->Pv, gw * h->Pv, workspace, workspace_bytes, stream, &c));
     const Plan& p = c.p;
     const int i = index;
-    char pb[64];
-    snprintf(pb, sizeof(pb), "fusion.blocks.%d", i);
-    const std::string blk = pb;
+    const auto& fw = h->w.fusion[i];
     const size_t elems = (size_t)B * sh * sw * h->Cp;
     Planes rb = c.pl(p.r_bf[i]);
     CHK(OPLC(mdpt_launch_nchw_to_nhwc, (const float*)reasm_in, c.at<float>(p.r_f32[i]), rb.hi, rb.lo, 1, B, sh, sw, h->C, h->Cp, c.s, rb.lo ? rb.f8 : 0, rb.f8_a8));
@@ -843,18 +823,18 @@ int mdpt_fusion_block(mdpt_handle* h, int32_t index, const void* reasm_in, const
         CHK(OPLC(mdpt_launch_nchw_to_nhwc, (const float*)prior_in, skip, nullptr, nullptr, 0, B, sh, sw, h->C, h->Cp, c.s));
         CHK(OPLC(mdpt_launch_add_f32, skip, c.at<float>(p.r_f32[i]), elems, c.s));
         Planes a1 = c.pl(p.a1[i]);
-        CHK(rcu_conv(c, blk + ".conv_reassembly." + rcu_seq(h) + ".1", rb, sh, sw, nullptr, nullptr, 0, 0, nullptr, a1, 1));
+        CHK(rcu_conv(c, fw.rcu[0][0], rb, sh, sw, nullptr, nullptr, 0, 0, nullptr, a1, 1));
         x_bf = c.pl(p.x_bf[i]);
-        CHK(rcu_conv(c, blk + ".conv_reassembly." + rcu_seq(h) + ".3", a1, sh, sw, skip, nullptr, 0, 0, c.at<float>(p.x_f32[i]), x_bf, 1));
+        CHK(rcu_conv(c, fw.rcu[0][1], a1, sh, sw, skip, nullptr, 0, 0, c.at<float>(p.x_f32[i]), x_bf, 1));
         x_f32 = c.at<float>(p.x_f32[i]);
     }
     Planes b1 = c.pl(p.b1[i]), b2 = c.pl(p.b2[i]);
-    CHK(rcu_conv(c, blk + "." + proj_seq(h) + ".0." + rcu_seq(h) + ".1", x_bf, sh, sw, nullptr, nullptr, 0, 0, nullptr, b1, 1));
-    CHK(rcu_conv(c, blk + "." + proj_seq(h) + ".0." + rcu_seq(h) + ".3", b1, sh, sw, x_f32, nullptr, 0, 0, nullptr, b2, 0));
+    CHK(rcu_conv(c, fw.rcu[1][0], x_bf, sh, sw, nullptr, nullptr, 0, 0, nullptr, b1, 1));
+    CHK(rcu_conv(c, fw.rcu[1][1], b1, sh, sw, x_f32, nullptr, 0, 0, nullptr, b2, 0));
     const bool to_head16 = i == 0 && head_upsamples_bf16(h);  // the last block's output is the head's input: same 16-bit map as the fused path
     {
-        GemmParams g = base_params(c, h->M(blk + "." + proj_seq(h) + ".2.weight"), b2, B * sh * sw, h->Cp);
-        g.bias = h->V(blk + "." + proj_seq(h) + ".2.bias");
+        GemmParams g = base_params(c, h->M(fw.proj), b2, B * sh * sw, h->Cp);
+        g.bias = h->V(fw.proj_b);
         if (to_head16) g.out_hi = c.at<op_t>(p.flo[0]);
         else g.out_f32 = c.at<float>(p.flo[i]);
         g.ldc = h->Cp;

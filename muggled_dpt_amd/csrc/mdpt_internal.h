@@ -93,12 +93,11 @@ enum { CLS_PATCH = MDPT_CLASS_PATCH, CLS_QKV = MDPT_CLASS_QKV, CLS_ATTN = MDPT_C
        CLS_FC2 = MDPT_CLASS_FC2, CLS_REASM = MDPT_CLASS_REASM, CLS_FUSION = MDPT_CLASS_FUSION, CLS_HEAD = MDPT_CLASS_HEAD,
        CLS_FUSION_IN = MDPT_CLASS_FUSION_IN, CLS_HEAD_TAIL = MDPT_CLASS_HEAD_TAIL, CLS_FUSION_PROJ = MDPT_CLASS_FUSION_PROJ, NCLS = MDPT_NUM_CLASSES };
 
-int mat_class(const std::string& src);
-
 struct Mat {  // packed operand panel [Np][Kp]
-    std::string src;
     int cls;  // CLS_*
-    std::string row_scale;  // name of a per-output-feature fp32 parameter folded into the rows at pack time ("" = none)
+    // pack-time form (mdpt_finalize): source parameter (index into specs), the column window of it that is packed (src_ld = its row length,
+    // 0 = the whole [N][K] parameter) and a per-output-feature fp32 parameter folded into the rows (spec index, -1 = none)
+    int spec, src_ld, src_col0, row_scale;
     int kind, N, K, Np, Kp, ksz;
     size_t off_hi, off_lo;
     op_t* hi;
@@ -111,12 +110,42 @@ struct Mat {  // packed operand panel [Np][Kp]
     const uint8_t* w8; const uint8_t* wlo8; const uint8_t* s8; const uint8_t* slo8;
 };
 
+// pack-time form of a Vec: a copy of parameter `spec`; spec * spec2 element-wise (a bias times its LayerScale); [spec (q_bias), zeros, spec2 (v_bias)]
+// (BEiT / SwinV2: the k projection has no bias); spec * log2(e) (SwinV2's logit scale: the window attention's scores are in log2 units)
+enum VecForm { VEC_COPY, VEC_SCALED, VEC_QV_BIAS, VEC_LOG2E };
+
 struct Vec {  // packed fp32 vector (zero padded)
-    std::string src;
-    std::string scale;  // name of a parameter multiplied in element-wise at pack time ("" = none); src then carries an "@..." suffix
+    int form, spec, spec2;  // VecForm and its source parameters (indices into specs, -1 = none)
     int n, np;
     size_t off;
     float* ptr;
+};
+
+// Typed references to the packed matrices / vectors of a handle: indices into mdpt_handle::mats / ::vecs, handed out by add_mat / add_vec while
+// the inventory is built - the only place a parameter is spelled as a string. They are rebuilt with the inventory (build_inventory), stay valid
+// across mdpt_finalize (which fills Mat::hi ... Vec::ptr in place), and check_weight_refs() reports one a stage driver needs and the inventory
+// did not create. -1 = the family has no such parameter.
+struct MatRef { int i = -1; };
+struct VecRef { int i = -1; };
+
+struct BlockRefs {  // one transformer block: encoder block b of ViT / BEiT, the SwinV2 blocks in stage-major order
+    VecRef ln1_w, ln1_b, ln2_w, ln2_b;
+    MatRef qkv, proj, fc1, fc2;  // (fc1 / fc2: ViT-G's inner_linear_doubled / outer_linear)
+    VecRef qkv_b, proj_b, fc1_b, fc2_b;
+    VecRef relpos_lut;                           // BEiT
+    VecRef logit_scale, cpb_w1, cpb_b1, cpb_w2;  // SwinV2: per-head logit scale, position-bias MLP
+};
+struct RcuRefs { MatRef w; VecRef b; };  // one 3x3 conv of a residual conv unit
+struct WeightRefs {
+    MatRef patch;
+    VecRef patch_b, patch_ln_w, patch_ln_b;  // (the LayerNorm: SwinV2)
+    VecRef cls_token, pos_cls, pos_patch, outnorm_w, outnorm_b;
+    std::vector<BlockRefs> blocks;
+    struct { MatRef reduction; VecRef norm_w, norm_b; } merge[3];  // SwinV2 patch merge behind stage s
+    struct { MatRef readout_tok, readout_cls, resample0, resample1, fuse_proj; VecRef readout_b, resample0_b, resample1_b; } reasm[4];
+    // rcu[u][k]: unit u = 0 conv_reassembly (blocks 0..2), 1 the projection path's; its first / second conv (the reference's ".1" / ".3")
+    struct { RcuRefs rcu[2][2]; MatRef proj; VecRef proj_b; } fusion[4];
+    struct { MatRef conv1, proj0, proj0_kc32; VecRef conv1_b, proj0_b, proj2_w, proj2_b; } head;  // proj0_kc32: LDS image of proj0 (fused tail)
 };
 
 struct Planes {
@@ -186,9 +215,8 @@ struct mdpt_handle {
     std::vector<WeightSpec> specs;
     std::map<std::string, int> spec_index;
     std::vector<Mat> mats;
-    std::map<std::string, int> mat_index;
     std::vector<Vec> vecs;
-    std::map<std::string, int> vec_index;
+    WeightRefs w;
     size_t packed_total;
     size_t zero_off;
     op_t* zero_page;
@@ -235,7 +263,7 @@ struct mdpt_handle {
         if (ev_join) hipEventDestroy(ev_join);
     }
 
-    void add_spec(const std::string& name, std::initializer_list<int64_t> shape) {
+    int add_spec(const std::string& name, std::initializer_list<int64_t> shape) {
         WeightSpec s;
         s.name = name;
         s.ndim = (int)shape.size();
@@ -246,11 +274,12 @@ struct mdpt_handle {
         s.dtype = MDPT_DTYPE_F32;
         spec_index[name] = (int)specs.size();
         specs.push_back(s);
+        return (int)specs.size() - 1;
     }
-    void add_mat(const std::string& src, int kind, int N, int K, int Np, int Kp, int ksz) {
+    MatRef add_mat(int spec, int cls, int kind, int N, int K, int Np, int Kp, int ksz, int src_ld = 0, int src_col0 = 0) {
         Mat m;
-        m.src = src; m.kind = kind; m.N = N; m.K = K; m.Np = Np; m.Kp = Kp; m.ksz = ksz;
-        m.cls = mat_class(src);
+        m.spec = spec; m.src_ld = src_ld; m.src_col0 = src_col0; m.row_scale = -1;
+        m.cls = cls; m.kind = kind; m.N = N; m.K = K; m.Np = Np; m.Kp = Kp; m.ksz = ksz;
         m.off_hi = packed_total;
         packed_total += rup256((size_t)Np * Kp * 2);
         m.off_lo = SIZE_MAX;
@@ -265,20 +294,20 @@ struct mdpt_handle {
             if (terms(m.cls) == 3) { m.off_wlo8 = packed_total; packed_total += rup256((size_t)Np * Kp); }
             m.off_s8 = packed_total; packed_total += rup256((size_t)Np * 2);
         }
-        mat_index[src] = (int)mats.size();
         mats.push_back(m);
+        return MatRef{(int)mats.size() - 1};
     }
-    void add_vec(const std::string& src, int n, int np) {
+    VecRef add_vec(int spec, int n, int np, int form = VEC_COPY, int spec2 = -1) {
         Vec v;
-        v.src = src; v.n = n; v.np = np;
+        v.form = form; v.spec = spec; v.spec2 = spec2; v.n = n; v.np = np;
         v.off = packed_total;
         packed_total += rup256((size_t)np * 4);
         v.ptr = nullptr;
-        vec_index[src] = (int)vecs.size();
         vecs.push_back(v);
+        return VecRef{(int)vecs.size() - 1};
     }
-    const Mat& M(const std::string& name) const { return mats[mat_index.at(name)]; }
-    const float* V(const std::string& name) const { return vecs[vec_index.at(name)].ptr; }
+    const Mat& M(MatRef r) const { return mats[r.i]; }
+    const float* V(VecRef r) const { return vecs[r.i].ptr; }
 };
 
 namespace mdpt {
@@ -336,19 +365,14 @@ struct SwinStageGeom {
 };
 
 // ---- mdpt_inventory.cpp
-std::string blk_name(const mdpt_handle* h, int block);
 inline bool is_beit(const mdpt_handle* h) { return h->cfg.family == MDPT_FAMILY_BEIT; }
 inline bool is_midas(const mdpt_handle* h) { return h->cfg.family == MDPT_FAMILY_BEIT || h->cfg.family == MDPT_FAMILY_SWINV2; }
-// reference attribute names differ between the families (v2: fusion_model.py:100,138 / v31_beit, v31_swinv2 fusion_model.py)
-inline const char* rcu_seq(const mdpt_handle* h) { return is_midas(h) ? "conv_seq" : "resconv_seq"; }
-inline const char* proj_seq(const mdpt_handle* h) { return is_midas(h) ? "proj_seq" : "scale_proj_seq"; }
 void compute_f8ok(mdpt_handle* h);
-int build_inventory(mdpt_handle* h);
+int build_inventory(mdpt_handle* h);  // (re)builds specs, mats, vecs and the references from the configuration and the pass counts; bindings are lost
 int make_plan(const mdpt_handle* h, int B, int H, int W, Plan* pl);
 int check_ws(const mdpt_handle* h, const Plan& p, const void* ws, size_t bytes);
 int make_ctx(mdpt_handle* h, int B, int H, int W, void* ws, size_t ws_bytes, void* stream, Ctx* c);
 int swin_geom(const mdpt_handle* h, int g0h, int g0w, int s, SwinStageGeom* g);
-std::string swin_blk(int s, int l);
 
 // ---- mdpt_stages.cpp
 GemmParams base_params(const Ctx& c, const Mat& w, Planes a, int M, int lda);
@@ -361,7 +385,7 @@ bool fc2_ksplit_fits(int rows, int F);  // batch small enough for the K-split fo
 int run_encoder(const Ctx& c, void* const taps_f32[4]);
 int run_reassemble(const Ctx& c);
 int run_reassemble_stage(const Ctx& c, int i);
-int rcu_conv(const Ctx& c, const std::string& wname, Planes in, int sh, int sw, const float* skip, const float* up_src, int Hu, int Wu,
+int rcu_conv(const Ctx& c, const RcuRefs& w, Planes in, int sh, int sw, const float* skip, const float* up_src, int Hu, int Wu,
              float* out_f32, Planes out, int relu_bf16);
 bool head_upsamples_bf16(const mdpt_handle* h);
 bool head_tail_fused(const mdpt_handle* h);

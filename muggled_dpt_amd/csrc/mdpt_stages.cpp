@@ -39,7 +39,7 @@ void as_conv(GemmParams& g, int Hi, int Wi, int Cin, int Ho, int Wo, int stride)
 // ---- stage: patch embed (fused form: writes the residual stream incl. position embedding)
 int run_pos(const Ctx& c) {
     const mdpt_handle* h = c.h;
-    return OPLC(mdpt_launch_posembed, h->V("imgencoder.posenc.base_patch_embedding"), c.at<float>(c.p.pos), h->cfg.base_patch_grid_h,
+    return OPLC(mdpt_launch_posembed, h->V(h->w.pos_patch), c.at<float>(c.p.pos), h->cfg.base_patch_grid_h,
                                 h->cfg.base_patch_grid_w, c.p.gh, c.p.gw, h->F, c.s);
 }
 
@@ -75,11 +75,11 @@ int run_patch_embed_fused(const Ctx& c, const void* image, int image_dtype) {
     CHK(run_patchify(c, image, image_dtype, im, p.H, p.W));
     const bool beit = is_beit(h);
     if (!beit && !c.consts_cached) CHK(run_pos(c));
-    CHK(OPLC(mdpt_launch_init_tokens, c.at<float>(p.resid), h->V("imgencoder.cls_token"), beit ? nullptr : h->V("imgencoder.posenc.cls_embedding"),
+    CHK(OPLC(mdpt_launch_init_tokens, c.at<float>(p.resid), h->V(h->w.cls_token), beit ? nullptr : h->V(h->w.pos_cls),
                                 p.B, p.N, p.npad, h->F, c.s));
-    GemmParams g = base_params(c, h->M("patch_embed.proj.weight"), im, p.B * p.Np, h->Kpatch);
+    GemmParams g = base_params(c, h->M(h->w.patch), im, p.B * p.Np, h->Kpatch);
     g.ekind = MDPT_E_PATCH;
-    g.bias = h->V("patch_embed.proj.bias");
+    g.bias = h->V(h->w.patch_b);
     g.pos = beit ? nullptr : c.at<float>(p.pos);
     g.out_f32 = c.at<float>(p.resid);
     g.tok_np = p.Np; g.npad = p.npad; g.ldc = h->F;
@@ -138,7 +138,7 @@ int run_encoder(const Ctx& c, void* const taps_f32[4]) {
     if (relpos_batched && !c.consts_cached) {  // every block's relative-position table, resized to the current grid: one launch per forward (per grid with the cache)
         BeitRelposBatch rb;
         memset(&rb, 0, sizeof(rb));
-        for (int b = 0; b < h->nblocks; ++b) rb.ref[b] = h->V(blk_name(h, b) + ".attn.relpos_enc.ref_bias_lut");
+        for (int b = 0; b < h->nblocks; ++b) rb.ref[b] = h->V(h->w.blocks[b].relpos_lut);
         rb.ext0 = c.at<float>(p.relpos_lut); rb.ext_stride = relpos_stride;
         rb.tq = c.at<int>(p.relpos_tq); rb.tk = c.at<int>(p.relpos_tk);
         rb.n = h->nblocks; rb.heads = h->heads; rb.Gh = h->cfg.base_patch_grid_h; rb.Gw = h->cfg.base_patch_grid_w;
@@ -164,17 +164,17 @@ int run_encoder(const Ctx& c, void* const taps_f32[4]) {
         return true;
     };
     for (int b = 0; b < h->nblocks; ++b) {
-        const std::string n = blk_name(h, b);
-        CHK(layernorm(h->V(n + ".norm1.weight"), h->V(n + ".norm1.bias"), xn_qkv.hi, xn_qkv.lo, nullptr));
+        const BlockRefs& w = h->w.blocks[b];
+        CHK(layernorm(h->V(w.ln1_w), h->V(w.ln1_b), xn_qkv.hi, xn_qkv.lo, nullptr));
         DBG_STOP(0);
         {
-            GemmParams g = base_params(c, h->M(n + ".attn.qkv.weight"), xn, rows, F);
+            GemmParams g = base_params(c, h->M(w.qkv), xn, rows, F);
             g.M_alg = p.B * p.N;
             g.ekind = MDPT_E_QKV;
-            g.bias = h->V(is_beit(h) ? n + ".attn.qkv.bias@qv" : n + ".attn.qkv.bias");
+            g.bias = h->V(w.qkv_b);  // (BEiT: [q_bias, 0, v_bias], assembled at pack time)
             g.q_hi = q.hi; g.q_lo = q.lo; g.k_hi = k.hi; g.k_lo = k.lo; g.vt_hi = vt.hi; g.vt_lo = vt.lo;
             g.F = F; g.heads = h->heads; g.npad = p.npad; g.npadv = p.npadv; g.qscale = 0.125f;
-            CHK(wrc_bias(c, g, h->M(n + ".attn.qkv.weight"), g.bias));
+            CHK(wrc_bias(c, g, h->M(w.qkv), g.bias));
             CHK(OPLC(mdpt_launch_gemm, g, c.s));
         }
         DBG_STOP(1);
@@ -188,7 +188,7 @@ int run_encoder(const Ctx& c, void* const taps_f32[4]) {
             if (is_beit(h)) {
                 float* lut_b = c.at<float>(p.relpos_lut) + (relpos_batched ? (size_t)b * relpos_stride : 0);
                 if (!relpos_batched)  // more than 32 blocks: this layer's table on its own (tiny kernel)
-                    CHK(OPLC(mdpt_launch_beit_relpos, h->V(n + ".attn.relpos_enc.ref_bias_lut"), lut_b, c.at<int>(p.relpos_tq), c.at<int>(p.relpos_tk),
+                    CHK(OPLC(mdpt_launch_beit_relpos, h->V(w.relpos_lut), lut_b, c.at<int>(p.relpos_tq), c.at<int>(p.relpos_tk),
                                                 h->heads, h->cfg.base_patch_grid_h, h->cfg.base_patch_grid_w, p.gh, p.gw, p.N, p.npadv, c.s));
                 a.bias_lut = lut_b; a.bias_elen = mdpt_beit_relpos_elen(p.gh, p.gw);
                 a.tq = c.at<int>(p.relpos_tq); a.tk = c.at<int>(p.relpos_tk);
@@ -198,47 +198,45 @@ int run_encoder(const Ctx& c, void* const taps_f32[4]) {
         }
         DBG_STOP(2);
         {
-            GemmParams g = base_params(c, h->M(n + ".attn.proj.weight"), att, rows, F);
+            GemmParams g = base_params(c, h->M(w.proj), att, rows, F);
             g.M_alg = p.B * p.N;
-            g.bias = h->V(n + ".attn.proj.bias@ls");  // layer scale folded into W and the bias at pack time
+            g.bias = h->V(w.proj_b);  // layer scale folded into W and the bias at pack time
             g.acc_init = 1;
             g.resid = resid; g.out_f32 = resid; g.ldr = F; g.ldc = F;
-            CHK(wrc_bias(c, g, h->M(n + ".attn.proj.weight"), g.bias));
+            CHK(wrc_bias(c, g, h->M(w.proj), g.bias));
             if (ksplit_setup(g)) { pending = g.ks_part; npending = g.ksplit - 1; }  // LN2 is the next reader of the residual stream
             CHK(OPLC(mdpt_launch_gemm, g, c.s));
         }
         DBG_STOP(3);
-        CHK(layernorm(h->V(n + ".norm2.weight"), h->V(n + ".norm2.bias"), xn_fc1.hi, xn_fc1.lo, nullptr));
+        CHK(layernorm(h->V(w.ln2_w), h->V(w.ln2_b), xn_fc1.hi, xn_fc1.lo, nullptr));
         DBG_STOP(4);
         if (h->gh_hidden) {  // ViT-G: (a | b) = x W12^T + b12 ; hidden = silu(a) * b
-            GemmParams g = base_params(c, h->M(n + ".mlp.inner_linear_doubled.weight"), xn, rows, F);
+            GemmParams g = base_params(c, h->M(w.fc1), xn, rows, F);
             g.M_alg = p.B * p.N;
-            g.bias = h->V(n + ".mlp.inner_linear_doubled.bias");
+            g.bias = h->V(w.fc1_b);
             g.out_f32 = c.at<float>(p.swi); g.ldc = 2 * h->gh_hidden;
-            CHK(wrc_bias(c, g, h->M(n + ".mlp.inner_linear_doubled.weight"), g.bias));
+            CHK(wrc_bias(c, g, h->M(w.fc1), g.bias));
             CHK(OPLC(mdpt_launch_gemm, g, c.s));
             CHK(OPLC(mdpt_launch_swiglu, c.at<float>(p.swi), hb.hi, hb.lo, (size_t)rows, h->gh_hidden, h->gh_hidden_p, c.s));
         } else {
-            GemmParams g = base_params(c, h->M(n + ".mlp.layers.0.weight"), xn, rows, F);
+            GemmParams g = base_params(c, h->M(w.fc1), xn, rows, F);
             g.M_alg = p.B * p.N;
-            g.bias = h->V(n + ".mlp.layers.0.bias");
+            g.bias = h->V(w.fc1_b);
             g.act = MDPT_ACT_GELU;
             g.out_hi = hb.hi; g.out_lo = hb.lo; g.ldc = 4 * F;
-            CHK(wrc_bias(c, g, h->M(n + ".mlp.layers.0.weight"), g.bias));
+            CHK(wrc_bias(c, g, h->M(w.fc1), g.bias));
             CHK(OPLC(mdpt_launch_gemm, g, c.s));
         }
         DBG_STOP(5);
         const bool v1 = h->cfg.family == MDPT_FAMILY_DAV1;
         const bool is_tap = v1 ? b >= h->nblocks - 4 : (b + 1) % h->bps == 0;
         {
-            const bool giant = h->gh_hidden != 0;
-            GemmParams g = base_params(c, h->M(giant ? n + ".mlp.outer_linear.weight" : n + ".mlp.layers.2.weight"), hb, rows,
-                                       giant ? h->gh_hidden_p : 4 * F);
+            GemmParams g = base_params(c, h->M(w.fc2), hb, rows, h->gh_hidden ? h->gh_hidden_p : 4 * F);
             g.M_alg = p.B * p.N;
-            g.bias = h->V(giant ? n + ".mlp.outer_linear.bias@ls" : n + ".mlp.layers.2.bias@ls");
+            g.bias = h->V(w.fc2_b);
             g.acc_init = 1;
             g.resid = resid; g.out_f32 = resid; g.ldr = F; g.ldc = F;
-            CHK(wrc_bias(c, g, h->M(giant ? n + ".mlp.outer_linear.weight" : n + ".mlp.layers.2.weight"), g.bias));
+            CHK(wrc_bias(c, g, h->M(w.fc2), g.bias));
             // a LayerNorm must be the next reader of the residual stream: not when this block's raw output is exported (block hooks, block norms, BEiT's
             // un-normed taps, a debug stop) or nothing follows (BEiT's last block is a tap)
             if (!(c.block_dump && c.block_dump[b]) && !c.norm_wanted(b) && !(is_beit(h) && is_tap) && (b + 1 < h->nblocks || is_tap) && ksplit_setup(g)) {
@@ -260,7 +258,7 @@ int run_encoder(const Ctx& c, void* const taps_f32[4]) {
                 CHK(OPLC(mdpt_launch_tokens_import, resid, tp.hi, tp.lo, p.B, p.npad, p.npad, F, c.s, tp.lo ? tp.f8 : 0, tp.f8_a8));
                 if (taps_f32) CHK(OPLC(mdpt_launch_tokens_export, nullptr, nullptr, resid, (float*)taps_f32[st], p.B, p.N, p.npad, F, 0, c.s));
             } else {
-                CHK(layernorm(h->V("imgencoder.outnorm.weight"), h->V("imgencoder.outnorm.bias"), tp.hi, tp.lo, f32, tp.lo ? tp.f8 : 0, tp.f8_a8));
+                CHK(layernorm(h->V(h->w.outnorm_w), h->V(h->w.outnorm_b), tp.hi, tp.lo, f32, tp.lo ? tp.f8 : 0, tp.f8_a8));
                 if (taps_f32)
                     CHK(OPLC(mdpt_launch_tokens_export, nullptr, nullptr, f32, (float*)taps_f32[st], p.B, p.N, p.npad, F, 0, c.s));
             }
@@ -325,21 +323,21 @@ int run_reassemble_stage(const Ctx& c, int i) {
     const Plan& p = c.p;
     const int F = h->F, gh = p.gh, gw = p.gw;
     {
-        const std::string n = std::string("reassemble.") + kStageNames[i];
+        const auto& w = h->w.reasm[i];
         const int hp = h->hidp[i];
         Planes tp = c.pl(p.tap[i]), t = c.pl(p.t[i]);
         bool tokens_mode = true;
         if (is_beit(h)) {
             // readout projection: GELU(W [tok ; cls] + b) = GELU(W_tok tok + (W_cls cls + b)); the cls term is one row per image
             {
-                GemmParams g = base_params(c, h->M(n + ".readout_proj.1.weight@cls"), tp, p.B, p.npad * F);  // row b = cls token of image b
-                g.bias = h->V(n + ".readout_proj.1.bias");
+                GemmParams g = base_params(c, h->M(w.readout_cls), tp, p.B, p.npad * F);  // row b = cls token of image b
+                g.bias = h->V(w.readout_b);
                 g.out_f32 = c.at<float>(p.cbuf); g.ldc = F;
                 CHK(OPLC(mdpt_launch_gemm, g, c.s));
             }
             Planes tr = c.pl(p.tokr);
             {
-                GemmParams g = base_params(c, h->M(n + ".readout_proj.1.weight"), tp, p.B * p.Np, F);
+                GemmParams g = base_params(c, h->M(w.readout_tok), tp, p.B * p.Np, F);
                 g.amode = MDPT_A_TOKENS; g.tok_np = p.Np; g.tok_stride = p.npad;
                 g.bias = c.at<float>(p.cbuf); g.bias_img_stride = F; g.bias_img_rows = p.Np;
                 g.act = MDPT_ACT_GELU;
@@ -350,9 +348,9 @@ int run_reassemble_stage(const Ctx& c, int i) {
             tokens_mode = false;
         }
         {   // 1x1 conv on the patch tokens (cls row skipped by the A-row generator)
-            GemmParams g = base_params(c, h->M(n + ".resample.0.weight"), tp, p.B * p.Np, F);
+            GemmParams g = base_params(c, h->M(w.resample0), tp, p.B * p.Np, F);
             if (tokens_mode) { g.amode = MDPT_A_TOKENS; g.tok_np = p.Np; g.tok_stride = p.npad; }
-            g.bias = h->V(n + ".resample.0.bias");
+            g.bias = h->V(w.resample0_b);
             out_planes(g, t); g.ldc = hp;
             CHK(OPLC(mdpt_launch_gemm, g, c.s));
         }
@@ -361,18 +359,18 @@ int run_reassemble_stage(const Ctx& c, int i) {
         if (i == 0 || i == 1) {  // ConvTranspose2d k == s: GEMM + depth-to-space
             const int kk = i == 0 ? 4 : 2;
             Planes u = c.pl(i == 0 ? p.u0 : p.u1);
-            GemmParams g = base_params(c, h->M(n + ".resample.1.weight"), t, p.B * p.Np, hp);
+            GemmParams g = base_params(c, h->M(w.resample1), t, p.B * p.Np, hp);
             g.ekind = MDPT_E_D2S;
-            g.bias = h->V(n + ".resample.1.bias");
+            g.bias = h->V(w.resample1_b);
             g.Ho = gh; g.Wo = gw; g.d2s_k = kk; g.d2s_cout = hp;
             out_planes(g, u);
             CHK(OPLC(mdpt_launch_gemm, g, c.s));
             src = u; sh = gh * kk; sw = gw * kk;
         } else if (i == 3) {  // 3x3 stride-2
             Planes d = c.pl(p.d3);
-            GemmParams g = base_params(c, h->M(n + ".resample.1.weight"), t, p.B * (gh / 2) * (gw / 2), hp);
+            GemmParams g = base_params(c, h->M(w.resample1), t, p.B * (gh / 2) * (gw / 2), hp);
             as_conv(g, gh, gw, hp, gh / 2, gw / 2, 2);
-            g.bias = h->V(n + ".resample.1.bias");
+            g.bias = h->V(w.resample1_b);
             out_planes(g, d); g.ldc = hp;
             bool split_done = false;
             CHK(try_ksplit_conv(c, g, &split_done));
@@ -380,7 +378,7 @@ int run_reassemble_stage(const Ctx& c, int i) {
             src = d; sh = gh / 2; sw = gw / 2;
         }
         {   // 3x3 projection to the fusion width (no bias): fp32 copy (skip path) + ReLU'd bf16 (next conv input)
-            CHK(conv3_to_fusion(c, h->M(n + ".fuse_proj.weight"), src, hp, sh, sw, nullptr, nullptr, nullptr, 0, 0, c.at<float>(p.r_f32[i]),
+            CHK(conv3_to_fusion(c, h->M(w.fuse_proj), src, hp, sh, sw, nullptr, nullptr, nullptr, 0, 0, c.at<float>(p.r_f32[i]),
                                 c.pl(p.r_bf[i]), 1));
         }
     }
@@ -435,10 +433,10 @@ int conv3_to_fusion(const Ctx& c, const Mat& w, Planes in, int Cin, int sh, int 
 }
 
 // one 3x3 conv C->C of a residual conv unit at level `lv` (spatial sh x sw)
-int rcu_conv(const Ctx& c, const std::string& wname, Planes in, int sh, int sw, const float* skip, const float* up_src, int Hu, int Wu,
+int rcu_conv(const Ctx& c, const RcuRefs& w, Planes in, int sh, int sw, const float* skip, const float* up_src, int Hu, int Wu,
              float* out_f32, Planes out, int relu_bf16) {
     const mdpt_handle* h = c.h;
-    return conv3_to_fusion(c, h->M(wname + ".weight"), in, h->Cp, sh, sw, h->V(wname + ".bias"), skip, up_src, Hu, Wu, out_f32, out, relu_bf16);
+    return conv3_to_fusion(c, h->M(w.w), in, h->Cp, sh, sw, h->V(w.b), skip, up_src, Hu, Wu, out_f32, out, relu_bf16);
 }
 
 // ---- stage: fusion. Level index i: 3 = coarsest (gh/2), 0 = finest (4gh). Output: flo[0] (fp32, 4gh x 4gw, before the
@@ -457,9 +455,7 @@ int fusion_rcu_a_first(const Ctx& c, int i) {
     const mdpt_handle* h = c.h;
     const Plan& p = c.p;
     const int sh[4] = {4 * p.gh, 2 * p.gh, p.gh, p.gh / 2}, sw[4] = {4 * p.gw, 2 * p.gw, p.gw, p.gw / 2};
-    char pb[64];
-    snprintf(pb, sizeof(pb), "fusion.blocks.%d", i);
-    return rcu_conv(c, std::string(pb) + ".conv_reassembly." + rcu_seq(h) + ".1", c.pl(p.r_bf[i]), sh[i], sw[i], nullptr, nullptr, 0, 0, nullptr, c.pl(p.a1[i]), 1);
+    return rcu_conv(c, h->w.fusion[i].rcu[0][0], c.pl(p.r_bf[i]), sh[i], sw[i], nullptr, nullptr, 0, 0, nullptr, c.pl(p.a1[i]), 1);
 }
 
 int run_fusion(const Ctx& c, bool for_head) {
@@ -467,9 +463,7 @@ int run_fusion(const Ctx& c, bool for_head) {
     const Plan& p = c.p;
     const int sh[4] = {4 * p.gh, 2 * p.gh, p.gh, p.gh / 2}, sw[4] = {4 * p.gw, 2 * p.gw, p.gw, p.gw / 2};
     for (int i = 3; i >= 0; --i) {
-        char pb[64];
-        snprintf(pb, sizeof(pb), "fusion.blocks.%d", i);
-        const std::string blk = pb;
+        const auto& w = h->w.fusion[i];
         const float* x_f32;
         Planes x_bf;
         if (i == 3) {  // top-most block: no reassembly RCU, no prior (fusion_model.py:89-114)
@@ -480,17 +474,17 @@ int run_fusion(const Ctx& c, bool for_head) {
             Planes a1 = c.pl(p.a1[i]);
             if (!c.a1_done) CHK(fusion_rcu_a_first(c, i));
             x_bf = c.pl(p.x_bf[i]);
-            CHK(rcu_conv(c, blk + ".conv_reassembly." + rcu_seq(h) + ".3", a1, sh[i], sw[i], c.at<float>(p.r_f32[i]), c.at<float>(p.flo[i + 1]),
+            CHK(rcu_conv(c, w.rcu[0][1], a1, sh[i], sw[i], c.at<float>(p.r_f32[i]), c.at<float>(p.flo[i + 1]),
                          sh[i + 1], sw[i + 1], c.at<float>(p.x_f32[i]), x_bf, 1));
             x_f32 = c.at<float>(p.x_f32[i]);
         }
         Planes b1 = c.pl(p.b1[i]), b2 = c.pl(p.b2[i]);
-        CHK(rcu_conv(c, blk + "." + proj_seq(h) + ".0." + rcu_seq(h) + ".1", x_bf, sh[i], sw[i], nullptr, nullptr, 0, 0, nullptr, b1, 1));
-        CHK(rcu_conv(c, blk + "." + proj_seq(h) + ".0." + rcu_seq(h) + ".3", b1, sh[i], sw[i], x_f32, nullptr, 0, 0, nullptr, b2, 0));
+        CHK(rcu_conv(c, w.rcu[1][0], x_bf, sh[i], sw[i], nullptr, nullptr, 0, 0, nullptr, b1, 1));
+        CHK(rcu_conv(c, w.rcu[1][1], b1, sh[i], sw[i], x_f32, nullptr, 0, 0, nullptr, b2, 0));
         {   // 1x1 projection at LOW resolution; the x2 bilinear upsample commutes with it exactly (both linear, weights
             // sum to 1) and is applied by the consumer (next level's epilogue / final upsample kernel)
-            GemmParams g = base_params(c, h->M(blk + "." + proj_seq(h) + ".2.weight"), b2, p.B * sh[i] * sw[i], h->Cp);
-            g.bias = h->V(blk + "." + proj_seq(h) + ".2.bias");
+            GemmParams g = base_params(c, h->M(w.proj), b2, p.B * sh[i] * sw[i], h->Cp);
+            g.bias = h->V(w.proj_b);
             if (i == 0 && for_head && head_upsamples_bf16(h)) g.out_hi = c.at<op_t>(p.flo[0]);  // bf16 map in the fp32 map's buffer
             else g.out_f32 = c.at<float>(p.flo[i]);
             g.ldc = h->Cp;
@@ -513,8 +507,9 @@ int run_head(const Ctx& c, void* depth, int depth_dtype, bool from_flo0b) {
     const Plan& p = c.p;
     const int fh = 8 * p.gh, fw = 8 * p.gw;
     const int np1 = h->terms(CLS_HEAD);
-    const Mat& w1 = h->M("head.spatial_upsampler.0.weight");
-    const float* b1 = h->V("head.spatial_upsampler.0.bias");
+    const auto& w = h->w.head;
+    const Mat& w1 = h->M(w.conv1);
+    const float* b1 = h->V(w.conv1_b);
     const bool tail_fused = head_tail_fused(h) && mdpt_head_tail_scale_ok(fh, fw, p.H, p.W);
     const bool halo_ok = h->C2p == 128 && conv3h_shape_ok(h, fh, fw, h->Cp) && h->gemm_tile == MDPT_TILE_AUTO;
     const bool big = ((long)p.B * fh * fw + 255) / 256 >= conv3h_min_tiles(c);
@@ -569,8 +564,8 @@ int run_head(const Ctx& c, void* depth, int depth_dtype, bool from_flo0b) {
     if (tail_fused) {
         HeadTailParams t;
         memset(&t, 0, sizeof(t));
-        t.src = h1b; t.src_lo = h1b_lo; t.w_kc = h->M("head.proj_1ch.0.weight@kc32").hi;
-        t.bias = h->V("head.proj_1ch.0.bias"); t.head_w = h->V("head.proj_1ch.2.weight"); t.head_b = h->V("head.proj_1ch.2.bias");
+        t.src = h1b; t.src_lo = h1b_lo; t.w_kc = h->M(w.proj0_kc32).hi;
+        t.bias = h->V(w.proj0_b); t.head_w = h->V(w.proj2_w); t.head_b = h->V(w.proj2_b);
         t.out = depth; t.out_dtype = depth_dtype; t.sigmoid = h->cfg.is_metric;
         t.B = p.B; t.Hi = fh; t.Wi = fw; t.Ho = p.H; t.Wo = p.W;
         CHK(OPLC(mdpt_launch_head_tail, t, h->C2p, c.s));
@@ -579,12 +574,12 @@ int run_head(const Ctx& c, void* depth, int depth_dtype, bool from_flo0b) {
     Planes hu = c.pl(p.h1u);
     CHK(OPLC(mdpt_launch_upsample, h1f, hu.hi, hu.lo, nullptr, p.B, fh, fw, p.H, p.W, h->C2p, c.s));
     {
-        GemmParams g = base_params(c, h->M("head.proj_1ch.0.weight"), hu, p.B * p.H * p.W, h->C2p);
+        GemmParams g = base_params(c, h->M(w.proj0), hu, p.B * p.H * p.W, h->C2p);
         as_conv(g, p.H, p.W, h->C2p, p.H, p.W, 1);
         g.ekind = MDPT_E_HEAD;
-        g.bias = h->V("head.proj_1ch.0.bias");
-        g.head_w = h->V("head.proj_1ch.2.weight");
-        g.head_b = h->V("head.proj_1ch.2.bias");
+        g.bias = h->V(w.proj0_b);
+        g.head_w = h->V(w.proj2_w);
+        g.head_b = h->V(w.proj2_b);
         g.head_sigmoid = h->cfg.is_metric;
         g.head_out = depth; g.head_out_dtype = depth_dtype;
         CHK(OPLC(mdpt_launch_gemm, g, c.s));

@@ -40,74 +40,71 @@ int swin_geom(const mdpt_handle* h, int g0h, int g0w, int s, SwinStageGeom* g) {
     return 0;
 }
 
-std::string swin_blk(int s, int l) {
-    char buf[96];
-    snprintf(buf, sizeof(buf), "imgencoder.stages.%d.blocks.%d", s, l);
-    return buf;
-}
-
-
-int build_inventory_swin_encoder(mdpt_handle* h) {
-    h->add_spec("patch_embed.norm.weight", {h->F});
-    h->add_spec("patch_embed.norm.bias", {h->F});
-    h->add_vec("patch_embed.norm.weight", h->F, h->F);
-    h->add_vec("patch_embed.norm.bias", h->F, h->F);
+static void build_inventory_swin_encoder(mdpt_handle* h) {
+    WeightRefs& w = h->w;
+    const int s_ln_w = h->add_spec("patch_embed.norm.weight", {h->F});
+    const int s_ln_b = h->add_spec("patch_embed.norm.bias", {h->F});
+    w.patch_ln_w = h->add_vec(s_ln_w, h->F, h->F);
+    w.patch_ln_b = h->add_vec(s_ln_b, h->F, h->F);
     for (int s = 0; s < 4; ++s) {
         const int F = h->hid[s], H = h->sH[s];
         for (int l = 0; l < h->sL[s]; ++l) {
-            const std::string p = swin_blk(s, l);
-            h->add_spec(p + ".attn.q_bias", {1, H, 1, 32});
-            h->add_spec(p + ".attn.v_bias", {1, H, 1, 32});
-            h->add_spec(p + ".attn.qkv.weight", {3 * F, F});
-            h->add_spec(p + ".attn.logit_scale", {H, 1, 1});
-            h->add_spec(p + ".attn.relpos_enc.bias_mlp.0.weight", {kCpbHidden, 2});
-            h->add_spec(p + ".attn.relpos_enc.bias_mlp.0.bias", {kCpbHidden});
-            h->add_spec(p + ".attn.relpos_enc.bias_mlp.2.weight", {H, kCpbHidden});
-            h->add_spec(p + ".attn.proj.weight", {F, F});
-            h->add_spec(p + ".attn.proj.bias", {F});
-            h->add_spec(p + ".norm1.weight", {F});
-            h->add_spec(p + ".norm1.bias", {F});
-            h->add_spec(p + ".mlp.layers.0.weight", {4 * F, F});
-            h->add_spec(p + ".mlp.layers.0.bias", {4 * F});
-            h->add_spec(p + ".mlp.layers.2.weight", {F, 4 * F});
-            h->add_spec(p + ".mlp.layers.2.bias", {F});
-            h->add_spec(p + ".norm2.weight", {F});
-            h->add_spec(p + ".norm2.bias", {F});
-            h->add_mat(p + ".attn.qkv.weight", MDPT_PACK_LINEAR, 3 * F, F, 3 * F, rup(F, 64), 0);
-            h->add_mat(p + ".attn.proj.weight", MDPT_PACK_LINEAR, F, F, F, rup(F, 64), 0);
-            h->add_mat(p + ".mlp.layers.0.weight", MDPT_PACK_LINEAR, 4 * F, F, 4 * F, rup(F, 64), 0);
-            h->add_mat(p + ".mlp.layers.2.weight", MDPT_PACK_LINEAR, F, 4 * F, F, 4 * F, 0);
-            h->add_vec(p + ".attn.qkv.bias@qv", 0, 3 * F);
-            h->add_vec(p + ".attn.logit_scale", H, H);
-            h->add_vec(p + ".attn.relpos_enc.bias_mlp.0.weight", 2 * kCpbHidden, 2 * kCpbHidden);
-            h->add_vec(p + ".attn.relpos_enc.bias_mlp.0.bias", kCpbHidden, kCpbHidden);
-            h->add_vec(p + ".attn.relpos_enc.bias_mlp.2.weight", H * kCpbHidden, H * kCpbHidden);
-            h->add_vec(p + ".attn.proj.bias", F, F);
-            h->add_vec(p + ".norm1.weight", F, F);
-            h->add_vec(p + ".norm1.bias", F, F);
-            h->add_vec(p + ".mlp.layers.0.bias", 4 * F, 4 * F);
-            h->add_vec(p + ".mlp.layers.2.bias", F, F);
-            h->add_vec(p + ".norm2.weight", F, F);
-            h->add_vec(p + ".norm2.bias", F, F);
+            char buf[96];
+            snprintf(buf, sizeof(buf), "imgencoder.stages.%d.blocks.%d", s, l);
+            const std::string p = buf;
+            BlockRefs r;
+            const int s_q_b = h->add_spec(p + ".attn.q_bias", {1, H, 1, 32});
+            const int s_v_b = h->add_spec(p + ".attn.v_bias", {1, H, 1, 32});
+            const int s_qkv = h->add_spec(p + ".attn.qkv.weight", {3 * F, F});
+            const int s_ls = h->add_spec(p + ".attn.logit_scale", {H, 1, 1});
+            const int s_cpb_w1 = h->add_spec(p + ".attn.relpos_enc.bias_mlp.0.weight", {kCpbHidden, 2});
+            const int s_cpb_b1 = h->add_spec(p + ".attn.relpos_enc.bias_mlp.0.bias", {kCpbHidden});
+            const int s_cpb_w2 = h->add_spec(p + ".attn.relpos_enc.bias_mlp.2.weight", {H, kCpbHidden});
+            const int s_proj = h->add_spec(p + ".attn.proj.weight", {F, F});
+            const int s_proj_b = h->add_spec(p + ".attn.proj.bias", {F});
+            const int s_n1w = h->add_spec(p + ".norm1.weight", {F});
+            const int s_n1b = h->add_spec(p + ".norm1.bias", {F});
+            const int s_fc1 = h->add_spec(p + ".mlp.layers.0.weight", {4 * F, F});
+            const int s_fc1_b = h->add_spec(p + ".mlp.layers.0.bias", {4 * F});
+            const int s_fc2 = h->add_spec(p + ".mlp.layers.2.weight", {F, 4 * F});
+            const int s_fc2_b = h->add_spec(p + ".mlp.layers.2.bias", {F});
+            const int s_n2w = h->add_spec(p + ".norm2.weight", {F});
+            const int s_n2b = h->add_spec(p + ".norm2.bias", {F});
+            r.qkv = h->add_mat(s_qkv, CLS_QKV, MDPT_PACK_LINEAR, 3 * F, F, 3 * F, rup(F, 64), 0);
+            r.proj = h->add_mat(s_proj, CLS_PROJ, MDPT_PACK_LINEAR, F, F, F, rup(F, 64), 0);
+            r.fc1 = h->add_mat(s_fc1, CLS_FC1, MDPT_PACK_LINEAR, 4 * F, F, 4 * F, rup(F, 64), 0);
+            r.fc2 = h->add_mat(s_fc2, CLS_FC2, MDPT_PACK_LINEAR, F, 4 * F, F, 4 * F, 0);
+            r.qkv_b = h->add_vec(s_q_b, 0, 3 * F, VEC_QV_BIAS, s_v_b);
+            r.logit_scale = h->add_vec(s_ls, H, H, VEC_LOG2E);
+            r.cpb_w1 = h->add_vec(s_cpb_w1, 2 * kCpbHidden, 2 * kCpbHidden);
+            r.cpb_b1 = h->add_vec(s_cpb_b1, kCpbHidden, kCpbHidden);
+            r.cpb_w2 = h->add_vec(s_cpb_w2, H * kCpbHidden, H * kCpbHidden);
+            r.proj_b = h->add_vec(s_proj_b, F, F);
+            r.ln1_w = h->add_vec(s_n1w, F, F);
+            r.ln1_b = h->add_vec(s_n1b, F, F);
+            r.fc1_b = h->add_vec(s_fc1_b, 4 * F, 4 * F);
+            r.fc2_b = h->add_vec(s_fc2_b, F, F);
+            r.ln2_w = h->add_vec(s_n2w, F, F);
+            r.ln2_b = h->add_vec(s_n2b, F, F);
+            w.blocks.push_back(r);
         }
         if (s < 3) {
             char pm[96];
             snprintf(pm, sizeof(pm), "imgencoder.patch_merge_layers.%d", s);
             const int Fo = h->hid[s + 1];
-            h->add_spec(std::string(pm) + ".reduction.weight", {Fo, 4 * F});
-            h->add_spec(std::string(pm) + ".norm.weight", {Fo});
-            h->add_spec(std::string(pm) + ".norm.bias", {Fo});
-            h->add_mat(std::string(pm) + ".reduction.weight", MDPT_PACK_LINEAR, Fo, 4 * F, Fo, 4 * F, 0);
-            h->add_vec(std::string(pm) + ".norm.weight", Fo, Fo);
-            h->add_vec(std::string(pm) + ".norm.bias", Fo, Fo);
+            const int s_red = h->add_spec(std::string(pm) + ".reduction.weight", {Fo, 4 * F});
+            const int s_nw = h->add_spec(std::string(pm) + ".norm.weight", {Fo});
+            const int s_nb = h->add_spec(std::string(pm) + ".norm.bias", {Fo});
+            w.merge[s].reduction = h->add_mat(s_red, CLS_PROJ, MDPT_PACK_LINEAR, Fo, 4 * F, Fo, 4 * F, 0);  // a token-mixing projection
+            w.merge[s].norm_w = h->add_vec(s_nw, Fo, Fo);
+            w.merge[s].norm_b = h->add_vec(s_nb, Fo, Fo);
         }
     }
     for (int s = 0; s < 4; ++s) {
         const std::string p = std::string("reassemble.") + kSwinStageNames[s];
-        h->add_spec(p + ".fuse_proj.weight", {h->C, h->hid[s], 3, 3});
-        h->add_mat(p + ".fuse_proj.weight", MDPT_PACK_CONV3, h->C, h->hid[s], h->Cp, 9 * h->hidp[s], 3);
+        w.reasm[s].fuse_proj = h->add_mat(h->add_spec(p + ".fuse_proj.weight", {h->C, h->hid[s], 3, 3}), CLS_REASM, MDPT_PACK_CONV3, h->C, h->hid[s], h->Cp,
+                                          9 * h->hidp[s], 3);
     }
-    return 0;
 }
 
 int make_plan_swin(const mdpt_handle* h, int B, int H, int W, Plan* pl) {

@@ -20,14 +20,14 @@ int run_patch_embed_swin(const Ctx& c, const void* image, int image_dtype, float
     const int rows = p.B * p.sw.g0h * p.sw.g0w;
     Planes im = c.pl(p.im2col);
     CHK(run_patchify(c, image, image_dtype, im, p.sw.g0h * h->P, p.sw.g0w * h->P));
-    GemmParams g = base_params(c, h->M("patch_embed.proj.weight"), im, rows, h->Kpatch);
-    g.bias = h->V("patch_embed.proj.bias");
+    GemmParams g = base_params(c, h->M(h->w.patch), im, rows, h->Kpatch);
+    g.bias = h->V(h->w.patch_b);
     g.out_f32 = c.at<float>(p.sw.x); g.ldc = h->F;
     CHK(OPLC(mdpt_launch_gemm, g, c.s));
     Planes xn = c.pl(p.sw.xn);
     float* out = tokens_out ? tokens_out : c.at<float>(p.sw.resid[0]);
     if (!tokens_out) CHK(swin_zero_pad_planes(c, rows));
-    CHK(OPLC(mdpt_launch_ln_res, c.at<float>(p.sw.x), nullptr, h->V("patch_embed.norm.weight"), h->V("patch_embed.norm.bias"), 1e-5f, out,
+    CHK(OPLC(mdpt_launch_ln_res, c.at<float>(p.sw.x), nullptr, h->V(h->w.patch_ln_w), h->V(h->w.patch_ln_b), 1e-5f, out,
                            tokens_out ? nullptr : xn.hi, tokens_out ? nullptr : xn.lo, rows, h->F, c.s, rup(h->F, 64)));
     return 0;
 }
@@ -51,10 +51,10 @@ int run_encoder_swin(const Ctx& c, void* const taps_f32[4]) {
             CHK(swin_geom(h, p.sw.g0h, p.sw.g0w, s, &g));
             for (int l = 0; l < h->sL[s]; ++l) {
                 if (cb.n >= 32) return fail(MDPT_E_UNSUPPORTED, "more than 32 SwinV2 blocks");
-                const std::string n = swin_blk(s, l);
-                cb.w1[cb.n] = h->V(n + ".attn.relpos_enc.bias_mlp.0.weight");
-                cb.b1[cb.n] = h->V(n + ".attn.relpos_enc.bias_mlp.0.bias");
-                cb.w2[cb.n] = h->V(n + ".attn.relpos_enc.bias_mlp.2.weight");
+                const BlockRefs& w = h->w.blocks[cb.n];
+                cb.w1[cb.n] = h->V(w.cpb_w1);
+                cb.b1[cb.n] = h->V(w.cpb_b1);
+                cb.w2[cb.n] = h->V(w.cpb_w2);
                 cb.lut[cb.n] = (float*)(c.ws + p.sw.lut + (size_t)cb.n * p.sw.lut_stride);
                 cb.heads[cb.n] = g.heads; cb.wh[cb.n] = g.wh; cb.ww[cb.n] = g.ww; cb.pre[cb.n] = h->spre[s];
                 ++cb.n;
@@ -91,12 +91,12 @@ int run_encoder_swin(const Ctx& c, void* const taps_f32[4]) {
         bool vt_zeroed = false;
         const bool qk_planes_ok = (2 * F) % 256 == 0 && (size_t)p.B * img_rows * 64 < 0xFFFFFFF0ull && (size_t)p.B * img_rows < 0x7FFFFFFFull;
         for (int l = 0; l < h->sL[s]; ++l) {
-            const std::string n = swin_blk(s, l);
+            const BlockRefs& w = h->w.blocks[blk_index];
             const int v = (l & 1) && shifting ? 1 : 0;  // odd blocks of a pair are the shifted ones (image_encoder_model.py:155-161)
             bool qk_fused = false, v_fused = false;
             {
-                GemmParams gm = base_params(c, h->M(n + ".attn.qkv.weight"), xn, rows, Fp);
-                gm.bias = h->V(n + ".attn.qkv.bias@qv");
+                GemmParams gm = base_params(c, h->M(w.qkv), xn, rows, Fp);
+                gm.bias = h->V(w.qkv_b);
                 gm.out_f32 = x; gm.ldc = 3 * F;
 #ifdef MDPT_DEBUG_SWITCHES  // A/B builds only (tests force the unfused forms through mdpt_set_gemm_tile)
                 static const bool no_fusion = getenv("MDPT_SWIN_NO_QK_FUSION") != nullptr;
@@ -106,13 +106,13 @@ int run_encoder_swin(const Ctx& c, void* const taps_f32[4]) {
 #endif
                 // token-mean compensation of the weight rounding (fp16 modes): per-image bias table; the fused Q / K / V epilogues take it for
                 // stages of >= 256 tokens per image (two images per tile at most), smaller stages keep the fp32 rows + prep kernels
-                CHK(wrc_bias(c, gm, h->M(n + ".attn.qkv.weight"), gm.bias, g.N, g.N));
+                CHK(wrc_bias(c, gm, h->M(w.qkv), gm.bias, g.N, g.N));
                 qk_fused = !no_fusion && qk_planes_ok && Fp == F && (!gm.bias_img_stride || g.N >= 256) && OPLC(mdpt_gemm_resolves_to_pp256, gm);
                 if (qk_fused) {
                     gm.ekind = MDPT_E_SWQKV;
                     gm.F = F; gm.heads = g.heads; gm.npad = g.npad; gm.npadv = g.npadv;
                     gm.q_hi = q.hi; gm.q_lo = q.lo; gm.k_hi = k.hi; gm.k_lo = k.lo;
-                    gm.swin_tokmap = tokmap[v]; gm.swin_logit_scale = h->V(n + ".attn.logit_scale");
+                    gm.swin_tokmap = tokmap[v]; gm.swin_logit_scale = h->V(w.logit_scale);
                     gm.swin_N = g.N; gm.swin_img_rows = (int)img_rows;
                     if (v_direct_ok && !no_fusion_v) {
                         gm.vt_hi = vt.hi; gm.vt_lo = vt.lo;
@@ -128,7 +128,7 @@ int run_encoder_swin(const Ctx& c, void* const taps_f32[4]) {
                 CHK(OPLC(mdpt_launch_gemm, gm, c.s));
             }
             if (!v_fused)
-                CHK(OPLC(mdpt_launch_swin_qkv_prep, x, rowmap[v], h->V(n + ".attn.logit_scale"), q.hi, q.lo, k.hi, k.lo, vt.hi, vt.lo, p.B, g.N, g.nw, g.wa,
+                CHK(OPLC(mdpt_launch_swin_qkv_prep, x, rowmap[v], h->V(w.logit_scale), q.hi, q.lo, k.hi, k.lo, vt.hi, vt.lo, p.B, g.N, g.nw, g.wa,
                                               g.npad, g.npadv, g.heads, c.s, !qk_fused));
             float* lut_l = (float*)(c.ws + p.sw.lut + (size_t)blk_index * p.sw.lut_stride);
             ++blk_index;
@@ -144,7 +144,7 @@ int run_encoder_swin(const Ctx& c, void* const taps_f32[4]) {
                 a.win_nw = g.nw; a.rowmap = rowmap[v]; a.region = v ? region[1] : nullptr; a.region_ld = g.wa;
                 a.bias_run4 = (g.ww % 4 == 0 && g.wa % 4 == 0) ? 1 : 0;
                 a.bias_row = 2 * g.ww - 1; a.bias_ww = g.ww;  // conflict-free LDS image of the bias table (attention.hip)
-                a.swin_ls = h->V(n + ".attn.logit_scale");
+                a.swin_ls = h->V(w.logit_scale);
 #ifdef MDPT_DEBUG_SWITCHES  // A/B builds only
                 static const bool no_run4 = getenv("MDPT_SWIN_NO_RUN4") != nullptr;
                 if (no_run4) a.bias_run4 = 0;
@@ -153,27 +153,27 @@ int run_encoder_swin(const Ctx& c, void* const taps_f32[4]) {
                 CHK(OPLC(mdpt_launch_attention, a, c.s));
             }
             {
-                GemmParams gm = base_params(c, h->M(n + ".attn.proj.weight"), att, rows, Fp);
-                gm.bias = h->V(n + ".attn.proj.bias");
+                GemmParams gm = base_params(c, h->M(w.proj), att, rows, Fp);
+                gm.bias = h->V(w.proj_b);
                 gm.out_f32 = x; gm.ldc = F;
-                CHK(wrc_bias(c, gm, h->M(n + ".attn.proj.weight"), gm.bias, g.N, g.N));
+                CHK(wrc_bias(c, gm, h->M(w.proj), gm.bias, g.N, g.N));
                 CHK(OPLC(mdpt_launch_gemm, gm, c.s));
             }
-            CHK(OPLC(mdpt_launch_ln_res, x, resid, h->V(n + ".norm1.weight"), h->V(n + ".norm1.bias"), 1e-5f, resid, xn.hi, xn.lo, rows, F, c.s, Fp));
+            CHK(OPLC(mdpt_launch_ln_res, x, resid, h->V(w.ln1_w), h->V(w.ln1_b), 1e-5f, resid, xn.hi, xn.lo, rows, F, c.s, Fp));
             {
-                GemmParams gm = base_params(c, h->M(n + ".mlp.layers.0.weight"), xn, rows, Fp);
-                gm.bias = h->V(n + ".mlp.layers.0.bias");
+                GemmParams gm = base_params(c, h->M(w.fc1), xn, rows, Fp);
+                gm.bias = h->V(w.fc1_b);
                 gm.act = MDPT_ACT_GELU;
                 gm.out_hi = hb.hi; gm.out_lo = hb.lo; gm.ldc = 4 * F;
-                CHK(wrc_bias(c, gm, h->M(n + ".mlp.layers.0.weight"), gm.bias, g.N, g.N));
+                CHK(wrc_bias(c, gm, h->M(w.fc1), gm.bias, g.N, g.N));
                 CHK(OPLC(mdpt_launch_gemm, gm, c.s));
             }
             const float* fc2_part = nullptr;
             {
-                GemmParams gm = base_params(c, h->M(n + ".mlp.layers.2.weight"), hb, rows, 4 * F);
-                gm.bias = h->V(n + ".mlp.layers.2.bias");
+                GemmParams gm = base_params(c, h->M(w.fc2), hb, rows, 4 * F);
+                gm.bias = h->V(w.fc2_b);
                 gm.out_f32 = x; gm.ldc = F;
-                CHK(wrc_bias(c, gm, h->M(n + ".mlp.layers.2.weight"), gm.bias, g.N, g.N));
+                CHK(wrc_bias(c, gm, h->M(w.fc2), gm.bias, g.N, g.N));
                 // the late stages are few tiles of long K (stage 2 of SwinV2-L at batch 16: 108 8-phase tiles x 48 K tiles, which ran the lockstep
                 // 128x128 tile at 0.25 of peak): K in two fixed ranges, twice the workgroups, and the post-norm that follows adds the second
                 // range's partial sums. Decided by K alone (swin_ksplit) - at EVERY batch size, every tile form computes the
@@ -185,7 +185,7 @@ int run_encoder_swin(const Ctx& c, void* const taps_f32[4]) {
                 }
                 CHK(OPLC(mdpt_launch_gemm, gm, c.s));
             }
-            CHK(OPLC(mdpt_launch_ln_res, x, resid, h->V(n + ".norm2.weight"), h->V(n + ".norm2.bias"), 1e-5f, resid, xn.hi, xn.lo, rows, F, c.s, Fp, fc2_part));
+            CHK(OPLC(mdpt_launch_ln_res, x, resid, h->V(w.ln2_w), h->V(w.ln2_b), 1e-5f, resid, xn.hi, xn.lo, rows, F, c.s, Fp, fc2_part));
             if (c.block_dump && c.block_dump[blk_index - 1])  // block output tokens [B, N_s, F_s] (image_encoder_model.py:213-225)
                 CHK(hipMemcpyAsync(c.block_dump[blk_index - 1], resid, (size_t)rows * F * 4, hipMemcpyDeviceToDevice, c.s));
             if (c.norm_wanted(blk_index - 1))  // per-token norms / one channel of the same tokens: fp32 [B, gh_s, gw_s]
@@ -197,15 +197,14 @@ int run_encoder_swin(const Ctx& c, void* const taps_f32[4]) {
         CHK(OPLC(mdpt_launch_f32_to_planes, resid, tp.hi, tp.lo, (size_t)rows, F, Fp, c.s));
         if (taps_f32) CHK(hipMemcpyAsync(taps_f32[s], resid, (size_t)rows * F * 4, hipMemcpyDeviceToDevice, c.s));
         if (s < 3) {
-            char pm[96];
-            snprintf(pm, sizeof(pm), "imgencoder.patch_merge_layers.%d", s);
+            const auto& pm = h->w.merge[s];
             const int Fo = h->hid[s + 1], rows_o = rows / 4;
             CHK(OPLC(mdpt_launch_swin_merge_gather, resid, xn.hi, xn.lo, p.B, g.gh, g.gw, F, c.s));
-            GemmParams gm = base_params(c, h->M(std::string(pm) + ".reduction.weight"), xn, rows_o, 4 * F);
+            GemmParams gm = base_params(c, h->M(pm.reduction), xn, rows_o, 4 * F);
             gm.out_f32 = x; gm.ldc = Fo;
-            CHK(wrc_bias(c, gm, h->M(std::string(pm) + ".reduction.weight"), nullptr, g.N / 4, g.N / 4));
+            CHK(wrc_bias(c, gm, h->M(pm.reduction), nullptr, g.N / 4, g.N / 4));
             CHK(OPLC(mdpt_launch_gemm, gm, c.s));
-            CHK(OPLC(mdpt_launch_ln_res, x, nullptr, h->V(std::string(pm) + ".norm.weight"), h->V(std::string(pm) + ".norm.bias"), 1e-5f,
+            CHK(OPLC(mdpt_launch_ln_res, x, nullptr, h->V(pm.norm_w), h->V(pm.norm_b), 1e-5f,
                                    c.at<float>(p.sw.resid[s + 1]), xn.hi, xn.lo, rows_o, Fo, c.s));
         }
     }
@@ -218,9 +217,8 @@ int run_reassemble_swin(const Ctx& c) {
     const Plan& p = c.p;
     for (int s = 0; s < 4; ++s) {
         const int sh = p.sw.g0h >> s, sw = p.sw.g0w >> s, F = h->hid[s];
-        const std::string n = std::string("reassemble.") + kSwinStageNames[s];
         Planes rb = c.pl(p.r_bf[s]);
-        GemmParams g = base_params(c, h->M(n + ".fuse_proj.weight"), c.pl(p.tap[s]), p.B * sh * sw, h->hidp[s]);
+        GemmParams g = base_params(c, h->M(h->w.reasm[s].fuse_proj), c.pl(p.tap[s]), p.B * sh * sw, h->hidp[s]);
         as_conv(g, sh, sw, h->hidp[s], sh, sw, 1);
         g.out_f32 = c.at<float>(p.r_f32[s]);
         g.out_hi = rb.hi; g.out_lo = rb.lo; g.relu_bf16 = 1; g.ldc = h->Cp;
