@@ -317,6 +317,39 @@ int mdpt_forward_bgr_frames(mdpt_handle* h, const void* const* frames_u8_hwc, co
                             const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw, int32_t depth_dtype, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* Crop and region inference (the reference's --crop: frame[y_slice, x_slice] before dpt_model.inference; additive to ABI v6). A box of an image is
+ * a frame: the resize kernels read it where the image lies - first pixel at byte y1 * pitch + 3 * x1, rows `pitch` bytes apart - and their
+ * antialias taps clip at the BOX's edges, so the result equals, bit for bit, the same call on a packed copy of the box and never depends on a pixel
+ * outside it. Pitches and frame strides are in BYTES and 64-bit; boxes are x1, y1, x2, y2 in pixels, half-open (0 <= x1 < x2 <= w, 0 <= y1 < y2 <= h).
+ * Nothing is copied, allocated or synchronised; everything is validated on the host before the first launch (MDPT_E_INVALID).
+ *
+ *   frames                         table run        pitch            frame_stride
+ *   packed [B,h,w,3]               one, count B     3 w              3 h w
+ *   view / box of a [B,H,W,3]      one, count B     the tensor's     the tensor's
+ *   list of frames, any sizes      one per frame    3 w_b            -
+ *   list of boxes of images        one per box      image b's        -
+ *
+ * The pitch-and-box form of mdpt_prepare_image: pitch 0 = packed (3 * in_w); H, W are the caller's, from the size rule applied to the BOX's size. */
+int mdpt_prepare_image_region(const void* bgr_u8_hwc, int32_t in_h, int32_t in_w, int64_t pitch, const int32_t box_xyxy[4], void* out_chw, int32_t out_dtype,
+                              int32_t out_h, int32_t out_w, const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* stream);
+
+/* The one-size batch read in place: frame b is uint8 [in_h,in_w,3] at bgr_u8 + b * frame_stride with rows `pitch` (>= 3 * in_w) bytes apart - one box
+ * cut out of every frame of a [B,H,W,3] tensor, or a sliced view of one. One run of the frame table, one im2col launch; with pitch = 3 * in_w and
+ * frame_stride = 3 * in_h * in_w it is the packed batch entry point above. frame_stride is not read when B = 1. */
+int mdpt_forward_bgr_pitched(mdpt_handle* h, const void* bgr_u8, int32_t B, int32_t in_h, int32_t in_w, int64_t pitch, int64_t frame_stride,
+                             int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw,
+                             int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/* B regions in one batched forward (DPTModel.inference_regions): region b is the box boxes_xyxy[4b .. 4b+3] of the uint8 [images_hw[2b],
+ * images_hw[2b+1], 3] BGR image at device pointer images_u8_hwc[b], whose rows are images_pitch[b] bytes apart (images_pitch NULL = every image
+ * packed). Images may repeat and boxes may overlap; every region is resized to the one model tensor size H x W -> depth [B,H,W]. The host arrays are
+ * read during the call only; tables go 64 regions per im2col launch and a batch at or above the split size runs as two halves, the second from table
+ * entry B0, as the per-frame entry point above does. Region b's map equals the single-image entry point on a packed copy of its box, bit for bit.
+ * 1 <= B <= 65535. Workspace as for mdpt_forward(B). */
+int mdpt_forward_bgr_regions(mdpt_handle* h, const void* const* images_u8_hwc, const int32_t* images_hw, const int64_t* images_pitch, const int32_t* boxes_xyxy,
+                             int32_t B, int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3], const float rgb_std[3], int32_t interpolation,
+                             void* depth_bhw, int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Depth post-processing on the device (reference muggled_dpt/demo_helpers/postprocess.py and
  * run_3dviewer.py:576-590). All buffers are device pointers; `minmax` is a 2-float device buffer {min, max} and
  * `scratch8` 8 bytes of device scratch - nothing is read back to the host, nothing synchronises.

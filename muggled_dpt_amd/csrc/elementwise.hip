@@ -647,8 +647,11 @@ __device__ __forceinline__ void aa_span(int i, float scale, int in_size, int& lo
 // The output is written in the MODEL's dtype (out_dtype = MDPT_DT_*; the reference builds the tensor in the model dtype too,
 // patch_embed.py:131-145 - here the filter runs in fp32 and rounds once): no cast kernel between this one and the patchify of mdpt_forward.
 // One output pixel (all three channels, R G B): the arithmetic both kernels below share, so that the fused form's values equal the stand-alone one's bit for bit.
+// The source is a BOX of an image read where it lies: `bgr` is the box's first pixel, ih x iw the box's size and `pitch` the bytes from one image
+// row to the next (3 iw for a packed image). The taps clip at the box's edges (aa_span), as the reference's resize of the cropped array does:
+// no pixel outside the box is read. A box starts at byte y1 pitch + 3 x1 of its image, which has no alignment: the loads stay byte-wise.
 template <int INTERP>
-__device__ __forceinline__ void aa_pixel_rgb(const unsigned char* __restrict__ bgr, int ih, int iw, int oh, int ow, int oy, int ox, float m0, float m1, float m2,
+__device__ __forceinline__ void aa_pixel_rgb(const unsigned char* __restrict__ bgr, size_t pitch, int ih, int iw, int oh, int ow, int oy, int ox, float m0, float m1, float m2,
                                              float s0, float s1, float s2, float& v0, float& v1, float& v2) {
     const float sy = (float)ih / (float)oh, sx = (float)iw / (float)ow;
     int ylo, yn, xlo, xn;
@@ -661,7 +664,7 @@ __device__ __forceinline__ void aa_pixel_rgb(const unsigned char* __restrict__ b
     float acc_b = 0.0f, acc_g = 0.0f, acc_r = 0.0f;
     for (int a = 0; a < yn; ++a) {
         const float wy = aa_filter<INTERP>(((float)(a + ylo) - yc + 0.5f) * yinv) / wys;
-        const unsigned char* row = bgr + ((size_t)(ylo + a) * iw + xlo) * 3;
+        const unsigned char* row = bgr + (size_t)(ylo + a) * pitch + (size_t)xlo * 3;
         float rb = 0.0f, rg = 0.0f, rr = 0.0f;  // horizontal pass first (like the reference's separable CPU kernel)
         for (int c = 0; c < xn; ++c) {
             const float wx = aa_filter<INTERP>(((float)(c + xlo) - xc + 0.5f) * xinv) / wxs;
@@ -679,14 +682,14 @@ __device__ __forceinline__ void aa_pixel_rgb(const unsigned char* __restrict__ b
 }
 
 template <int INTERP>
-__global__ __launch_bounds__(256) void prepare_image_kernel(const unsigned char* __restrict__ bgr, void* __restrict__ out, int out_dtype, int ih,
+__global__ __launch_bounds__(256) void prepare_image_kernel(const unsigned char* __restrict__ bgr, size_t pitch, void* __restrict__ out, int out_dtype, int ih,
                                                             int iw, int oh, int ow, float m0, float m1, float m2, float s0,
                                                             float s1, float s2) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= oh * ow) return;
     const int ox = idx % ow, oy = idx / ow;
     float v0, v1, v2;
-    aa_pixel_rgb<INTERP>(bgr, ih, iw, oh, ow, oy, ox, m0, m1, m2, s0, s1, s2, v0, v1, v2);
+    aa_pixel_rgb<INTERP>(bgr, pitch, ih, iw, oh, ow, oy, ox, m0, m1, m2, s0, s1, s2, v0, v1, v2);
     const size_t plane = (size_t)oh * ow;
     if (out_dtype == MDPT_DT_BF16) {
         __bf16* o = (__bf16*)out;
@@ -705,7 +708,7 @@ __global__ __launch_bounds__(256) void prepare_image_kernel(const unsigned char*
 // values - and so every bit behind them - equal mdpt_prepare_image + patchify_kernel) and stored straight into its three places of the patch
 // embedding's im2col rows (k = c P^2 + ky P + kx). The normalised image never exists in memory. The first pixel of a patch also zeroes its
 // row's padding columns [3 P^2, Kp). Batched (mdpt_forward_bgr_batch / _frames): blockIdx.y = frame b of the launch's frame table, read from its
-// run's source with that run's own size (ih, iw), writes rows b gh gw + py gw + px, the row layout of patchify_kernel.
+// run's source with that run's own size, row pitch and frame stride (frame j of a run at ptr + j frame_stride), writes rows b gh gw + py gw + px, the row layout of patchify_kernel.
 template <int INTERP>
 __global__ __launch_bounds__(256) void prepare_patchify_kernel(const BgrRunTable t, int img_dt, op_t* out_hi, op_t* out_lo, int H, int W, int P, int Kp,
                                                                float m0, float m1, float m2, float s0, float s1, float s2) {
@@ -718,7 +721,7 @@ __global__ __launch_bounds__(256) void prepare_patchify_kernel(const BgrRunTable
     const int ih = t.run[r].ih, iw = t.run[r].iw;
     const int ox = idx % W, oy = idx / W;
     float v[3];
-    aa_pixel_rgb<INTERP>(bgr + (size_t)j * ih * iw * 3, ih, iw, H, W, oy, ox, m0, m1, m2, s0, s1, s2, v[0], v[1], v[2]);
+    aa_pixel_rgb<INTERP>(bgr + (size_t)j * (size_t)t.run[r].frame_stride, (size_t)t.run[r].pitch, ih, iw, H, W, oy, ox, m0, m1, m2, s0, s1, s2, v[0], v[1], v[2]);
     const int py = oy / P, ky = oy - py * P, px = ox / P, kx = ox - px * P;
     const size_t row = ((size_t)b * (H / P) * (W / P) + (size_t)py * (W / P) + px) * Kp;
 #pragma unroll
@@ -1162,15 +1165,16 @@ int MDPT_FN(mdpt_launch_tokens_to_resid)(const float* tokens, const float* pos, 
     LAUNCH_RET();
 }
 
-int MDPT_FN(mdpt_launch_prepare_image)(const unsigned char* bgr, void* out, int out_dtype, int ih, int iw, int oh, int ow, const float mean[3],
+int MDPT_FN(mdpt_launch_prepare_image)(const unsigned char* bgr, size_t pitch, void* out, int out_dtype, int ih, int iw, int oh, int ow, const float mean[3],
                               const float inv_std[3], int interp, hipStream_t stream) {
+    if (pitch < (size_t)3 * (size_t)(iw > 0 ? iw : 0)) return (int)hipErrorInvalidValue;
     if (ih <= 0 || iw <= 0 || oh <= 0 || ow <= 0 || (interp != 0 && interp != 1) || out_dtype < MDPT_DT_F32 || out_dtype > MDPT_DT_F16) return (int)hipErrorInvalidValue;
     MdptProfScope prof("prepare_image_kernel", 0.0, stream);
     if (interp == 0)
-        hipLaunchKernelGGL(prepare_image_kernel<0>, dim3((oh * ow + 255) / 256), dim3(256), 0, stream, bgr, out, out_dtype, ih, iw, oh, ow, mean[0], mean[1],
+        hipLaunchKernelGGL(prepare_image_kernel<0>, dim3((oh * ow + 255) / 256), dim3(256), 0, stream, bgr, pitch, out, out_dtype, ih, iw, oh, ow, mean[0], mean[1],
                            mean[2], inv_std[0], inv_std[1], inv_std[2]);
     else
-        hipLaunchKernelGGL(prepare_image_kernel<1>, dim3((oh * ow + 255) / 256), dim3(256), 0, stream, bgr, out, out_dtype, ih, iw, oh, ow, mean[0], mean[1],
+        hipLaunchKernelGGL(prepare_image_kernel<1>, dim3((oh * ow + 255) / 256), dim3(256), 0, stream, bgr, pitch, out, out_dtype, ih, iw, oh, ow, mean[0], mean[1],
                            mean[2], inv_std[0], inv_std[1], inv_std[2]);
     LAUNCH_RET();
 }
@@ -1182,7 +1186,9 @@ int MDPT_FN(mdpt_launch_prepare_patchify)(const BgrRunTable& t, int img_dtype, o
         return (int)hipErrorInvalidValue;
     int B = 0;
     for (int r = 0; r < t.n; ++r) {
-        if (!t.run[r].ptr || t.run[r].ih <= 0 || t.run[r].iw <= 0 || t.run[r].count <= 0 || t.run[r].count > 65535 - B) return (int)hipErrorInvalidValue;
+        if (!t.run[r].ptr || t.run[r].ih <= 0 || t.run[r].iw <= 0 || t.run[r].count <= 0 || t.run[r].count > 65535 - B || t.run[r].pitch < 3ll * t.run[r].iw ||
+            (t.run[r].count > 1 && t.run[r].frame_stride <= 0))
+            return (int)hipErrorInvalidValue;
         B += t.run[r].count;
     }
     MdptProfScope prof("prepare_patchify_kernel", 0.0, stream);

@@ -456,12 +456,7 @@ static int forward_batch(mdpt_handle* h, const void* image_bchw, const Ctx::BgrS
         if (bgr) {
             c0.bgr = *bgr;
             c1.bgr = *bgr;
-            if (bgr->frames) {
-                c1.bgr.frames += B0;  // (table entry B0 on)
-                c1.bgr.frames_hw += 2 * B0;
-            } else {
-                c1.bgr.ptr += (size_t)B0 * bgr->ih * bgr->iw * 3;
-            }
+            c1.bgr.advance(B0);  // (frame B0 / table entry B0 on)
         }
         int rc = forward_one(h, c0, image_bchw, image_dtype, depth_bhw, depth_dtype);
         if (rc == 0) rc = forward_one(h, c1, bgr ? nullptr : (const char*)image_bchw + in_stride * B0, image_dtype, (char*)depth_bhw + out_stride * B0, depth_dtype);
@@ -534,6 +529,51 @@ int mdpt_forward_bgr_frames(mdpt_handle* h, const void* const* frames_u8_hwc, co
     Ctx::BgrSource src;
     fill_bgr_source(src, image_dtype, interpolation, rgb_mean, rgb_std);
     src.frames = frames_u8_hwc; src.frames_hw = frames_hw;
+    return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
+}
+
+// ---- mdpt_forward_bgr_batch on frames read where they lie: rows `pitch` bytes apart, frames `frame_stride` bytes apart (a box of every frame of a
+// [B,H,W,3] tensor, or any view of one whose innermost strides are (3, 1)): still one run of the frame table and one im2col launch
+int mdpt_forward_bgr_pitched(mdpt_handle* h, const void* bgr_u8, int32_t B, int32_t in_h, int32_t in_w, int64_t pitch, int64_t frame_stride,
+                             int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw,
+                             int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !bgr_u8 || !depth_bhw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
+    for (int dt : {image_dtype, depth_dtype})
+        if (!tensor_dtype_ok(dt)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
+    CHK(check_interp(interpolation));
+    if (in_h <= 0 || in_w <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d", in_h, in_w);
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    if (pitch < (int64_t)3 * in_w) return fail(MDPT_E_INVALID, "row pitch %lld is below 3 * width (%d)", (long long)pitch, in_w);
+    if (B > 1 && frame_stride <= 0) return fail(MDPT_E_INVALID, "bad frame stride %lld", (long long)frame_stride);
+    Ctx::BgrSource src;
+    fill_bgr_source(src, image_dtype, interpolation, rgb_mean, rgb_std);
+    src.ptr = (const unsigned char*)bgr_u8; src.ih = in_h; src.iw = in_w; src.pitch = pitch; src.frame_stride = B > 1 ? frame_stride : pitch * in_h;
+    return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
+}
+
+// ---- mdpt_forward_bgr_frames on boxes: region b is the box boxes_xyxy[4b..4b+3] of the image at images_u8_hwc[b] (images may repeat and boxes may
+// overlap), read in place; everything is validated here, on the host, before anything is launched
+int mdpt_forward_bgr_regions(mdpt_handle* h, const void* const* images_u8_hwc, const int32_t* images_hw, const int64_t* images_pitch, const int32_t* boxes_xyxy,
+                             int32_t B, int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3], const float rgb_std[3], int32_t interpolation,
+                             void* depth_bhw, int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !images_u8_hwc || !images_hw || !boxes_xyxy || !depth_bhw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
+    for (int dt : {image_dtype, depth_dtype})
+        if (!tensor_dtype_ok(dt)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
+    CHK(check_interp(interpolation));
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    for (int b = 0; b < B; ++b) {
+        const int ih = images_hw[2 * b], iw = images_hw[2 * b + 1];
+        const int32_t* box = boxes_xyxy + 4 * b;
+        if (!images_u8_hwc[b]) return fail(MDPT_E_INVALID, "null argument (region %d)", b);
+        if (ih <= 0 || iw <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d (region %d)", ih, iw, b);
+        if (!(0 <= box[0] && box[0] < box[2] && box[2] <= iw && 0 <= box[1] && box[1] < box[3] && box[3] <= ih))
+            return fail(MDPT_E_INVALID, "box (%d, %d)-(%d, %d) of region %d is empty or outside its %dx%d image", box[0], box[1], box[2], box[3], b, ih, iw);
+        if (images_pitch && images_pitch[b] < (int64_t)3 * iw)
+            return fail(MDPT_E_INVALID, "row pitch %lld of region %d is below 3 * width (%d)", (long long)images_pitch[b], b, iw);
+    }
+    Ctx::BgrSource src;
+    fill_bgr_source(src, image_dtype, interpolation, rgb_mean, rgb_std);
+    src.frames = images_u8_hwc; src.frames_hw = images_hw; src.frames_pitch = images_pitch; src.boxes = boxes_xyxy;
     return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
 }
 
@@ -887,12 +927,25 @@ int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspac
 // ---- PatchEmbed.prepare_image (reference v2_depthanything/patch_embed.py:103-145): resize + BGR->RGB + normalise on the GPU
 int mdpt_prepare_image(const void* bgr_u8_hwc, int32_t in_h, int32_t in_w, void* out_chw, int32_t out_dtype, int32_t out_h, int32_t out_w,
                        const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* stream) {
-    if (!bgr_u8_hwc || !out_chw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
+    const int32_t full[4] = {0, 0, in_w, in_h};
+    return mdpt_prepare_image_region(bgr_u8_hwc, in_h, in_w, 0, full, out_chw, out_dtype, out_h, out_w, rgb_mean, rgb_std, interpolation, stream);
+}
+
+// ---- the same on a box of the image, read in place (what the reference does to image[y1:y2, x1:x2]): pitch in bytes (0 = packed), box in pixels, half-open
+int mdpt_prepare_image_region(const void* bgr_u8_hwc, int32_t in_h, int32_t in_w, int64_t pitch, const int32_t box_xyxy[4], void* out_chw, int32_t out_dtype,
+                              int32_t out_h, int32_t out_w, const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* stream) {
+    if (!bgr_u8_hwc || !box_xyxy || !out_chw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
     if (!tensor_dtype_ok(out_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", out_dtype);
     CHK(check_interp(interpolation));
     if (in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d -> %dx%d", in_h, in_w, out_h, out_w);
+    if (pitch == 0) pitch = (int64_t)3 * in_w;
+    if (pitch < (int64_t)3 * in_w) return fail(MDPT_E_INVALID, "row pitch %lld is below 3 * width (%d)", (long long)pitch, in_w);
+    const int x1 = box_xyxy[0], y1 = box_xyxy[1], x2 = box_xyxy[2], y2 = box_xyxy[3];
+    if (!(0 <= x1 && x1 < x2 && x2 <= in_w && 0 <= y1 && y1 < y2 && y2 <= in_h))
+        return fail(MDPT_E_INVALID, "box (%d, %d)-(%d, %d) is empty or outside the %dx%d image", x1, y1, x2, y2, in_h, in_w);
     const float inv_std[3] = {1.0f / rgb_std[0], 1.0f / rgb_std[1], 1.0f / rgb_std[2]};  // patch_embed.py:38-39,62
-    CHK(mdpt_launch_prepare_image_bf16((const unsigned char*)bgr_u8_hwc, out_chw, out_dtype, in_h, in_w, out_h, out_w, rgb_mean, inv_std, interpolation, (hipStream_t)stream));
+    const unsigned char* first = (const unsigned char*)bgr_u8_hwc + (size_t)y1 * (size_t)pitch + (size_t)x1 * 3;
+    CHK(mdpt_launch_prepare_image_bf16(first, (size_t)pitch, out_chw, out_dtype, y2 - y1, x2 - x1, out_h, out_w, rgb_mean, inv_std, interpolation, (hipStream_t)stream));
     return 0;
 }
 

@@ -335,11 +335,26 @@ struct Ctx {
     bool consts_cached = false;  // the per-grid constants of this (workspace, shape) are in place (mdpt_set_grid_cache): skip the kernels that write them
     // mdpt_forward_bgr: the patch embedding's im2col kernel builds its rows from this uint8 BGR image (resize + normalise fused in) instead of an image tensor
     // uint8 BGR source of the fused im2col (mdpt_forward_bgr[_batch|_frames]): B packed frames of one size (ptr, ih, iw), or the caller's host table
-    // of per-frame pointers and sizes (frames, frames_hw = h0,w0,h1,w1,...; read only during the call), frame b of this Ctx at entry b
+    // of per-frame pointers and sizes (frames, frames_hw = h0,w0,h1,w1,...; read only during the call), frame b of this Ctx at entry b.
+    // Frames read in place (mdpt_forward_bgr_pitched / _regions): `pitch` / `frame_stride` (bytes; 0 = packed) are the row pitch and frame distance of
+    // the one-size form; a table may carry per-frame row pitches (frames_pitch, null = packed) and boxes (boxes = x1,y1,x2,y2 per frame, pixels,
+    // half-open; null = the whole frame): entry b is then the box of frame b, frames_hw the size of the image around it.
     struct BgrSource {
         const unsigned char* ptr = nullptr; int ih = 0, iw = 0, round_dtype = 0, interp = 0; float mean[3] = {0, 0, 0}, inv_std[3] = {1, 1, 1};
+        int64_t pitch = 0, frame_stride = 0;
         const void* const* frames = nullptr; const int32_t* frames_hw = nullptr;
+        const int64_t* frames_pitch = nullptr; const int32_t* boxes = nullptr;
         bool active() const { return ptr || frames; }
+        // the split's second half: from frame / table entry B0 on
+        void advance(int B0) {
+            if (frames) {
+                frames += B0; frames_hw += 2 * B0;
+                if (frames_pitch) frames_pitch += B0;
+                if (boxes) boxes += 4 * B0;
+            } else {
+                ptr += (size_t)B0 * (size_t)(frame_stride ? frame_stride : (int64_t)ih * iw * 3);
+            }
+        }
     } bgr;
     void* const* attn_dump = nullptr;  // per block: where to write softmax(q k^T) as fp32 [B,H,N,N] (null entries: skip)
     void* const* block_dump = nullptr; // per block: where to write the block's output tokens as fp32 [B,N,F] (null entries: skip)

@@ -178,12 +178,16 @@ struct HeadTailParams {
 // SwinV2 helpers (swin.hip)
 // ------------------------------------------------------------------------------------------------
 // frame table of the fused resize + normalise + im2col kernel (prepare_patchify_kernel), passed BY VALUE as a kernel argument (nothing is
-// copied to the device, so a forward from uint8 frames stays graph-capturable): run r holds `count` packed uint8 [ih,iw,3] frames from `ptr`.
-// The frames of a launch are the runs' frames in order (blockIdx.y = frame); one size for the whole batch is one run, a list of frames of
-// different sizes is one run per frame. 64 runs = 1.5 KB of kernel arguments.
+// copied to the device, so a forward from uint8 frames stays graph-capturable): run r holds `count` uint8 [ih,iw,3] frames from `ptr`, each read
+// where it lies: rows `pitch` bytes apart, frame j at ptr + j frame_stride (bytes). Packed frames have pitch = 3 iw and frame_stride = 3 ih iw; a
+// box of an image is a frame whose ptr is the box's first pixel, ih x iw the box's size and pitch the IMAGE's row pitch.
+// The frames of a launch are the runs' frames in order (blockIdx.y = frame); one size for the whole batch is one run (also one box cut out of
+// every frame of a [B,H,W,3] tensor), a list of frames or boxes of different sizes is one run per frame. 64 runs = 2.5 KB of kernel arguments.
 #define MDPT_BGR_RUNS 64
-struct BgrRun { const unsigned char* ptr; int ih, iw, count; };
+struct BgrRun { const unsigned char* ptr; long long pitch, frame_stride; int ih, iw, count; };
 struct BgrRunTable { BgrRun run[MDPT_BGR_RUNS]; int n; };
+// HIP passes at most 4 KB of kernel arguments: the table plus the other arguments of prepare_patchify_kernel (two pointers, five ints, six floats)
+static_assert(sizeof(BgrRunTable) <= 3072, "BgrRunTable must leave room for the other kernel arguments below HIP's 4 KB limit");
 
 // image table of the per-image display tail (postprocess.hip seg_* and colorize kernels), by value like BgrRunTable: run r holds `count`
 // packed images of ih x iw elements from `in` (image j at in + j ih iw) whose outputs are oh x ow (the resize target; = ih x iw for the

@@ -69,8 +69,9 @@ int MDPT_FN(mdpt_launch_nchw_to_nhwc)(const float* in, float* out_f32, op_t* out
 // stage-level encoder entry: resid[b, 1+t, :] = tokens[b, t, :] + pos[t, :]
 int MDPT_FN(mdpt_launch_tokens_to_resid)(const float* tokens, const float* pos, float* resid, int B, int Np, int npad, int F,
                                 hipStream_t stream);
-// uint8 HWC BGR -> normalised fp32 [3,oh,ow] RGB through PyTorch-compatible antialiased bilinear resize
-int MDPT_FN(mdpt_launch_prepare_image)(const unsigned char* bgr, void* out, int out_dtype, int ih, int iw, int oh, int ow, const float mean[3],
+// uint8 HWC BGR -> normalised fp32 [3,oh,ow] RGB through PyTorch-compatible antialiased bilinear resize; bgr = the first pixel of an ih x iw box of an
+// image whose rows are `pitch` bytes apart (3 iw: a packed image)
+int MDPT_FN(mdpt_launch_prepare_image)(const unsigned char* bgr, size_t pitch, void* out, int out_dtype, int ih, int iw, int oh, int ow, const float mean[3],
                               const float inv_std[3], int interp, hipStream_t stream);
 // ... fused with patchify for the frames of a BgrRunTable (at most 65535), written from im2col row 0 of out_hi / out_lo
 int MDPT_FN(mdpt_launch_prepare_patchify)(const BgrRunTable& t, int img_dtype, op_t* out_hi, op_t* out_lo, int H, int W, int P, int Kp,

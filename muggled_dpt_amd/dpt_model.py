@@ -200,9 +200,12 @@ class PatchEmbed(_Stage):
         return scaled_hw, interp, p, out_dtype
 
     def prepare_image(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True,
-                      interpolation_mode: str = "bilinear") -> Tensor:
+                      interpolation_mode: str = "bilinear", *, crop=None) -> Tensor:
         """uint8 HxWx3 BGR -> normalised [1,3,H',W'] on the model device/dtype (patch_embed.py:103-145).
-        Sides snap to multiples of 2*patch (so a 518x518 image is processed at 504x504)."""
+        Sides snap to multiples of 2*patch (so a 518x518 image is processed at 504x504). crop (see DPTModel.inference): the tensor of
+        image_bgr[y_slice, x_slice]; only the box's bytes are staged."""
+        if crop is not None:
+            image_bgr = _crop_host(image_bgr, crop)
         scaled_hw, interp, p, out_dtype = self._prepare_plan(image_bgr, max_side_length, use_square_sizing, interpolation_mode)
         img_h, img_w = image_bgr.shape[0:2]
         with torch.cuda.device(p.device):
@@ -210,12 +213,18 @@ class PatchEmbed(_Stage):
             return self._prepare_device(src, img_h, img_w, scaled_hw, interp, p, out_dtype)
 
     def _prepare_device(self, src: Tensor, img_h: int, img_w: int, scaled_hw, interp: int, p, out_dtype) -> Tensor:
-        """mdpt_prepare_image on one uint8 HxWx3 frame already on the device -> [1,3,H',W'] in the model dtype."""
+        """mdpt_prepare_image on one uint8 HxWx3 frame already on the device -> [1,3,H',W'] in the model dtype. A [h,w,3] view whose rows are not
+        packed (strides (pitch, 3, 1): a box of an image) is read in place by the pitch-and-box form, mdpt_prepare_image_region."""
         lib = native.load()
         with torch.cuda.device(p.device):
             out = torch.empty((1, 3, scaled_hw[0], scaled_hw[1]), device=p.device, dtype=out_dtype)
             stream = torch.cuda.current_stream(p.device).cuda_stream
             mean3, std3 = self._norm_constants()
+            if src.dim() == 3 and not src.is_contiguous():
+                box = (ctypes.c_int32 * 4)(0, 0, img_w, img_h)
+                native.check(lib, lib.mdpt_prepare_image_region(src.data_ptr(), img_h, img_w, _row_pitch(src), box, out.data_ptr(), native.dtype_code(out_dtype),
+                                                                scaled_hw[0], scaled_hw[1], mean3, std3, interp, stream))
+                return out if out.dtype == p.dtype else out.to(p.dtype)
             # the kernel writes the model's dtype (dtype-tagged like mdpt_forward's tensors): nothing but this launch between the copy and the forward
             native.check(lib, lib.mdpt_prepare_image(src.data_ptr(), img_h, img_w, out.data_ptr(), native.dtype_code(out_dtype), scaled_hw[0], scaled_hw[1],
                                                      mean3, std3, interp, stream))
@@ -496,9 +505,83 @@ def native_config(cfg: dict, family: str, precision: int) -> "native.MdptConfig"
     return c
 
 
+def is_cropping(crop_xy1xy2_norm) -> bool:
+    """Whether a normalised ((x1, y1), (x2, y2)) box leaves anything out (the reference's CropData.is_cropping, run_3dviewer.py): a side
+    spanning less than 0.999 of the image crops."""
+    (x1, y1), (x2, y2) = crop_xy1xy2_norm
+    return bool((x2 - x1) < 0.999 or (y2 - y1) < 0.999)
+
+
+def crop_slices_from_norm(image_shape, crop_xy1xy2_norm, minimum_crop_xy=(5, 5)) -> tuple[slice, slice]:
+    """Normalised ((x1, y1), (x2, y2)) -> (y_slice, x_slice) in pixels, by the reference's rule (demo_helpers/crop_ui.py,
+    make_crop_slices_from_xy1xy2_norm): the corners times (w, h) as a float32 product, rounded half to even, clipped to [0, w] x [0, h]; a side
+    shorter than its minimum falls back to the image's full extent. Corners are not reordered (a reversed box gives an empty slice, as there)."""
+    full_h, full_w = int(image_shape[0]), int(image_shape[1])
+    norm = np.asarray(crop_xy1xy2_norm, dtype=np.float32)
+    if norm.shape != (2, 2):
+        raise TypeError(f"a normalised crop is ((x1, y1), (x2, y2)), got shape {norm.shape}")
+    limits = np.array([full_w, full_h], dtype=np.int32)
+    px = np.clip(np.round(norm * limits.astype(np.float32)).astype(np.int32), 0, limits)
+    (x1, y1), (x2, y2) = px.tolist()
+    if abs(x2 - x1) < minimum_crop_xy[0]:
+        x1, x2 = 0, full_w
+    if abs(y2 - y1) < minimum_crop_xy[1]:
+        y1, y2 = 0, full_h
+    return slice(y1, y2), slice(x1, x2)
+
+
+def _is_crop(crop) -> bool:
+    """a crop argument: a (y_slice, x_slice) pair, or ((x1, y1), (x2, y2)) in normalised units"""
+    if not isinstance(crop, (tuple, list)) or len(crop) != 2:
+        return False
+    if all(isinstance(c, slice) for c in crop):
+        return True
+    real = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)  # noqa: E731
+    return all(isinstance(c, (tuple, list, np.ndarray)) and len(c) == 2 and all(real(v) for v in c) for c in crop)
+
+
+def _crop_box(image_hw, crop) -> tuple[int, int, int, int]:
+    """A crop argument on an image of (h, w) -> the pixel box (x1, y1, x2, y2), half-open; None is the full image. Slices mean what they mean
+    in image[y_slice, x_slice] (negative and open ends included); a normalised box goes through crop_slices_from_norm. Host-side only."""
+    h, w = int(image_hw[0]), int(image_hw[1])
+    if crop is None:
+        return 0, 0, w, h
+    if not _is_crop(crop):
+        raise TypeError(f"a crop is ((x1, y1), (x2, y2)) in normalised units or a (y_slice, x_slice) pair, got {crop!r}")
+    ys, xs = crop if isinstance(crop[0], slice) else crop_slices_from_norm((h, w), crop)
+    (y1, y2, sy), (x1, x2, sx) = ys.indices(h), xs.indices(w)
+    if sy != 1 or sx != 1:
+        raise ValueError(f"crop slices must have step 1, got {ys}, {xs}")
+    if x2 <= x1 or y2 <= y1:
+        raise ValueError(f"the crop {crop!r} of a {h}x{w} image is empty")
+    return x1, y1, x2, y2
+
+
+def _crop_host(image_bgr, crop):
+    """image_bgr[y_slice, x_slice] of a host image as a view (nothing is copied; the staging copy reads the box's bytes only)"""
+    if not (isinstance(image_bgr, np.ndarray) and image_bgr.ndim == 3):
+        raise TypeError("a crop needs an OpenCV-style uint8 HxWx3 BGR image (cv2.imread output)")
+    x1, y1, x2, y2 = _crop_box(image_bgr.shape[0:2], crop)
+    return image_bgr[y1:y2, x1:x2]
+
+
+def _row_pitch(t: Tensor) -> int:
+    """bytes between the rows of a uint8 [..., h, w, 3] device tensor that _in_place() accepted (a single row has no pitch: packed)"""
+    return int(t.stride(-3)) if t.shape[-3] > 1 else 3 * int(t.shape[-2])
+
+
+def _in_place(t: Tensor) -> bool:
+    """Whether the im2col kernel can read a uint8 [h,w,3] / [B,h,w,3] device tensor where it lies: innermost strides (3, 1), rows at least a
+    row apart ([..., pitch, 3, 1]), frames any positive distance apart. Sliced views of packed tensors are of this kind."""
+    if t.stride(-1) != 1 or t.stride(-2) != 3 or (t.shape[-3] > 1 and t.stride(-3) < 3 * t.shape[-2]):
+        return False
+    return t.dim() == 3 or t.shape[0] == 1 or t.stride(0) > 0
+
+
 def _check_frames(images_bgr):
     """Argument checks of DPTModel.inference_batch (host-side only, nothing touches a GPU) -> (frames, on_device, (H, W)): frames is the
-    ndarray / list as given, or a contiguous [B,H,W,3] CUDA tensor."""
+    ndarray / list as given, or a [B,H,W,3] CUDA tensor the kernel can read in place (_in_place: as given, e.g. a sliced view; any other
+    layout is made contiguous)."""
     if isinstance(images_bgr, torch.Tensor):
         if images_bgr.dtype != torch.uint8 or images_bgr.dim() != 4 or images_bgr.shape[3] != 3:
             raise TypeError(f"inference_batch expects uint8 BxHxWx3 BGR frames, got a {images_bgr.dtype} tensor of shape {tuple(images_bgr.shape)}")
@@ -507,7 +590,7 @@ def _check_frames(images_bgr):
         if images_bgr.device.type != "cuda":
             images_bgr = images_bgr.numpy()
         else:
-            return images_bgr.contiguous(), True, tuple(images_bgr.shape[1:3])
+            return images_bgr if _in_place(images_bgr) else images_bgr.contiguous(), True, tuple(images_bgr.shape[1:3])
     if isinstance(images_bgr, np.ndarray):
         if images_bgr.dtype != np.uint8 or images_bgr.ndim != 4 or images_bgr.shape[3] != 3:
             raise TypeError(f"inference_batch expects uint8 BxHxWx3 BGR frames, got a {images_bgr.dtype} array of shape {images_bgr.shape}")
@@ -529,7 +612,7 @@ def _check_frames(images_bgr):
 
 def _check_images(images_bgr, batch_size) -> tuple[list, bool]:
     """Argument checks of DPTModel.inference_images (host-side only, nothing touches a GPU) -> (images, on_device): a list of uint8 HxWx3
-    ndarrays, or of contiguous uint8 HxWx3 CUDA tensors."""
+    ndarrays, or of uint8 HxWx3 CUDA tensors the kernel can read in place (_in_place; any other layout is made contiguous)."""
     if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)):
         raise TypeError(f"inference_images: batch_size must be an int, got {type(batch_size)}")
     if batch_size < 1:
@@ -553,7 +636,45 @@ def _check_images(images_bgr, batch_size) -> tuple[list, bool]:
             raise ValueError(f"inference_images got an empty image ({f.shape[0]}x{f.shape[1]})")
     if on_device and len({f.device for f in images_bgr}) != 1:
         raise RuntimeError("inference_images: the device tensors are on different devices")
-    return [f.contiguous() if on_device else f for f in images_bgr], on_device
+    return [(f if _in_place(f) else f.contiguous()) if on_device else f for f in images_bgr], on_device
+
+
+def _check_crops(crops, n_images: int) -> list:
+    """The `crops` argument of DPTModel.inference_images -> one crop (or None) per image: None, one crop for all, or a list of one per image."""
+    if crops is None or _is_crop(crops):
+        return [crops] * n_images
+    if not isinstance(crops, (list, tuple)) or not all(c is None or _is_crop(c) for c in crops):
+        raise TypeError("crops is one crop for all images or a list of one crop (or None) per image; a crop is ((x1, y1), (x2, y2)) in normalised "
+                        "units or a (y_slice, x_slice) pair")
+    if len(crops) != n_images:
+        raise ValueError(f"{n_images} images but {len(crops)} crops")
+    return list(crops)
+
+
+def _check_regions(regions, image_shapes) -> list[tuple[int, int, int, int, int]]:
+    """The `regions` argument of DPTModel.inference_regions (host-side only): (image_index, x1, y1, x2, y2) pixel boxes, half-open, inside their image."""
+    if not isinstance(regions, (list, tuple, np.ndarray)):
+        raise TypeError(f"inference_regions expects a list of (image_index, x1, y1, x2, y2) boxes, got {type(regions)}")
+    if len(regions) == 0:
+        raise ValueError("inference_regions got no regions")
+    out = []
+    for k, r in enumerate(regions):
+        if not hasattr(r, "__len__") or len(r) != 5 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in r):
+            raise TypeError(f"region {k} must be five ints (image_index, x1, y1, x2, y2), got {r!r}")
+        i, x1, y1, x2, y2 = (int(v) for v in r)
+        if not 0 <= i < len(image_shapes):
+            raise IndexError(f"region {k}: image index {i} is outside [0, {len(image_shapes)})")
+        h, w = int(image_shapes[i][0]), int(image_shapes[i][1])
+        if not (0 <= x1 < x2 <= w and 0 <= y1 < y2 <= h):
+            raise ValueError(f"region {k}: box ({x1}, {y1})-({x2}, {y2}) is empty or outside its {h}x{w} image")
+        out.append((i, x1, y1, x2, y2))
+    return out
+
+
+def region_chunks(regions, scaled_hw, batch_size: int):
+    """Forward plan of DPTModel.inference_regions (pure host code): image_chunks on the BOX sizes - the reference applies its size rule to the
+    cropped frame - so the indices are region indices."""
+    return image_chunks([(y2 - y1, x2 - x1) for _, x1, y1, x2, y2 in regions], scaled_hw, batch_size)
 
 
 def image_chunks(sizes_hw, scaled_hw, batch_size: int) -> list[tuple[tuple[int, int], list[int]]]:
@@ -919,8 +1040,13 @@ class DPTModel(nn.Module):
             out = self.imgencoder.block_norms(tokens, hw, channels)
         return (*out[1:], hw)
 
-    def inference(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True) -> Tensor:
-        """prepare_image + forward under inference_mode -> [1,H,W] (dpt_model.py:87-109)."""
+    def inference(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True, *, crop=None) -> Tensor:
+        """prepare_image + forward under inference_mode -> [1,H,W] (dpt_model.py:87-109). crop: the reference's --crop, a box as
+        ((x1, y1), (x2, y2)) in normalised units (crop_slices_from_norm turns it into pixels by the reference's rule) or the (y_slice, x_slice)
+        pair its crop UI returns. The result is inference(np.ascontiguousarray(image_bgr[y_slice, x_slice])) bit for bit - the size rule sees the
+        box's size - and only the box's bytes are staged and read."""
+        if crop is not None:
+            image_bgr = _crop_host(image_bgr, crop)
         with torch.inference_mode():
             probes = self.imgencoder.__dict__.get("_softmax_probes") or []
             blocks = self.imgencoder.__dict__.get("_block_probes") or []
@@ -940,14 +1066,21 @@ class DPTModel(nn.Module):
                                  out, native.dtype_code(out.dtype), size_hw=(h, w), batch=1)
             return out
 
-    def inference_batch(self, images_bgr, max_side_length: int | None = None, use_square_sizing: bool = True) -> Tensor:
+    def inference_batch(self, images_bgr, max_side_length: int | None = None, use_square_sizing: bool = True, *, crop=None) -> Tensor:
         """inference() for B frames of one size -> [B,H',W'] in the model dtype (not in the reference; its demos loop over frames). Takes a uint8
         ndarray [B,H,W,3], a list / tuple of HxWx3 uint8 arrays of one shape, or a uint8 CUDA tensor [B,H,W,3] on the model's device (frames that
         already live there skip the host staging). Same size rule, resize and inference_mode as inference(); row b equals
-        model(torch.cat([prepare_image_bgr(frame) for frame in frames]))[b] bit for bit, through one mdpt_forward_bgr_batch call."""
+        model(torch.cat([prepare_image_bgr(frame) for frame in frames]))[b] bit for bit, through one mdpt_forward_bgr_batch call.
+        crop (see inference): one box cut out of every frame, the result that of the packed copies frame[y_slice, x_slice]. Device frames are read
+        where they lie - a cropped tensor, like any sliced view [B, y1:y2, x1:x2] passed without a crop, is still one run of the frame table
+        and one im2col launch (mdpt_forward_bgr_pitched: row pitch and frame stride); host frames are staged box by box."""
         frames, on_device, (img_h, img_w) = _check_frames(images_bgr)
         if img_h == 0 or img_w == 0:
             raise ValueError(f"inference_batch got empty frames ({img_h}x{img_w})")
+        if crop is not None:
+            x1, y1, x2, y2 = _crop_box((img_h, img_w), crop)
+            frames = [f[y1:y2, x1:x2] for f in frames] if isinstance(frames, list) else frames[:, y1:y2, x1:x2]
+            img_h, img_w = y2 - y1, x2 - x1
         pe = self.patch_embed
         p = next(self.parameters())
         if p.device.type != "cuda":
@@ -973,18 +1106,29 @@ class DPTModel(nn.Module):
                 src = frames if on_device else pe._stage_host_image(frames, p.device)
                 out = torch.empty((b, h, w), device=p.device, dtype=eng.dtype)
                 mean3, std3 = pe._norm_constants()
-                eng.call_checked("mdpt_forward_bgr_batch", src, b, img_h, img_w, native.dtype_code(img_dtype), h, w, mean3, std3, native.INTERP_BILINEAR,
-                                 out, native.dtype_code(out.dtype), size_hw=(h, w), batch=b)
+                if src.is_contiguous():
+                    eng.call_checked("mdpt_forward_bgr_batch", src, b, img_h, img_w, native.dtype_code(img_dtype), h, w, mean3, std3, native.INTERP_BILINEAR,
+                                     out, native.dtype_code(out.dtype), size_hw=(h, w), batch=b)
+                else:  # a box / sliced view of device frames, read in place
+                    eng.call_checked("mdpt_forward_bgr_pitched", src, b, img_h, img_w, _row_pitch(src), int(src.stride(0)), native.dtype_code(img_dtype), h, w,
+                                     mean3, std3, native.INTERP_BILINEAR, out, native.dtype_code(out.dtype), size_hw=(h, w), batch=b)
             return out
 
-    def inference_images(self, images_bgr, max_side_length: int | None = None, use_square_sizing: bool = True, batch_size: int = 32) -> list[Tensor]:
+    def inference_images(self, images_bgr, max_side_length: int | None = None, use_square_sizing: bool = True, batch_size: int = 32, *,
+                         crops=None) -> list[Tensor]:
         """inference() for a list of images of ANY sizes (not in the reference; its run_image.py loops over files) -> a list in input order, element
         i the [1,H_i,W_i] map of image i in the model dtype (a view into its chunk's output). Takes uint8 HxWx3 BGR ndarrays, or uint8 HxWx3 CUDA
         tensors on the model's device (not a mix). Images whose size rule gives the same tensor size share batched forwards of at most batch_size
         images (image_chunks; square sizing, the default, gives every image the same size), each one mdpt_forward_bgr_frames call reading every
         image from its own place. Element i equals model(torch.cat([prepare_image_bgr(f) for f in its chunk]))[its row] bit for bit; in the
-        default (batch-invariant) modes that is inference(image i)."""
+        default (batch-invariant) modes that is inference(image i). crops: one crop for all images or a list of one (or None) per image (see
+        inference): element i is then the map of images[i][y_slice, x_slice], its size rule applied to the box; device images are read in place,
+        host images staged box by box."""
         images, on_device = _check_images(images_bgr, batch_size)
+        crops = _check_crops(crops, len(images))
+        if any(c is not None for c in crops):
+            boxes = [_crop_box(f.shape[0:2], c) for f, c in zip(images, crops)]
+            images = [f[y1:y2, x1:x2] for f, (x1, y1, x2, y2) in zip(images, boxes)]
         pe = self.patch_embed
         p = next(self.parameters())
         if p.device.type != "cuda":
@@ -1012,8 +1156,11 @@ class DPTModel(nn.Module):
                     y = self(x)
                 else:
                     with torch.cuda.device(p.device):
+                        pitches = None
                         if on_device:
                             ptrs = [images[i].data_ptr() for i in idx]
+                            if not all(images[i].is_contiguous() for i in idx):  # boxes / sliced views, read in place with their images' row pitches
+                                pitches = [_row_pitch(images[i]) for i in idx]
                         else:
                             # one pinned staging copy for the chunk: image k starts where image k-1 ends
                             src = pe._stage_host_image([images[i] for i in idx], p.device)
@@ -1022,15 +1169,84 @@ class DPTModel(nn.Module):
                         ptr_arr = np.asarray(ptrs, dtype=np.uint64)
                         hw_arr = np.asarray([images[i].shape[0:2] for i in idx], dtype=np.int32).ravel()
                         y = torch.empty((b, h, w), device=p.device, dtype=eng.dtype)
-                        eng.call_checked("mdpt_forward_bgr_frames", ptr_arr.ctypes.data, hw_arr.ctypes.data, b, native.dtype_code(img_dtype), h, w, mean3,
-                                         std3, native.INTERP_BILINEAR, y, native.dtype_code(y.dtype), size_hw=(h, w), batch=b)
+                        if pitches is None:
+                            eng.call_checked("mdpt_forward_bgr_frames", ptr_arr.ctypes.data, hw_arr.ctypes.data, b, native.dtype_code(img_dtype), h, w, mean3,
+                                             std3, native.INTERP_BILINEAR, y, native.dtype_code(y.dtype), size_hw=(h, w), batch=b)
+                        else:  # every view is the whole of a "frame" with its own pitch
+                            pitch_arr = np.asarray(pitches, dtype=np.int64)
+                            box_arr = np.asarray([(0, 0, images[i].shape[1], images[i].shape[0]) for i in idx], dtype=np.int32).ravel()
+                            eng.call_checked("mdpt_forward_bgr_regions", ptr_arr.ctypes.data, hw_arr.ctypes.data, pitch_arr.ctypes.data, box_arr.ctypes.data, b,
+                                             native.dtype_code(img_dtype), h, w, mean3, std3, native.INTERP_BILINEAR, y, native.dtype_code(y.dtype),
+                                             size_hw=(h, w), batch=b)
                 for k, i in enumerate(idx):
                     out[i] = y[k:k + 1]
         return out
 
+    def inference_regions(self, images, regions, max_side_length: int | None = None, use_square_sizing: bool = True, batch_size: int = 32) -> list[Tensor]:
+        """Depth of BOXES of images, batched (not in the reference, whose demos crop one frame and predict): images as inference_images takes them
+        (uint8 HxWx3 ndarrays, or CUDA tensors on the model's device; not a mix), regions a list of (image_index, x1, y1, x2, y2) pixel boxes,
+        half-open - any number per image, overlapping or not (detector boxes, tiles of a large photo) -> one [1,H_r,W_r] map per region, in region
+        order. Region r equals inference(np.ascontiguousarray(image[y1:y2, x1:x2])) bit for bit in the default (batch-invariant) modes: the size
+        rule is applied to the box's size, and the antialias taps stop at the box's edges. Regions whose boxes get the same tensor size share
+        batched forwards of at most batch_size regions (region_chunks), one mdpt_forward_bgr_regions call each.
+        Device images are read where they lie (base pointer, row pitch, box): no packed copy of any box is made. Host images are copied box by
+        box into the pinned staging buffer, so the staged bytes are the boxes' bytes, not the images' - which also means that MANY OVERLAPPING
+        regions of one host image are staged once each: put such an image on the device once (torch.from_numpy(image).cuda()) instead."""
+        images, on_device = _check_images(images, batch_size)
+        regions = _check_regions(regions, [f.shape for f in images])
+        pe = self.patch_embed
+        p = next(self.parameters())
+        if p.device.type != "cuda":
+            raise RuntimeError("inference_regions runs on the GPU only (no CPU fallback): move the model to a cuda device first")
+        if on_device and images[0].device != p.device:
+            raise RuntimeError(f"Expected all tensors to be on the same device, model is on {p.device} but the images are on {images[0].device}")
+        chunks = region_chunks(regions, lambda h, w: pe._scaled_hw(h, w, max_side_length, use_square_sizing), batch_size)
+        out: list[Tensor | None] = [None] * len(regions)
+        with torch.inference_mode():
+            probes = self.imgencoder.__dict__.get("_softmax_probes") or []
+            blocks = self.imgencoder.__dict__.get("_block_probes") or []
+            img_dtype = p.dtype if p.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
+            staged = img_dtype != p.dtype or any(len(pr._forward_hooks) > 0 for pr in probes) or any(len(node._forward_hooks) > 0 for node, _ in blocks)
+            eng = None if staged else self._get_engine()
+            mean3, std3 = pe._norm_constants()
+            view = lambda r: images[regions[r][0]][regions[r][2]:regions[r][4], regions[r][1]:regions[r][3]]  # noqa: E731
+            for (h, w), idx in chunks:
+                b = len(idx)
+                if staged:
+                    # hooks listening: the stage-by-stage route of forward(), on the tensor the region form of prepare gives per box
+                    if on_device:
+                        x = torch.cat([pe._prepare_device(view(r), view(r).shape[0], view(r).shape[1], (h, w), native.INTERP_BILINEAR, p, img_dtype) for r in idx])
+                    else:
+                        x = torch.cat([pe.prepare_image(view(r), max_side_length, use_square_sizing) for r in idx])
+                    y = self(x)
+                else:
+                    with torch.cuda.device(p.device):
+                        if on_device:
+                            ptrs = [images[regions[r][0]].data_ptr() for r in idx]
+                            hws = [images[regions[r][0]].shape[0:2] for r in idx]
+                            pitch_arr = np.asarray([_row_pitch(images[regions[r][0]]) for r in idx], dtype=np.int64)
+                            box_arr = np.asarray([regions[r][1:] for r in idx], dtype=np.int32).ravel()
+                        else:
+                            # one pinned staging copy for the chunk, box by box: box k starts where box k-1 ends, packed
+                            src = pe._stage_host_image([view(r) for r in idx], p.device)
+                            offs = np.cumsum([0] + [view(r).size for r in idx[:-1]])
+                            ptrs = [src.data_ptr() + int(o) for o in offs]
+                            hws = [view(r).shape[0:2] for r in idx]
+                            pitch_arr = None
+                            box_arr = np.asarray([(0, 0, hw[1], hw[0]) for hw in hws], dtype=np.int32).ravel()
+                        ptr_arr = np.asarray(ptrs, dtype=np.uint64)
+                        hw_arr = np.asarray(hws, dtype=np.int32).ravel()
+                        y = torch.empty((b, h, w), device=p.device, dtype=eng.dtype)
+                        eng.call_checked("mdpt_forward_bgr_regions", ptr_arr.ctypes.data, hw_arr.ctypes.data, None if pitch_arr is None else pitch_arr.ctypes.data,
+                                         box_arr.ctypes.data, b, native.dtype_code(img_dtype), h, w, mean3, std3, native.INTERP_BILINEAR, y,
+                                         native.dtype_code(y.dtype), size_hw=(h, w), batch=b)
+                for k, r in enumerate(idx):
+                    out[r] = y[k:k + 1]
+        return out
+
     def prepare_image_bgr(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True,
-                          interpolation_mode: str = "bilinear") -> Tensor:
-        return self.patch_embed.prepare_image(image_bgr, max_side_length, use_square_sizing, interpolation_mode)
+                          interpolation_mode: str = "bilinear", *, crop=None) -> Tensor:
+        return self.patch_embed.prepare_image(image_bgr, max_side_length, use_square_sizing, interpolation_mode, crop=crop)
 
     def verify_input(self, image_rgb_normalized_bchw: Tensor) -> bool:
         """Same assertions as dpt_model.py:133-166."""

@@ -197,6 +197,12 @@ SYMBOLS = {
                                               _VP]),
     "mdpt_forward_bgr_frames": (ctypes.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _I, _VP, _I, _VP,
                                                _SZ, _VP]),
+    "mdpt_prepare_image_region": (ctypes.c_int, [_VP, _I, _I, ctypes.c_int64, _VP, _VP, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _I,
+                                                 _VP]),
+    "mdpt_forward_bgr_pitched": (ctypes.c_int, [_VP, _VP, _I, _I, _I, ctypes.c_int64, ctypes.c_int64, _I, _I, _I, ctypes.POINTER(ctypes.c_float),
+                                                ctypes.POINTER(ctypes.c_float), _I, _VP, _I, _VP, _SZ, _VP]),
+    "mdpt_forward_bgr_regions": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _I, _VP, _I,
+                                                _VP, _SZ, _VP]),
     "mdpt_post_minmax": (ctypes.c_int, [_VP, _SZ, _VP, _VP, _VP]),
     "mdpt_post_scale_prediction": (ctypes.c_int, [_VP, _I, _I, _I, _VP, _I, _I, _VP, _VP, _VP]),
     "mdpt_post_normalize": (ctypes.c_int, [_VP, _SZ, _VP, _VP, _I, _I, _VP]),

@@ -15,10 +15,13 @@ when the blocks' grids differ (SwinV2).
 For one image or several, --mesh DIR saves the 3D viewer's "Save 3D Model" result (postprocess.pack_depth_u24_frames -> depth_frames_to_mesh ->
 mesh_io): <name>.glb with the photo as its texture, or with --mesh_obj <name>.obj plus <name>_image.png; --mesh_faces, --mesh_fov and --mesh_points
 are the viewer's mesh density, FOV and point mode.
+--crop X1 Y1 X2 Y2 is the reference's --crop with a stored box: normalised corners, applied to every image before it is predicted
+(crop_slices_from_norm: a side under 5 px falls back to the image's full extent); every output is then that of the cropped image.
 
   python tools/mdpt_run_image.py --synthetic vits --size 518 --fp32
   python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i image.npy -o depth_u8.npy
   python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i a.npy -i b.npy -i c.npy -o depth_dir
+  python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i image.npy --crop 0.25 0.1 0.75 0.9 -o depth_u8.npy
   python tools/mdpt_run_image.py -m model_weights/depth_anything_v2_vitl.pth -i a.npy -i b.npy --mask 0.5 1 --remove_plane 0.5 --cutout cut_dir
 """
 import argparse
@@ -42,6 +45,8 @@ def main():
     ap.add_argument("-b", "--batch_size", type=int, default=32, help="several images: at most this many per batched forward")
     ap.add_argument("-s", "--size", type=int, default=None, help="max side length (default: the model's base size)")
     ap.add_argument("-a", "--use_aspect_ratio", action="store_true", help="keep the image aspect ratio (default: square sizing)")
+    ap.add_argument("--crop", type=float, nargs=4, default=None, metavar=("X1", "Y1", "X2", "Y2"),
+                    help="predict this box of every image only: normalised top-left and bottom-right corners (the reference's --crop)")
     ap.add_argument("--fp32", action="store_true", help="float32 model = split-bf16 fp32-class arithmetic (default: bfloat16)")
     ap.add_argument("-o", "--output", default=None, help="save the 8-bit depth map (.npy)")
     ap.add_argument("--remove_plane", type=float, default=0.0, metavar="F", help="single image: remove F times the plane of best fit (run_image.py)")
@@ -78,13 +83,15 @@ def main():
         img = np.load(args.image_path[0])
     else:
         img = np.random.default_rng(1).integers(0, 256, (518, 518, 3), dtype=np.uint8)
-    model.inference(img, args.size, not args.use_aspect_ratio)  # first call builds the engine (weight repack)
+    crop = crop_argument(args)
+    model.inference(img, args.size, not args.use_aspect_ratio, crop=crop)  # first call builds the engine (weight repack)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     print(f"Loading model & first call: {round(1000 * (t1 - t0))} ms", flush=True)
-    depth = model.inference(img, args.size, not args.use_aspect_ratio)
+    depth = model.inference(img, args.size, not args.use_aspect_ratio, crop=crop)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
+    img = cropped(img, crop)  # what was predicted: the display steps below work at its size
     print(f"Inference: {round(1000 * (t2 - t1), 2)} ms", f"Prediction shape: {tuple(depth.shape)}, dtype {depth.dtype}, device {depth.device}", sep="\n")
     if args.output:
         np.save(args.output, convert_to_uint8(depth).squeeze(0).cpu().numpy())
@@ -101,6 +108,21 @@ def main():
     save_cutouts(args, args.image_path or ["synthetic.npy"], [img], [depth])
     save_block_norms(model, args, args.image_path or ["synthetic.npy"], [img])
     save_meshes(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
+
+
+def crop_argument(args):
+    """--crop X1 Y1 X2 Y2 -> the ((x1, y1), (x2, y2)) box DPTModel.inference takes, or None"""
+    return None if args.crop is None else ((args.crop[0], args.crop[1]), (args.crop[2], args.crop[3]))
+
+
+def cropped(img, crop):
+    """the box of the image that crop= makes the model predict (a packed copy, for the display steps)"""
+    if crop is None:
+        return img
+    from muggled_dpt_amd import crop_slices_from_norm
+    ys, xs = crop_slices_from_norm(img.shape, crop)
+    print(f"Cropping to x {xs.start}:{xs.stop}, y {ys.start}:{ys.stop} of {img.shape[1]}x{img.shape[0]}")
+    return np.ascontiguousarray(img[ys, xs])
 
 
 def save_cutouts(args, paths, images, depths):
@@ -173,13 +195,15 @@ def run_images(model, args, t0, is_metric=False):
     from muggled_dpt_amd.postprocess import depth_to_color_images
     images = [np.load(p) for p in args.image_path]
     square = not args.use_aspect_ratio
-    model.inference_images(images, args.size, square, args.batch_size)  # first call builds the engine (weight repack)
+    crop = crop_argument(args)
+    model.inference_images(images, args.size, square, args.batch_size, crops=crop)  # first call builds the engine (weight repack)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     print(f"Loading model & first call: {round(1000 * (t1 - t0))} ms", flush=True)
-    depths = model.inference_images(images, args.size, square, args.batch_size)
+    depths = model.inference_images(images, args.size, square, args.batch_size, crops=crop)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
+    images = [cropped(img, crop) for img in images]  # what was predicted: the display steps below work at those sizes
     print(f"Inference of {len(images)} images: {round(1000 * (t2 - t1), 2)} ms ({round(1000 * (t2 - t1) / len(images), 2)} ms per image)")
     for path, img, d in zip(args.image_path, images, depths):
         print(f"  {path}: {img.shape[1]}x{img.shape[0]} -> prediction {tuple(d.shape)}, dtype {d.dtype}")
