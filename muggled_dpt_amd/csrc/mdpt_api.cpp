@@ -482,12 +482,6 @@ static int check_interp(int interpolation) {
     return 0;
 }
 
-// what every uint8 BGR source of the fused im2col shares; the caller adds where the frames are (packed: ptr, ih, iw; a table: frames, frames_hw)
-static void fill_bgr_source(Ctx::BgrSource& src, int image_dtype, int interpolation, const float rgb_mean[3], const float rgb_std[3]) {
-    src.round_dtype = image_dtype; src.interp = interpolation;
-    for (int i = 0; i < 3; ++i) { src.mean[i] = rgb_mean[i]; src.inv_std[i] = 1.0f / rgb_std[i]; }  // patch_embed.py:38-39,62
-}
-
 int mdpt_forward(mdpt_handle* h, const void* image_bchw, int32_t image_dtype, int32_t B, int32_t H, int32_t W, void* depth_bhw,
                  int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !image_bchw || !depth_bhw) return fail(MDPT_E_INVALID, "null argument");
@@ -496,40 +490,62 @@ int mdpt_forward(mdpt_handle* h, const void* image_bchw, int32_t image_dtype, in
     return forward_batch(h, image_bchw, nullptr, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
 }
 
+// ---- the uint8 BGR entry points (mdpt_forward_bgr and its _batch / _frames / _pitched / _regions forms): each checks its arguments on the host
+// in the order null pointers, dtypes, interpolation, [the one frame size], batch (check_bgr_args), then its own pitches or its table, describes
+// where its frames are in a Ctx::BgrSource and hands that to forward_bgr
+static int check_bgr_args(bool pointers_ok, int image_dtype, int depth_dtype, int interpolation, int B, int in_h = 1, int in_w = 1) {
+    if (!pointers_ok) return fail(MDPT_E_INVALID, "null argument");
+    for (int dt : {image_dtype, depth_dtype})
+        if (!tensor_dtype_ok(dt)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
+    CHK(check_interp(interpolation));
+    if (in_h <= 0 || in_w <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d", in_h, in_w);  // (the forms with one frame size)
+    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);  // (the im2col kernel's grid y is the frame index)
+    return 0;
+}
+
+// the per-entry checks of a frame table; pitch and boxes are optional (`what` names an entry in the messages: "frame", "region")
+static int check_bgr_table(const void* const* frames, const int32_t* frames_hw, const int64_t* frames_pitch, const int32_t* boxes, int B, const char* what) {
+    for (int b = 0; b < B; ++b) {
+        const int ih = frames_hw[2 * b], iw = frames_hw[2 * b + 1];
+        if (!frames[b]) return fail(MDPT_E_INVALID, "null argument (%s %d)", what, b);
+        if (ih <= 0 || iw <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d (%s %d)", ih, iw, what, b);
+        const int32_t* box = boxes ? boxes + 4 * b : nullptr;
+        if (box && !(0 <= box[0] && box[0] < box[2] && box[2] <= iw && 0 <= box[1] && box[1] < box[3] && box[3] <= ih))
+            return fail(MDPT_E_INVALID, "box (%d, %d)-(%d, %d) of %s %d is empty or outside its %dx%d image", box[0], box[1], box[2], box[3], what, b, ih, iw);
+        if (frames_pitch && frames_pitch[b] < (int64_t)3 * iw)
+            return fail(MDPT_E_INVALID, "row pitch %lld of %s %d is below 3 * width (%d)", (long long)frames_pitch[b], what, b, iw);
+    }
+    return 0;
+}
+
+// what every uint8 BGR source shares (the caller has filled in where the frames are), then the forward
+static int forward_bgr(mdpt_handle* h, Ctx::BgrSource& src, int32_t B, int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3], const float rgb_std[3],
+                       int32_t interpolation, void* depth_bhw, int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    src.round_dtype = image_dtype; src.interp = interpolation;
+    for (int i = 0; i < 3; ++i) { src.mean[i] = rgb_mean[i]; src.inv_std[i] = 1.0f / rgb_std[i]; }  // patch_embed.py:38-39,62
+    return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
+}
+
 // ---- DPTModel.inference's device half (reference dpt_model.py:87-109: prepare_image_bgr -> forward), SURVEY 8(f) row 1 "fused with patchify",
 // for B packed frames of one size (DPTModel.inference_batch); image b's map equals mdpt_prepare_image(frame b), stacked, then mdpt_forward
 int mdpt_forward_bgr_batch(mdpt_handle* h, const void* bgr_u8_bhwc, int32_t B, int32_t in_h, int32_t in_w, int32_t image_dtype, int32_t H, int32_t W,
                            const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw, int32_t depth_dtype, void* workspace,
                            size_t workspace_bytes, void* stream) {
-    if (!h || !bgr_u8_bhwc || !depth_bhw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
-    for (int dt : {image_dtype, depth_dtype})
-        if (!tensor_dtype_ok(dt)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
-    CHK(check_interp(interpolation));
-    if (in_h <= 0 || in_w <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d", in_h, in_w);
-    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);  // (the im2col kernel's grid y is the frame index)
+    CHK(check_bgr_args(h && bgr_u8_bhwc && depth_bhw && rgb_mean && rgb_std, image_dtype, depth_dtype, interpolation, B, in_h, in_w));
     Ctx::BgrSource src;
-    fill_bgr_source(src, image_dtype, interpolation, rgb_mean, rgb_std);
     src.ptr = (const unsigned char*)bgr_u8_bhwc; src.ih = in_h; src.iw = in_w;
-    return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
+    return forward_bgr(h, src, B, image_dtype, H, W, rgb_mean, rgb_std, interpolation, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
 }
 
 // ---- the same for B frames of any sizes, each its own device pointer, all resized to one model tensor size (DPTModel.inference_images)
 int mdpt_forward_bgr_frames(mdpt_handle* h, const void* const* frames_u8_hwc, const int32_t* frames_hw, int32_t B, int32_t image_dtype, int32_t H, int32_t W,
                             const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw, int32_t depth_dtype, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    if (!h || !frames_u8_hwc || !frames_hw || !depth_bhw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
-    for (int dt : {image_dtype, depth_dtype})
-        if (!tensor_dtype_ok(dt)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
-    CHK(check_interp(interpolation));
-    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
-    for (int b = 0; b < B; ++b) {
-        if (!frames_u8_hwc[b]) return fail(MDPT_E_INVALID, "null argument (frame %d)", b);
-        if (frames_hw[2 * b] <= 0 || frames_hw[2 * b + 1] <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d (frame %d)", frames_hw[2 * b], frames_hw[2 * b + 1], b);
-    }
+    CHK(check_bgr_args(h && frames_u8_hwc && frames_hw && depth_bhw && rgb_mean && rgb_std, image_dtype, depth_dtype, interpolation, B));
+    CHK(check_bgr_table(frames_u8_hwc, frames_hw, nullptr, nullptr, B, "frame"));
     Ctx::BgrSource src;
-    fill_bgr_source(src, image_dtype, interpolation, rgb_mean, rgb_std);
     src.frames = frames_u8_hwc; src.frames_hw = frames_hw;
-    return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
+    return forward_bgr(h, src, B, image_dtype, H, W, rgb_mean, rgb_std, interpolation, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
 }
 
 // ---- mdpt_forward_bgr_batch on frames read where they lie: rows `pitch` bytes apart, frames `frame_stride` bytes apart (a box of every frame of a
@@ -537,18 +553,12 @@ int mdpt_forward_bgr_frames(mdpt_handle* h, const void* const* frames_u8_hwc, co
 int mdpt_forward_bgr_pitched(mdpt_handle* h, const void* bgr_u8, int32_t B, int32_t in_h, int32_t in_w, int64_t pitch, int64_t frame_stride,
                              int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3], const float rgb_std[3], int32_t interpolation, void* depth_bhw,
                              int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h || !bgr_u8 || !depth_bhw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
-    for (int dt : {image_dtype, depth_dtype})
-        if (!tensor_dtype_ok(dt)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
-    CHK(check_interp(interpolation));
-    if (in_h <= 0 || in_w <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d", in_h, in_w);
-    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
+    CHK(check_bgr_args(h && bgr_u8 && depth_bhw && rgb_mean && rgb_std, image_dtype, depth_dtype, interpolation, B, in_h, in_w));
     if (pitch < (int64_t)3 * in_w) return fail(MDPT_E_INVALID, "row pitch %lld is below 3 * width (%d)", (long long)pitch, in_w);
     if (B > 1 && frame_stride <= 0) return fail(MDPT_E_INVALID, "bad frame stride %lld", (long long)frame_stride);
     Ctx::BgrSource src;
-    fill_bgr_source(src, image_dtype, interpolation, rgb_mean, rgb_std);
     src.ptr = (const unsigned char*)bgr_u8; src.ih = in_h; src.iw = in_w; src.pitch = pitch; src.frame_stride = B > 1 ? frame_stride : pitch * in_h;
-    return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
+    return forward_bgr(h, src, B, image_dtype, H, W, rgb_mean, rgb_std, interpolation, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
 }
 
 // ---- mdpt_forward_bgr_frames on boxes: region b is the box boxes_xyxy[4b..4b+3] of the image at images_u8_hwc[b] (images may repeat and boxes may
@@ -556,25 +566,11 @@ int mdpt_forward_bgr_pitched(mdpt_handle* h, const void* bgr_u8, int32_t B, int3
 int mdpt_forward_bgr_regions(mdpt_handle* h, const void* const* images_u8_hwc, const int32_t* images_hw, const int64_t* images_pitch, const int32_t* boxes_xyxy,
                              int32_t B, int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3], const float rgb_std[3], int32_t interpolation,
                              void* depth_bhw, int32_t depth_dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h || !images_u8_hwc || !images_hw || !boxes_xyxy || !depth_bhw || !rgb_mean || !rgb_std) return fail(MDPT_E_INVALID, "null argument");
-    for (int dt : {image_dtype, depth_dtype})
-        if (!tensor_dtype_ok(dt)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dt);
-    CHK(check_interp(interpolation));
-    if (B <= 0 || B > 65535) return fail(MDPT_E_INVALID, "bad batch %d", B);
-    for (int b = 0; b < B; ++b) {
-        const int ih = images_hw[2 * b], iw = images_hw[2 * b + 1];
-        const int32_t* box = boxes_xyxy + 4 * b;
-        if (!images_u8_hwc[b]) return fail(MDPT_E_INVALID, "null argument (region %d)", b);
-        if (ih <= 0 || iw <= 0) return fail(MDPT_E_INVALID, "bad image size %dx%d (region %d)", ih, iw, b);
-        if (!(0 <= box[0] && box[0] < box[2] && box[2] <= iw && 0 <= box[1] && box[1] < box[3] && box[3] <= ih))
-            return fail(MDPT_E_INVALID, "box (%d, %d)-(%d, %d) of region %d is empty or outside its %dx%d image", box[0], box[1], box[2], box[3], b, ih, iw);
-        if (images_pitch && images_pitch[b] < (int64_t)3 * iw)
-            return fail(MDPT_E_INVALID, "row pitch %lld of region %d is below 3 * width (%d)", (long long)images_pitch[b], b, iw);
-    }
+    CHK(check_bgr_args(h && images_u8_hwc && images_hw && boxes_xyxy && depth_bhw && rgb_mean && rgb_std, image_dtype, depth_dtype, interpolation, B));
+    CHK(check_bgr_table(images_u8_hwc, images_hw, images_pitch, boxes_xyxy, B, "region"));
     Ctx::BgrSource src;
-    fill_bgr_source(src, image_dtype, interpolation, rgb_mean, rgb_std);
     src.frames = images_u8_hwc; src.frames_hw = images_hw; src.frames_pitch = images_pitch; src.boxes = boxes_xyxy;
-    return forward_batch(h, nullptr, &src, image_dtype, B, H, W, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
+    return forward_bgr(h, src, B, image_dtype, H, W, rgb_mean, rgb_std, interpolation, depth_bhw, depth_dtype, workspace, workspace_bytes, stream);
 }
 
 int mdpt_forward_bgr(mdpt_handle* h, const void* bgr_u8_hwc, int32_t in_h, int32_t in_w, int32_t image_dtype, int32_t H, int32_t W, const float rgb_mean[3],

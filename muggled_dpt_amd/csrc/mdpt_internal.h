@@ -333,18 +333,31 @@ struct Ctx {
     bool a1_done = false;  // ... where the first conv of every conv_reassembly unit was queued too: run_fusion skips it
     unsigned* poison = nullptr;  // mdpt_forward with non-finite propagation on: the plan's per-image words, cleared, for the im2col kernel to set
     bool consts_cached = false;  // the per-grid constants of this (workspace, shape) are in place (mdpt_set_grid_cache): skip the kernels that write them
-    // mdpt_forward_bgr: the patch embedding's im2col kernel builds its rows from this uint8 BGR image (resize + normalise fused in) instead of an image tensor
-    // uint8 BGR source of the fused im2col (mdpt_forward_bgr[_batch|_frames]): B packed frames of one size (ptr, ih, iw), or the caller's host table
-    // of per-frame pointers and sizes (frames, frames_hw = h0,w0,h1,w1,...; read only during the call), frame b of this Ctx at entry b.
-    // Frames read in place (mdpt_forward_bgr_pitched / _regions): `pitch` / `frame_stride` (bytes; 0 = packed) are the row pitch and frame distance of
-    // the one-size form; a table may carry per-frame row pitches (frames_pitch, null = packed) and boxes (boxes = x1,y1,x2,y2 per frame, pixels,
-    // half-open; null = the whole frame): entry b is then the box of frame b, frames_hw the size of the image around it.
+    // uint8 BGR source of the fused im2col (mdpt_forward_bgr and its _batch / _frames / _pitched / _regions forms): the patch embedding's im2col
+    // kernel builds its rows from the caller's uint8 frames (resize + normalise fused in) instead of an image tensor. Every source is a list of
+    // views, held in one of two forms:
+    //   one run  B frames of one size (ptr, ih, iw), rows `pitch` and frames `frame_stride` bytes apart (0 = packed): one BgrRun, one launch;
+    //   a table  the caller's host arrays (read only during the call), frame b of this Ctx at entry b: its pointer and frames_hw = h0,w0,h1,w1,...,
+    //            optionally its row pitch (frames_pitch; null = packed) and a box (boxes = x1,y1,x2,y2 per entry, pixels, half-open; null = the
+    //            whole frame - with a box, frames_hw is the size of the image around it): one BgrRun of one frame per entry.
+    // run_of() is the one place either form - and what "packed" means - is decoded; run_patchify only loops over it and launches.
     struct BgrSource {
         const unsigned char* ptr = nullptr; int ih = 0, iw = 0, round_dtype = 0, interp = 0; float mean[3] = {0, 0, 0}, inv_std[3] = {1, 1, 1};
         int64_t pitch = 0, frame_stride = 0;
         const void* const* frames = nullptr; const int32_t* frames_hw = nullptr;
         const int64_t* frames_pitch = nullptr; const int32_t* boxes = nullptr;
         bool active() const { return ptr || frames; }
+        bool table() const { return frames != nullptr; }
+        // entry b of a table, or (b = 0) the one run of the B frames of one size
+        BgrRun run_of(int b, int B) const {
+            if (!frames) return BgrRun{ptr, pitch ? pitch : 3ll * iw, frame_stride ? frame_stride : 3ll * iw * ih, ih, iw, B};
+            const int fh = frames_hw[2 * b], fw = frames_hw[2 * b + 1];
+            const long long row = frames_pitch ? frames_pitch[b] : 3ll * fw;
+            const unsigned char* p = (const unsigned char*)frames[b];
+            if (!boxes) return BgrRun{p, row, 0, fh, fw, 1};
+            const int32_t* box = boxes + 4 * b;  // x1, y1, x2, y2 (validated by the entry point): the run starts at the box's first pixel
+            return BgrRun{p + (size_t)box[1] * (size_t)row + (size_t)box[0] * 3, row, 0, box[3] - box[1], box[2] - box[0], 1};
+        }
         // the split's second half: from frame / table entry B0 on
         void advance(int B0) {
             if (frames) {
@@ -352,7 +365,7 @@ struct Ctx {
                 if (frames_pitch) frames_pitch += B0;
                 if (boxes) boxes += 4 * B0;
             } else {
-                ptr += (size_t)B0 * (size_t)(frame_stride ? frame_stride : (int64_t)ih * iw * 3);
+                ptr += (size_t)B0 * (size_t)run_of(0, B0).frame_stride;
             }
         }
     } bgr;

@@ -44,34 +44,17 @@ int run_pos(const Ctx& c) {
 }
 
 // im2col rows of the patch embedding: from an image tensor, or (mdpt_forward_bgr[_batch|_frames|_pitched|_regions]) straight from the caller's uint8
-// BGR frames. Frames of one size are one run of the frame table (one launch); a per-frame table goes MDPT_BGR_RUNS frames per launch, each launch
-// from its first frame's im2col rows. A box of a frame is a run that starts at the box's first pixel with the frame's row pitch.
+// BGR frames (Ctx::BgrSource). Frames of one size are one run of the frame table (one launch); a per-frame table goes MDPT_BGR_RUNS entries per
+// launch, each launch from its first frame's im2col rows.
 int run_patchify(const Ctx& c, const void* image, int image_dtype, const Planes& im, int H, int W) {
     const mdpt_handle* h = c.h;
     if (c.bgr.active()) {
-        BgrRunTable t{};
-        if (!c.bgr.frames) {
-            t.n = 1;
-            const long long packed_pitch = 3ll * c.bgr.iw;
-            const long long pitch = c.bgr.pitch ? c.bgr.pitch : packed_pitch;
-            t.run[0] = BgrRun{c.bgr.ptr, pitch, c.bgr.frame_stride ? c.bgr.frame_stride : packed_pitch * c.bgr.ih, c.bgr.ih, c.bgr.iw, c.p.B};
-            return OPLC(mdpt_launch_prepare_patchify, t, c.bgr.round_dtype, im.hi, im.lo, H, W, h->P, h->Kpatch, c.bgr.mean, c.bgr.inv_std, c.bgr.interp, c.s);
-        }
+        const int runs = c.bgr.table() ? c.p.B : 1;
         const size_t frame_elems = (size_t)(H / h->P) * (W / h->P) * h->Kpatch;
-        for (int b0 = 0; b0 < c.p.B; b0 += MDPT_BGR_RUNS) {
-            t.n = c.p.B - b0 < MDPT_BGR_RUNS ? c.p.B - b0 : MDPT_BGR_RUNS;
-            for (int r = 0; r < t.n; ++r) {
-                const int b = b0 + r;
-                const int fh = c.bgr.frames_hw[2 * b], fw = c.bgr.frames_hw[2 * b + 1];
-                const long long pitch = c.bgr.frames_pitch ? c.bgr.frames_pitch[b] : 3ll * fw;
-                const unsigned char* p = (const unsigned char*)c.bgr.frames[b];
-                if (c.bgr.boxes) {
-                    const int32_t* box = c.bgr.boxes + 4 * b;  // x1, y1, x2, y2 (validated by the entry point)
-                    t.run[r] = BgrRun{p + (size_t)box[1] * (size_t)pitch + (size_t)box[0] * 3, pitch, 0, box[3] - box[1], box[2] - box[0], 1};
-                } else {
-                    t.run[r] = BgrRun{p, pitch, 0, fh, fw, 1};
-                }
-            }
+        BgrRunTable t{};
+        for (int b0 = 0; b0 < runs; b0 += MDPT_BGR_RUNS) {
+            t.n = runs - b0 < MDPT_BGR_RUNS ? runs - b0 : MDPT_BGR_RUNS;
+            for (int r = 0; r < t.n; ++r) t.run[r] = c.bgr.run_of(b0 + r, c.p.B);
             CHK(OPLC(mdpt_launch_prepare_patchify, t, c.bgr.round_dtype, im.hi + frame_elems * b0, im.lo ? im.lo + frame_elems * b0 : nullptr, H, W, h->P,
                      h->Kpatch, c.bgr.mean, c.bgr.inv_std, c.bgr.interp, c.s));
         }

@@ -27,6 +27,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import native
+from .frame_inputs import (_check_crops, _check_frames, _check_images, _check_regions, _crop_box, _crop_host, _in_place, _is_crop,  # noqa: F401
+                           _row_pitch, crop_slices_from_norm, image_chunks, is_cropping, region_chunks)
 from .state_dict_conversion import COMPONENTS, expected_new_keys
 
 RGB_MEAN = (0.485, 0.456, 0.406)  # reference v2_depthanything/patch_embed.py:38
@@ -186,18 +188,26 @@ class PatchEmbed(_Stage):
     def _prepare_plan(self, image_bgr: np.ndarray, max_side_length: int | None, use_square_sizing: bool, interpolation_mode: str):
         """Size rule and argument checks of prepare_image (patch_embed.py:103-130): -> (model tensor (H, W), MDPT_INTERP_*, parameter, image dtype)."""
         scaled_hw = self._scaled_hw(image_bgr.shape[0], image_bgr.shape[1], max_side_length, use_square_sizing)
-        p = next(self.parameters())
         # one HIP kernel (antialiased resize + BGR->RGB + normalisation), mdpt_prepare_image. No torch fallback: what the kernel does not
         # cover raises, exactly where torch's own F.interpolate(antialias=True) would (it supports bilinear and bicubic only).
         interp = {"bilinear": native.INTERP_BILINEAR, "bicubic": native.INTERP_BICUBIC}.get(interpolation_mode)
         if interp is None:
             raise ValueError(f"Anti-alias option is restricted to bilinear and bicubic modes (got interpolation_mode={interpolation_mode!r})")
-        if p.device.type != "cuda":
-            raise RuntimeError("prepare_image runs on the GPU only (no CPU fallback): move the model to a cuda device first")
+        p, out_dtype = self._target("prepare_image")
         if not (isinstance(image_bgr, np.ndarray) and image_bgr.dtype == np.uint8 and image_bgr.ndim == 3 and image_bgr.shape[2] == 3):
             raise TypeError("prepare_image expects an OpenCV-style uint8 HxWx3 BGR image (cv2.imread output)")
-        out_dtype = p.dtype if p.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
         return scaled_hw, interp, p, out_dtype
+
+    def _target(self, who: str, source_device=None, what: str = "frames"):
+        """Precondition of every uint8 route, `who` the method the caller called: the model is on a GPU and device-resident input (source_device) is
+        on the same one -> (parameter, image dtype): the dtype the prepared image is written in - the model's, fp32 for a model dtype the kernels do
+        not write."""
+        p = next(self.parameters())
+        if p.device.type != "cuda":
+            raise RuntimeError(f"{who} runs on the GPU only (no CPU fallback): move the model to a cuda device first")
+        if source_device is not None and source_device != p.device:
+            raise RuntimeError(f"Expected all tensors to be on the same device, model is on {p.device} but the {what} are on {source_device}")
+        return p, p.dtype if p.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
 
     def prepare_image(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True,
                       interpolation_mode: str = "bilinear", *, crop=None) -> Tensor:
@@ -207,27 +217,23 @@ class PatchEmbed(_Stage):
         if crop is not None:
             image_bgr = _crop_host(image_bgr, crop)
         scaled_hw, interp, p, out_dtype = self._prepare_plan(image_bgr, max_side_length, use_square_sizing, interpolation_mode)
-        img_h, img_w = image_bgr.shape[0:2]
-        with torch.cuda.device(p.device):
-            src = self._stage_host_image(image_bgr, p.device)
-            return self._prepare_device(src, img_h, img_w, scaled_hw, interp, p, out_dtype)
+        return self._prepare_view(image_bgr, scaled_hw, interp, p, out_dtype)
 
-    def _prepare_device(self, src: Tensor, img_h: int, img_w: int, scaled_hw, interp: int, p, out_dtype) -> Tensor:
-        """mdpt_prepare_image on one uint8 HxWx3 frame already on the device -> [1,3,H',W'] in the model dtype. A [h,w,3] view whose rows are not
-        packed (strides (pitch, 3, 1): a box of an image) is read in place by the pitch-and-box form, mdpt_prepare_image_region."""
+    def _prepare_view(self, view, scaled_hw, interp: int, p, out_dtype) -> Tensor:
+        """One uint8 [h,w,3] view -> [1,3,H',W'] in the model dtype: the per-view step of prepare_image and of every staged route. A host ndarray
+        (any view of one: a crop) is staged first and is packed from there on; a device tensor that _in_place() accepted is read where it lies.
+        Either way mdpt_prepare_image_region gets the view's pointer, its row pitch and the full box (mdpt_prepare_image is that call with pitch 0)."""
+        img_h, img_w = view.shape[0:2]
         lib = native.load()
         with torch.cuda.device(p.device):
+            src, pitch = (view, _row_pitch(view)) if isinstance(view, torch.Tensor) else (self._stage_host_image(view, p.device), 0)
+            # the kernel writes the model's dtype (dtype-tagged like mdpt_forward's tensors): nothing but this launch between the copy and the forward
             out = torch.empty((1, 3, scaled_hw[0], scaled_hw[1]), device=p.device, dtype=out_dtype)
             stream = torch.cuda.current_stream(p.device).cuda_stream
             mean3, std3 = self._norm_constants()
-            if src.dim() == 3 and not src.is_contiguous():
-                box = (ctypes.c_int32 * 4)(0, 0, img_w, img_h)
-                native.check(lib, lib.mdpt_prepare_image_region(src.data_ptr(), img_h, img_w, _row_pitch(src), box, out.data_ptr(), native.dtype_code(out_dtype),
-                                                                scaled_hw[0], scaled_hw[1], mean3, std3, interp, stream))
-                return out if out.dtype == p.dtype else out.to(p.dtype)
-            # the kernel writes the model's dtype (dtype-tagged like mdpt_forward's tensors): nothing but this launch between the copy and the forward
-            native.check(lib, lib.mdpt_prepare_image(src.data_ptr(), img_h, img_w, out.data_ptr(), native.dtype_code(out_dtype), scaled_hw[0], scaled_hw[1],
-                                                     mean3, std3, interp, stream))
+            box = (ctypes.c_int32 * 4)(0, 0, img_w, img_h)
+            native.check(lib, lib.mdpt_prepare_image_region(src.data_ptr(), img_h, img_w, pitch, box, out.data_ptr(), native.dtype_code(out_dtype),
+                                                            scaled_hw[0], scaled_hw[1], mean3, std3, interp, stream))
         return out if out.dtype == p.dtype else out.to(p.dtype)
 
     def _norm_constants(self):
@@ -503,188 +509,6 @@ def native_config(cfg: dict, family: str, precision: int) -> "native.MdptConfig"
     c.precision = precision
     c.family = {"v2": native.FAMILY_DAV2, "v1": native.FAMILY_DAV1, "beit": native.FAMILY_BEIT, "swinv2": native.FAMILY_SWINV2}[family]
     return c
-
-
-def is_cropping(crop_xy1xy2_norm) -> bool:
-    """Whether a normalised ((x1, y1), (x2, y2)) box leaves anything out (the reference's CropData.is_cropping, run_3dviewer.py): a side
-    spanning less than 0.999 of the image crops."""
-    (x1, y1), (x2, y2) = crop_xy1xy2_norm
-    return bool((x2 - x1) < 0.999 or (y2 - y1) < 0.999)
-
-
-def crop_slices_from_norm(image_shape, crop_xy1xy2_norm, minimum_crop_xy=(5, 5)) -> tuple[slice, slice]:
-    """Normalised ((x1, y1), (x2, y2)) -> (y_slice, x_slice) in pixels, by the reference's rule (demo_helpers/crop_ui.py,
-    make_crop_slices_from_xy1xy2_norm): the corners times (w, h) as a float32 product, rounded half to even, clipped to [0, w] x [0, h]; a side
-    shorter than its minimum falls back to the image's full extent. Corners are not reordered (a reversed box gives an empty slice, as there)."""
-    full_h, full_w = int(image_shape[0]), int(image_shape[1])
-    norm = np.asarray(crop_xy1xy2_norm, dtype=np.float32)
-    if norm.shape != (2, 2):
-        raise TypeError(f"a normalised crop is ((x1, y1), (x2, y2)), got shape {norm.shape}")
-    limits = np.array([full_w, full_h], dtype=np.int32)
-    px = np.clip(np.round(norm * limits.astype(np.float32)).astype(np.int32), 0, limits)
-    (x1, y1), (x2, y2) = px.tolist()
-    if abs(x2 - x1) < minimum_crop_xy[0]:
-        x1, x2 = 0, full_w
-    if abs(y2 - y1) < minimum_crop_xy[1]:
-        y1, y2 = 0, full_h
-    return slice(y1, y2), slice(x1, x2)
-
-
-def _is_crop(crop) -> bool:
-    """a crop argument: a (y_slice, x_slice) pair, or ((x1, y1), (x2, y2)) in normalised units"""
-    if not isinstance(crop, (tuple, list)) or len(crop) != 2:
-        return False
-    if all(isinstance(c, slice) for c in crop):
-        return True
-    real = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)  # noqa: E731
-    return all(isinstance(c, (tuple, list, np.ndarray)) and len(c) == 2 and all(real(v) for v in c) for c in crop)
-
-
-def _crop_box(image_hw, crop) -> tuple[int, int, int, int]:
-    """A crop argument on an image of (h, w) -> the pixel box (x1, y1, x2, y2), half-open; None is the full image. Slices mean what they mean
-    in image[y_slice, x_slice] (negative and open ends included); a normalised box goes through crop_slices_from_norm. Host-side only."""
-    h, w = int(image_hw[0]), int(image_hw[1])
-    if crop is None:
-        return 0, 0, w, h
-    if not _is_crop(crop):
-        raise TypeError(f"a crop is ((x1, y1), (x2, y2)) in normalised units or a (y_slice, x_slice) pair, got {crop!r}")
-    ys, xs = crop if isinstance(crop[0], slice) else crop_slices_from_norm((h, w), crop)
-    (y1, y2, sy), (x1, x2, sx) = ys.indices(h), xs.indices(w)
-    if sy != 1 or sx != 1:
-        raise ValueError(f"crop slices must have step 1, got {ys}, {xs}")
-    if x2 <= x1 or y2 <= y1:
-        raise ValueError(f"the crop {crop!r} of a {h}x{w} image is empty")
-    return x1, y1, x2, y2
-
-
-def _crop_host(image_bgr, crop):
-    """image_bgr[y_slice, x_slice] of a host image as a view (nothing is copied; the staging copy reads the box's bytes only)"""
-    if not (isinstance(image_bgr, np.ndarray) and image_bgr.ndim == 3):
-        raise TypeError("a crop needs an OpenCV-style uint8 HxWx3 BGR image (cv2.imread output)")
-    x1, y1, x2, y2 = _crop_box(image_bgr.shape[0:2], crop)
-    return image_bgr[y1:y2, x1:x2]
-
-
-def _row_pitch(t: Tensor) -> int:
-    """bytes between the rows of a uint8 [..., h, w, 3] device tensor that _in_place() accepted (a single row has no pitch: packed)"""
-    return int(t.stride(-3)) if t.shape[-3] > 1 else 3 * int(t.shape[-2])
-
-
-def _in_place(t: Tensor) -> bool:
-    """Whether the im2col kernel can read a uint8 [h,w,3] / [B,h,w,3] device tensor where it lies: innermost strides (3, 1), rows at least a
-    row apart ([..., pitch, 3, 1]), frames any positive distance apart. Sliced views of packed tensors are of this kind."""
-    if t.stride(-1) != 1 or t.stride(-2) != 3 or (t.shape[-3] > 1 and t.stride(-3) < 3 * t.shape[-2]):
-        return False
-    return t.dim() == 3 or t.shape[0] == 1 or t.stride(0) > 0
-
-
-def _check_frames(images_bgr):
-    """Argument checks of DPTModel.inference_batch (host-side only, nothing touches a GPU) -> (frames, on_device, (H, W)): frames is the
-    ndarray / list as given, or a [B,H,W,3] CUDA tensor the kernel can read in place (_in_place: as given, e.g. a sliced view; any other
-    layout is made contiguous)."""
-    if isinstance(images_bgr, torch.Tensor):
-        if images_bgr.dtype != torch.uint8 or images_bgr.dim() != 4 or images_bgr.shape[3] != 3:
-            raise TypeError(f"inference_batch expects uint8 BxHxWx3 BGR frames, got a {images_bgr.dtype} tensor of shape {tuple(images_bgr.shape)}")
-        if images_bgr.shape[0] == 0:
-            raise ValueError("inference_batch got no frames")
-        if images_bgr.device.type != "cuda":
-            images_bgr = images_bgr.numpy()
-        else:
-            return images_bgr if _in_place(images_bgr) else images_bgr.contiguous(), True, tuple(images_bgr.shape[1:3])
-    if isinstance(images_bgr, np.ndarray):
-        if images_bgr.dtype != np.uint8 or images_bgr.ndim != 4 or images_bgr.shape[3] != 3:
-            raise TypeError(f"inference_batch expects uint8 BxHxWx3 BGR frames, got a {images_bgr.dtype} array of shape {images_bgr.shape}")
-        if images_bgr.shape[0] == 0:
-            raise ValueError("inference_batch got no frames")
-        return images_bgr, False, images_bgr.shape[1:3]
-    if not isinstance(images_bgr, (list, tuple)):
-        raise TypeError(f"inference_batch expects a uint8 [B,H,W,3] ndarray / CUDA tensor or a list of HxWx3 uint8 arrays, got {type(images_bgr)}")
-    if len(images_bgr) == 0:
-        raise ValueError("inference_batch got no frames")
-    for f in images_bgr:
-        if not (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3):
-            raise TypeError("inference_batch expects OpenCV-style uint8 HxWx3 BGR frames (cv2.imread output)")
-    shapes = {f.shape for f in images_bgr}
-    if len(shapes) != 1:
-        raise ValueError(f"inference_batch needs frames of one size, got {sorted(shapes)}")
-    return list(images_bgr), False, images_bgr[0].shape[0:2]
-
-
-def _check_images(images_bgr, batch_size) -> tuple[list, bool]:
-    """Argument checks of DPTModel.inference_images (host-side only, nothing touches a GPU) -> (images, on_device): a list of uint8 HxWx3
-    ndarrays, or of uint8 HxWx3 CUDA tensors the kernel can read in place (_in_place; any other layout is made contiguous)."""
-    if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)):
-        raise TypeError(f"inference_images: batch_size must be an int, got {type(batch_size)}")
-    if batch_size < 1:
-        raise ValueError(f"inference_images: batch_size must be at least 1, got {batch_size}")
-    if not isinstance(images_bgr, (list, tuple)):
-        raise TypeError(f"inference_images expects a list of uint8 HxWx3 BGR images (ndarrays or CUDA tensors), got {type(images_bgr)}")
-    if len(images_bgr) == 0:
-        raise ValueError("inference_images got no images")
-    n_dev = sum(isinstance(f, torch.Tensor) for f in images_bgr)
-    if 0 < n_dev < len(images_bgr):
-        raise TypeError("inference_images expects host arrays or device tensors, not a mix of both")
-    on_device = n_dev > 0
-    for f in images_bgr:
-        if on_device:
-            ok = f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 3 and f.device.type == "cuda"
-        else:
-            ok = isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3
-        if not ok:
-            raise TypeError("inference_images expects OpenCV-style uint8 HxWx3 BGR images (cv2.imread output), or uint8 HxWx3 CUDA tensors")
-        if f.shape[0] == 0 or f.shape[1] == 0:
-            raise ValueError(f"inference_images got an empty image ({f.shape[0]}x{f.shape[1]})")
-    if on_device and len({f.device for f in images_bgr}) != 1:
-        raise RuntimeError("inference_images: the device tensors are on different devices")
-    return [(f if _in_place(f) else f.contiguous()) if on_device else f for f in images_bgr], on_device
-
-
-def _check_crops(crops, n_images: int) -> list:
-    """The `crops` argument of DPTModel.inference_images -> one crop (or None) per image: None, one crop for all, or a list of one per image."""
-    if crops is None or _is_crop(crops):
-        return [crops] * n_images
-    if not isinstance(crops, (list, tuple)) or not all(c is None or _is_crop(c) for c in crops):
-        raise TypeError("crops is one crop for all images or a list of one crop (or None) per image; a crop is ((x1, y1), (x2, y2)) in normalised "
-                        "units or a (y_slice, x_slice) pair")
-    if len(crops) != n_images:
-        raise ValueError(f"{n_images} images but {len(crops)} crops")
-    return list(crops)
-
-
-def _check_regions(regions, image_shapes) -> list[tuple[int, int, int, int, int]]:
-    """The `regions` argument of DPTModel.inference_regions (host-side only): (image_index, x1, y1, x2, y2) pixel boxes, half-open, inside their image."""
-    if not isinstance(regions, (list, tuple, np.ndarray)):
-        raise TypeError(f"inference_regions expects a list of (image_index, x1, y1, x2, y2) boxes, got {type(regions)}")
-    if len(regions) == 0:
-        raise ValueError("inference_regions got no regions")
-    out = []
-    for k, r in enumerate(regions):
-        if not hasattr(r, "__len__") or len(r) != 5 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in r):
-            raise TypeError(f"region {k} must be five ints (image_index, x1, y1, x2, y2), got {r!r}")
-        i, x1, y1, x2, y2 = (int(v) for v in r)
-        if not 0 <= i < len(image_shapes):
-            raise IndexError(f"region {k}: image index {i} is outside [0, {len(image_shapes)})")
-        h, w = int(image_shapes[i][0]), int(image_shapes[i][1])
-        if not (0 <= x1 < x2 <= w and 0 <= y1 < y2 <= h):
-            raise ValueError(f"region {k}: box ({x1}, {y1})-({x2}, {y2}) is empty or outside its {h}x{w} image")
-        out.append((i, x1, y1, x2, y2))
-    return out
-
-
-def region_chunks(regions, scaled_hw, batch_size: int):
-    """Forward plan of DPTModel.inference_regions (pure host code): image_chunks on the BOX sizes - the reference applies its size rule to the
-    cropped frame - so the indices are region indices."""
-    return image_chunks([(y2 - y1, x2 - x1) for _, x1, y1, x2, y2 in regions], scaled_hw, batch_size)
-
-
-def image_chunks(sizes_hw, scaled_hw, batch_size: int) -> list[tuple[tuple[int, int], list[int]]]:
-    """Forward plan of DPTModel.inference_images (pure host code): image sizes [(h, w), ...] and the size rule scaled_hw(h, w) -> model
-    tensor (H, W) -> [((H, W), [image indices]), ...]. A group is every image with the same tensor size, groups in order of first appearance,
-    indices in input order; each group is cut into chunks of at most batch_size images, one batched forward each."""
-    groups: dict[tuple[int, int], list[int]] = {}
-    for i, (h, w) in enumerate(sizes_hw):
-        groups.setdefault(tuple(int(v) for v in scaled_hw(int(h), int(w))), []).append(i)
-    return [(hw, idx[k:k + batch_size]) for hw, idx in groups.items() for k in range(0, len(idx), batch_size)]
 
 
 class _Engine:
@@ -1004,13 +828,17 @@ class DPTModel(nn.Module):
         from .export import export_model
         return export_model(self, path, dtype)
 
+    def _listening(self) -> bool:
+        """Whether somebody is listening on an attention softmax module or on an encoder block (a registered forward hook): forward() then goes
+        stage by stage, and the uint8 routes hand it the prepared tensor instead of fusing prepare into the patch embedding."""
+        enc = self.imgencoder.__dict__
+        return (any(len(pr._forward_hooks) > 0 for pr in enc.get("_softmax_probes") or ())
+                or any(len(node._forward_hooks) > 0 for node, _ in enc.get("_block_probes") or ()))
+
     # ---- reference API
     def forward(self, image_rgb_normalized_bchw: Tensor) -> Tensor:
         """[B,3,H,W] normalised RGB -> inverse depth [B,H,W] (dpt_model.py:61-83), one fused C-ABI call."""
-        probes = self.imgencoder.__dict__.get("_softmax_probes") or []
-        blocks = self.imgencoder.__dict__.get("_block_probes") or []
-        if any(len(pr._forward_hooks) > 0 for pr in probes) or any(len(node._forward_hooks) > 0 for node, _ in blocks):
-            # somebody is listening on attention softmax modules or on blocks: go stage by stage so the encoder can dump what they see
+        if self._listening():  # go stage by stage so the encoder can dump what the hooks see
             tokens, hw = self.patch_embed(image_rgb_normalized_bchw)
             return self.head(self.fusion(*self.reassemble(*self.imgencoder(tokens, hw), hw)))
         eng = self._get_engine()
@@ -1048,12 +876,10 @@ class DPTModel(nn.Module):
         if crop is not None:
             image_bgr = _crop_host(image_bgr, crop)
         with torch.inference_mode():
-            probes = self.imgencoder.__dict__.get("_softmax_probes") or []
-            blocks = self.imgencoder.__dict__.get("_block_probes") or []
             pe = self.patch_embed
             scaled_hw, interp, p, img_dtype = pe._prepare_plan(image_bgr, max_side_length, use_square_sizing, "bilinear")
-            if img_dtype != p.dtype or any(len(pr._forward_hooks) > 0 for pr in probes) or any(len(node._forward_hooks) > 0 for node, _ in blocks):
-                return self(pe.prepare_image(image_bgr, max_side_length, use_square_sizing))  # (hooks listening: the stage-by-stage route of forward())
+            if img_dtype != p.dtype or self._listening():
+                return self(pe._prepare_view(image_bgr, scaled_hw, interp, p, img_dtype))  # (hooks listening: the stage-by-stage route of forward())
             # mdpt_forward_bgr: the im2col kernel of the patch embedding reads the uint8 image itself (prepare_image fused into patchify) - same bits as
             # prepare_image + forward, one launch and one trip of the image through memory fewer
             eng = self._get_engine()
@@ -1082,26 +908,14 @@ class DPTModel(nn.Module):
             frames = [f[y1:y2, x1:x2] for f in frames] if isinstance(frames, list) else frames[:, y1:y2, x1:x2]
             img_h, img_w = y2 - y1, x2 - x1
         pe = self.patch_embed
-        p = next(self.parameters())
-        if p.device.type != "cuda":
-            raise RuntimeError("inference_batch runs on the GPU only (no CPU fallback): move the model to a cuda device first")
-        if on_device and frames.device != p.device:
-            raise RuntimeError(f"Expected all tensors to be on the same device, model is on {p.device} but the frames are on {frames.device}")
-        scaled_hw = pe._scaled_hw(img_h, img_w, max_side_length, use_square_sizing)
+        p, img_dtype = pe._target("inference_batch", frames.device if on_device else None, "frames")
+        h, w = pe._scaled_hw(img_h, img_w, max_side_length, use_square_sizing)
         b = len(frames)
         with torch.inference_mode():
-            probes = self.imgencoder.__dict__.get("_softmax_probes") or []
-            blocks = self.imgencoder.__dict__.get("_block_probes") or []
-            img_dtype = p.dtype if p.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
-            if img_dtype != p.dtype or any(len(pr._forward_hooks) > 0 for pr in probes) or any(len(node._forward_hooks) > 0 for node, _ in blocks):
+            if img_dtype != p.dtype or self._listening():
                 # hooks listening: the stage-by-stage route of forward(), on the tensor prepare_image_bgr gives per frame
-                if on_device:
-                    x = torch.cat([pe._prepare_device(frames[i], img_h, img_w, scaled_hw, native.INTERP_BILINEAR, p, img_dtype) for i in range(b)])
-                else:
-                    x = torch.cat([pe.prepare_image(f, max_side_length, use_square_sizing) for f in frames])
-                return self(x)
+                return self(torch.cat([pe._prepare_view(f, (h, w), native.INTERP_BILINEAR, p, img_dtype) for f in frames]))
             eng = self._get_engine()
-            h, w = scaled_hw
             with torch.cuda.device(p.device):
                 src = frames if on_device else pe._stage_host_image(frames, p.device)
                 out = torch.empty((b, h, w), device=p.device, dtype=eng.dtype)
@@ -1114,73 +928,69 @@ class DPTModel(nn.Module):
                                      mean3, std3, native.INTERP_BILINEAR, out, native.dtype_code(out.dtype), size_hw=(h, w), batch=b)
             return out
 
+    def _run_view_chunks(self, views: list, chunks, p, img_dtype, boxed: bool = False) -> list[Tensor]:
+        """The runner of the table routes (inference_images, inference_regions). views: uint8 [h,w,3] views, all host ndarrays (views of images
+        included) or all device tensors _in_place() accepted; chunks: the forward plan [((H, W), [view indices]), ...] (image_chunks). One batched
+        forward per chunk -> element i the [1,H,W] map of view i, a view into its chunk's output.
+        A chunk is one mdpt_forward_bgr_frames call on a table of (pointer, h, w) entries when every view is packed, else - or always, with
+        `boxed` - one mdpt_forward_bgr_regions call whose entries carry the view's row pitch and the full box: a view read in place IS a frame with
+        its own pitch. Host views are copied view by view into the pinned staging buffer in one go (the staged bytes are the views' bytes, not the
+        images'; view k starts where view k-1 ends, packed). With hooks listening (or a model dtype the kernels do not write) the chunk takes the
+        stage-by-stage route of forward() on the per-view prepared tensors instead."""
+        pe = self.patch_embed
+        on_device = isinstance(views[0], torch.Tensor)
+        out: list[Tensor | None] = [None] * len(views)
+        with torch.inference_mode():
+            staged = img_dtype != p.dtype or self._listening()
+            eng = None if staged else self._get_engine()
+            mean3, std3 = pe._norm_constants()
+            for (h, w), idx in chunks:
+                chunk = [views[i] for i in idx]
+                b = len(chunk)
+                if staged:
+                    y = self(torch.cat([pe._prepare_view(v, (h, w), native.INTERP_BILINEAR, p, img_dtype) for v in chunk]))
+                else:
+                    with torch.cuda.device(p.device):
+                        if on_device:
+                            ptrs = [v.data_ptr() for v in chunk]
+                            packed = all(v.is_contiguous() for v in chunk)
+                        else:
+                            src = pe._stage_host_image(chunk, p.device)
+                            ptrs = [src.data_ptr() + int(o) for o in np.cumsum([0] + [v.size for v in chunk[:-1]])]
+                            packed = True
+                        ptr_arr = np.asarray(ptrs, dtype=np.uint64)
+                        hw_arr = np.asarray([v.shape[0:2] for v in chunk], dtype=np.int32).ravel()
+                        if packed and not boxed:
+                            fn_name, table = "mdpt_forward_bgr_frames", ()
+                        else:
+                            pitch_arr = None if packed else np.asarray([_row_pitch(v) for v in chunk], dtype=np.int64)
+                            box_arr = np.asarray([(0, 0, v.shape[1], v.shape[0]) for v in chunk], dtype=np.int32).ravel()
+                            fn_name, table = "mdpt_forward_bgr_regions", (None if packed else pitch_arr.ctypes.data, box_arr.ctypes.data)
+                        y = torch.empty((b, h, w), device=p.device, dtype=eng.dtype)
+                        eng.call_checked(fn_name, ptr_arr.ctypes.data, hw_arr.ctypes.data, *table, b, native.dtype_code(img_dtype), h, w, mean3, std3,
+                                         native.INTERP_BILINEAR, y, native.dtype_code(y.dtype), size_hw=(h, w), batch=b)
+                for k, i in enumerate(idx):
+                    out[i] = y[k:k + 1]
+        return out
+
     def inference_images(self, images_bgr, max_side_length: int | None = None, use_square_sizing: bool = True, batch_size: int = 32, *,
                          crops=None) -> list[Tensor]:
         """inference() for a list of images of ANY sizes (not in the reference; its run_image.py loops over files) -> a list in input order, element
         i the [1,H_i,W_i] map of image i in the model dtype (a view into its chunk's output). Takes uint8 HxWx3 BGR ndarrays, or uint8 HxWx3 CUDA
         tensors on the model's device (not a mix). Images whose size rule gives the same tensor size share batched forwards of at most batch_size
-        images (image_chunks; square sizing, the default, gives every image the same size), each one mdpt_forward_bgr_frames call reading every
-        image from its own place. Element i equals model(torch.cat([prepare_image_bgr(f) for f in its chunk]))[its row] bit for bit; in the
-        default (batch-invariant) modes that is inference(image i). crops: one crop for all images or a list of one (or None) per image (see
-        inference): element i is then the map of images[i][y_slice, x_slice], its size rule applied to the box; device images are read in place,
-        host images staged box by box."""
+        images (image_chunks; square sizing, the default, gives every image the same size), each one call reading every image from its own place
+        (_run_view_chunks). Element i equals model(torch.cat([prepare_image_bgr(f) for f in its chunk]))[its row] bit for bit; in the default
+        (batch-invariant) modes that is inference(image i). crops: one crop for all images or a list of one (or None) per image (see inference):
+        element i is then the map of the view images[i][y_slice, x_slice], its size rule applied to the box."""
         images, on_device = _check_images(images_bgr, batch_size)
         crops = _check_crops(crops, len(images))
         if any(c is not None for c in crops):
             boxes = [_crop_box(f.shape[0:2], c) for f, c in zip(images, crops)]
             images = [f[y1:y2, x1:x2] for f, (x1, y1, x2, y2) in zip(images, boxes)]
         pe = self.patch_embed
-        p = next(self.parameters())
-        if p.device.type != "cuda":
-            raise RuntimeError("inference_images runs on the GPU only (no CPU fallback): move the model to a cuda device first")
-        if on_device and images[0].device != p.device:
-            raise RuntimeError(f"Expected all tensors to be on the same device, model is on {p.device} but the images are on {images[0].device}")
+        p, img_dtype = pe._target("inference_images", images[0].device if on_device else None, "images")
         chunks = image_chunks([f.shape[0:2] for f in images], lambda h, w: pe._scaled_hw(h, w, max_side_length, use_square_sizing), batch_size)
-        out: list[Tensor | None] = [None] * len(images)
-        with torch.inference_mode():
-            probes = self.imgencoder.__dict__.get("_softmax_probes") or []
-            blocks = self.imgencoder.__dict__.get("_block_probes") or []
-            img_dtype = p.dtype if p.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
-            staged = img_dtype != p.dtype or any(len(pr._forward_hooks) > 0 for pr in probes) or any(len(node._forward_hooks) > 0 for node, _ in blocks)
-            eng = None if staged else self._get_engine()
-            mean3, std3 = pe._norm_constants()
-            for (h, w), idx in chunks:
-                b = len(idx)
-                if staged:
-                    # hooks listening: the stage-by-stage route of forward(), on the tensor prepare_image_bgr gives per image
-                    if on_device:
-                        x = torch.cat([pe._prepare_device(images[i], images[i].shape[0], images[i].shape[1], (h, w), native.INTERP_BILINEAR, p, img_dtype)
-                                       for i in idx])
-                    else:
-                        x = torch.cat([pe.prepare_image(images[i], max_side_length, use_square_sizing) for i in idx])
-                    y = self(x)
-                else:
-                    with torch.cuda.device(p.device):
-                        pitches = None
-                        if on_device:
-                            ptrs = [images[i].data_ptr() for i in idx]
-                            if not all(images[i].is_contiguous() for i in idx):  # boxes / sliced views, read in place with their images' row pitches
-                                pitches = [_row_pitch(images[i]) for i in idx]
-                        else:
-                            # one pinned staging copy for the chunk: image k starts where image k-1 ends
-                            src = pe._stage_host_image([images[i] for i in idx], p.device)
-                            offs = np.cumsum([0] + [images[i].size for i in idx[:-1]])
-                            ptrs = [src.data_ptr() + int(o) for o in offs]
-                        ptr_arr = np.asarray(ptrs, dtype=np.uint64)
-                        hw_arr = np.asarray([images[i].shape[0:2] for i in idx], dtype=np.int32).ravel()
-                        y = torch.empty((b, h, w), device=p.device, dtype=eng.dtype)
-                        if pitches is None:
-                            eng.call_checked("mdpt_forward_bgr_frames", ptr_arr.ctypes.data, hw_arr.ctypes.data, b, native.dtype_code(img_dtype), h, w, mean3,
-                                             std3, native.INTERP_BILINEAR, y, native.dtype_code(y.dtype), size_hw=(h, w), batch=b)
-                        else:  # every view is the whole of a "frame" with its own pitch
-                            pitch_arr = np.asarray(pitches, dtype=np.int64)
-                            box_arr = np.asarray([(0, 0, images[i].shape[1], images[i].shape[0]) for i in idx], dtype=np.int32).ravel()
-                            eng.call_checked("mdpt_forward_bgr_regions", ptr_arr.ctypes.data, hw_arr.ctypes.data, pitch_arr.ctypes.data, box_arr.ctypes.data, b,
-                                             native.dtype_code(img_dtype), h, w, mean3, std3, native.INTERP_BILINEAR, y, native.dtype_code(y.dtype),
-                                             size_hw=(h, w), batch=b)
-                for k, i in enumerate(idx):
-                    out[i] = y[k:k + 1]
-        return out
+        return self._run_view_chunks(images, chunks, p, img_dtype)
 
     def inference_regions(self, images, regions, max_side_length: int | None = None, use_square_sizing: bool = True, batch_size: int = 32) -> list[Tensor]:
         """Depth of BOXES of images, batched (not in the reference, whose demos crop one frame and predict): images as inference_images takes them
@@ -1188,61 +998,20 @@ class DPTModel(nn.Module):
         half-open - any number per image, overlapping or not (detector boxes, tiles of a large photo) -> one [1,H_r,W_r] map per region, in region
         order. Region r equals inference(np.ascontiguousarray(image[y1:y2, x1:x2])) bit for bit in the default (batch-invariant) modes: the size
         rule is applied to the box's size, and the antialias taps stop at the box's edges. Regions whose boxes get the same tensor size share
-        batched forwards of at most batch_size regions (region_chunks), one mdpt_forward_bgr_regions call each.
-        Device images are read where they lie (base pointer, row pitch, box): no packed copy of any box is made. Host images are copied box by
-        box into the pinned staging buffer, so the staged bytes are the boxes' bytes, not the images' - which also means that MANY OVERLAPPING
-        regions of one host image are staged once each: put such an image on the device once (torch.from_numpy(image).cuda()) instead."""
+        batched forwards of at most batch_size regions (region_chunks), one mdpt_forward_bgr_regions call each (_run_view_chunks).
+        No packed copy of any box of a device image is made. MANY OVERLAPPING regions of one host image are staged once each: put such an image on
+        the device once (torch.from_numpy(image).cuda()) instead."""
         images, on_device = _check_images(images, batch_size)
         regions = _check_regions(regions, [f.shape for f in images])
         pe = self.patch_embed
-        p = next(self.parameters())
-        if p.device.type != "cuda":
-            raise RuntimeError("inference_regions runs on the GPU only (no CPU fallback): move the model to a cuda device first")
-        if on_device and images[0].device != p.device:
-            raise RuntimeError(f"Expected all tensors to be on the same device, model is on {p.device} but the images are on {images[0].device}")
+        p, img_dtype = pe._target("inference_regions", images[0].device if on_device else None, "images")
         chunks = region_chunks(regions, lambda h, w: pe._scaled_hw(h, w, max_side_length, use_square_sizing), batch_size)
-        out: list[Tensor | None] = [None] * len(regions)
-        with torch.inference_mode():
-            probes = self.imgencoder.__dict__.get("_softmax_probes") or []
-            blocks = self.imgencoder.__dict__.get("_block_probes") or []
-            img_dtype = p.dtype if p.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
-            staged = img_dtype != p.dtype or any(len(pr._forward_hooks) > 0 for pr in probes) or any(len(node._forward_hooks) > 0 for node, _ in blocks)
-            eng = None if staged else self._get_engine()
-            mean3, std3 = pe._norm_constants()
-            view = lambda r: images[regions[r][0]][regions[r][2]:regions[r][4], regions[r][1]:regions[r][3]]  # noqa: E731
-            for (h, w), idx in chunks:
-                b = len(idx)
-                if staged:
-                    # hooks listening: the stage-by-stage route of forward(), on the tensor the region form of prepare gives per box
-                    if on_device:
-                        x = torch.cat([pe._prepare_device(view(r), view(r).shape[0], view(r).shape[1], (h, w), native.INTERP_BILINEAR, p, img_dtype) for r in idx])
-                    else:
-                        x = torch.cat([pe.prepare_image(view(r), max_side_length, use_square_sizing) for r in idx])
-                    y = self(x)
-                else:
-                    with torch.cuda.device(p.device):
-                        if on_device:
-                            ptrs = [images[regions[r][0]].data_ptr() for r in idx]
-                            hws = [images[regions[r][0]].shape[0:2] for r in idx]
-                            pitch_arr = np.asarray([_row_pitch(images[regions[r][0]]) for r in idx], dtype=np.int64)
-                            box_arr = np.asarray([regions[r][1:] for r in idx], dtype=np.int32).ravel()
-                        else:
-                            # one pinned staging copy for the chunk, box by box: box k starts where box k-1 ends, packed
-                            src = pe._stage_host_image([view(r) for r in idx], p.device)
-                            offs = np.cumsum([0] + [view(r).size for r in idx[:-1]])
-                            ptrs = [src.data_ptr() + int(o) for o in offs]
-                            hws = [view(r).shape[0:2] for r in idx]
-                            pitch_arr = None
-                            box_arr = np.asarray([(0, 0, hw[1], hw[0]) for hw in hws], dtype=np.int32).ravel()
-                        ptr_arr = np.asarray(ptrs, dtype=np.uint64)
-                        hw_arr = np.asarray(hws, dtype=np.int32).ravel()
-                        y = torch.empty((b, h, w), device=p.device, dtype=eng.dtype)
-                        eng.call_checked("mdpt_forward_bgr_regions", ptr_arr.ctypes.data, hw_arr.ctypes.data, None if pitch_arr is None else pitch_arr.ctypes.data,
-                                         box_arr.ctypes.data, b, native.dtype_code(img_dtype), h, w, mean3, std3, native.INTERP_BILINEAR, y,
-                                         native.dtype_code(y.dtype), size_hw=(h, w), batch=b)
-                for k, r in enumerate(idx):
-                    out[r] = y[k:k + 1]
-        return out
+        # A region is nothing but the view image[y1:y2, x1:x2], on the host and on the device alike. For a device image the library gets the view's
+        # own pointer and row pitch with a full box instead of the base pointer and the box: the same frame-table entry - first byte
+        # base + y1 * pitch + 3 * x1, the image's pitch, the box's size - so the same map (a one-row view counts as packed: its pitch is never
+        # used). _check_regions has put every box inside its image, so every view is what the box names.
+        views = [images[i][y1:y2, x1:x2] for i, x1, y1, x2, y2 in regions]
+        return self._run_view_chunks(views, chunks, p, img_dtype, boxed=True)
 
     def prepare_image_bgr(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True,
                           interpolation_mode: str = "bilinear", *, crop=None) -> Tensor:
