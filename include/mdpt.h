@@ -511,6 +511,43 @@ int mdpt_post_mesh(const void* frames_bgra, int32_t B, int32_t H, int32_t W, int
                    double tan_half_fov, double x_scale, double y_scale, double edge_threshold, int32_t is_metric, int32_t mode, void* xyz_f32,
                    void* uv_f32, void* faces_u32, void* counts_i32, void* bounds_f32, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Tiled high-resolution inference on the device (additive to ABI v6): the depth maps of T overlapping tiles of one H x W photo (what
+ * mdpt_forward_bgr_regions returns for the tiles' boxes) put together into one fp32 map at the photo's resolution. Every forward of a relative-depth
+ * model has its own unknown scale and shift (the reference's .readme_assets/results_explainer.md, "Results are scene-specific!"); its "Fitting to
+ * (more) known data" names a least-squares fit of the two terms and has no code for it. Here the whole photo inferred once at model size is the
+ * guide (gh x gw, covering the photo), every tile is fitted to the guide over its own box, and the fitted tiles are feather-blended. fp64
+ * arithmetic, nothing contracted, rounded to fp32 once; nothing is read back, nothing synchronises; both calls are bit-deterministic.
+ * A tile is an mdpt_tile record: its map (device pointer, h x w elements of map_dtype) and its half-open pixel box (x1, y1, x2, y2), bw = x2 - x1,
+ * bh = y2 - y1. The kernels read the table from DEVICE memory (tiles_dev: the caller's upload of the T records, 8-byte aligned), so T is not bounded
+ * by a kernel's arguments; tiles_host is the same table on the host, read during the call for the argument checks only.
+ *   mdpt_post_tile_scratch_bytes .. the device scratch mdpt_post_tile_fit needs for this table (the partial sums)
+ *   mdpt_post_tile_fit ............ one sample per tile-map pixel (j, i): x = m[j, i]; y = the guide sampled bilinearly (fp64 weights, rows first)
+ *                                   at u = X gw / W - 0.5, v = Y gh / H - 0.5 clamped to the guide, (X, Y) = (x1 + (i + 0.5) bw / w,
+ *                                   y1 + (j + 0.5) bh / h) the pixel's centre in the photo; a sample whose x or y is not finite is skipped.
+ *                                   sums_f64 [T, 6] = {n, Sx, Sy, Sxx, Sxy, Syy}: every workgroup reduces a fixed chunk of 2048 samples with a
+ *                                   fixed tree, a second launch adds each tile's partials in chunk order (no float atomics, no workgroup waits for
+ *                                   another). fit_f64 [T, 2] = {s, t}: var = n Sxx - Sx^2, s = (n Sxy - Sx Sy) / var, t = (Sy - s Sx) / n. A
+ *                                   degenerate tile (n < 2, var <= 0, s not finite or <= 0) gets s = 0, t = Sy / n, the guide's mean; n == 0
+ *                                   gives t = 0 and marks the tile empty (sums[t][0] == 0). T <= 65535.
+ *   mdpt_post_tile_blend .......... out_f32 [H, W]: per pixel, over the tiles whose box holds it, in table order, skipping empty tiles (sums_f64
+ *                                   != NULL: n == 0): out = (float)(sum w z / sum w), z = s val + t (fit_f64 == NULL: s = 1, t = 0), val =
+ *                                   cv2.resize(map, (bw, bh)) at (Y - y1, X - x1) by the CV_64F rule of the depth masking block above (one change: a
+ *                                   lerp of two equal taps is that tap, so constant tiles blend to exactly their constant; finite taps move by at
+ *                                   most the rounding of the weights, equal infinite taps give that infinity under both rules), w = wx wy,
+ *                                   wx = min(1, (dx + 1) / (feather + 1)) with dx the distance in pixels to the nearer of the tile's left and
+ *                                   right edge columns - an edge on the photo's border does not count, so the photo's own border has no ramp -
+ *                                   and wy likewise. A pixel no tile covers is NaN; a z that is not finite propagates. feather >= 0, finite. The
+ *                                   photo must need fewer than 2^24 blocks of 64 x 16 pixels, a tile map fewer than 2^24 chunks.
+ * Both calls check on the host that every box lies inside the photo, that sizes are positive and that pointers are aligned (maps to their
+ * element, the fp64 buffers to 8 bytes, out_f32 to 4), and launch nothing otherwise. */
+typedef struct mdpt_tile { const void* map; int32_t h, w; int32_t x1, y1, x2, y2; } mdpt_tile;
+int mdpt_post_tile_scratch_bytes(const mdpt_tile* tiles_host, int32_t T, size_t* bytes);
+int mdpt_post_tile_fit(const mdpt_tile* tiles_host, const void* tiles_dev, int32_t T, int32_t map_dtype, const void* guide, int32_t guide_dtype,
+                       int32_t guide_h, int32_t guide_w, int32_t H, int32_t W, void* fit_f64, void* sums_f64, void* scratch, size_t scratch_bytes,
+                       void* stream);
+int mdpt_post_tile_blend(const mdpt_tile* tiles_host, const void* tiles_dev, int32_t T, int32_t map_dtype, int32_t H, int32_t W, const void* fit_f64,
+                         const void* sums_f64, double feather, void* out_f32, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

@@ -230,6 +230,14 @@ struct MeshJob {
 };
 inline size_t mesh_blocks(size_t n) { return (n + 255) / 256; }  // the compaction's blocks: 256 vertices (or grid cells) each
 
+// one tile of tiled high-resolution inference (postprocess.hip tile_* kernels; = mdpt_tile of include/mdpt.h): its h x w map (the table's dtype) and
+// its half-open pixel box in the photo. The table lives in DEVICE memory (any number of tiles); the kernels index it by tile.
+struct PostTile { const void* map; int h, w, x1, y1, x2, y2; };
+// samples of one tile map that one workgroup of the fit reduces (256 threads x 8): the partial sums of tile t's chunk c are the 6 doubles at
+// parts[(t max_chunks + c) 6], max_chunks = the chunks of the call's largest map
+#define MDPT_TILE_FIT_CHUNK 2048
+__host__ __device__ inline size_t tile_fit_chunks(size_t map_elems) { return (map_elems + MDPT_TILE_FIT_CHUNK - 1) / MDPT_TILE_FIT_CHUNK; }
+
 // the same for every block of the encoder in ONE launch (the LUTs depend on weights and window sizes only, not on activations)
 struct SwinCpbBatch {
     const float* w1[32]; const float* b1[32]; const float* w2[32]; float* lut[32];
@@ -281,6 +289,14 @@ int mdpt_launch_post_block_norm_tiles(const PostRunTable& t, unsigned char* out,
 // the kept vertices (xyz [B, nv, 3], uv [B, nv, 2]) and faces ([B, nf, 3] or, for points, [B, nv, 1]) packed at the front of each image's slab,
 // counts [B, 2] = {kept vertices, kept faces}, bounds [B, 2, 3] = {min xyz, max xyz}. Five launches (four for points), no single-pass scan.
 int mdpt_launch_post_mesh(const MeshJob& m, float* xyz, float* uv, unsigned* faces, int* counts, float* bounds, hipStream_t stream);
+// tiled high-resolution inference: tiles = T PostTile records on the device (maps of dtype dt). Fit: every tile's map against the guide (gh x gw,
+// dtype gdt, covering the H x W photo) over the tile's box -> sums [T, 6] fp64 {n, Sx, Sy, Sxx, Sxy, Syy}, fit [T, 2] fp64 {scale, shift}; parts =
+// [T, max_chunks, 6] fp64 scratch. Two launches, bit-deterministic. Blend: the feathered weighted mean of the fitted tiles -> out fp32 [H, W]; fit ==
+// null: scale 1, shift 0; sums != null: a tile with n == 0 is skipped
+int mdpt_launch_post_tile_fit(const PostTile* tiles, int T, int max_chunks, int dt, const void* guide, int gdt, int gh, int gw, int H, int W, double* parts,
+                              double* sums, double* fit, hipStream_t stream);
+int mdpt_launch_post_tile_blend(const PostTile* tiles, int T, int dt, int H, int W, const double* fit, const double* sums, double feather, float* out,
+                                hipStream_t stream);
 
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);

@@ -386,4 +386,73 @@ int mdpt_post_mesh(const void* frames_bgra, int32_t B, int32_t H, int32_t W, int
     return 0;
 }
 
+// ---- tiled high-resolution inference (the fit the reference's results_explainer.md describes under "Fitting to (more) known data")
+static_assert(sizeof(mdpt_tile) == sizeof(PostTile) && sizeof(mdpt_tile) == 32, "mdpt_tile of include/mdpt.h is PostTile of mdpt_kernels.h");
+
+static size_t dtype_bytes(int dt) { return dt == MDPT_DTYPE_F32 ? 4 : 2; }
+
+// the host table: sizes positive, boxes inside the H x W photo (H = 0: boxes only ordered and non-negative), maps aligned to their element;
+// *max_chunks = the fit chunks of the largest map
+static int check_tiles(const mdpt_tile* tiles, int32_t T, int32_t map_dtype, int32_t H, int32_t W, size_t* max_chunks) {
+    if (!tiles) return fail(MDPT_E_INVALID, "null argument");
+    if (T <= 0) return fail(MDPT_E_INVALID, "bad tile count %d", T);
+    size_t most = 0;
+    for (int t = 0; t < T; ++t) {
+        const mdpt_tile& q = tiles[t];
+        if (!q.map || ((uintptr_t)q.map & (dtype_bytes(map_dtype) - 1)) != 0) return fail(MDPT_E_INVALID, "null or misaligned map (tile %d)", t);
+        if (q.h <= 0 || q.w <= 0) return fail(MDPT_E_INVALID, "bad map size %dx%d (tile %d)", q.h, q.w, t);
+        if (!(0 <= q.x1 && q.x1 < q.x2 && 0 <= q.y1 && q.y1 < q.y2) || (H > 0 && (q.x2 > W || q.y2 > H)))
+            return fail(MDPT_E_INVALID, "box (%d, %d)-(%d, %d) of tile %d is empty or outside the %dx%d photo", q.x1, q.y1, q.x2, q.y2, t, H, W);
+        const size_t c = tile_fit_chunks((size_t)q.h * q.w);
+        most = c > most ? c : most;
+    }
+    if (most >= ((size_t)1 << 24)) return fail(MDPT_E_INVALID, "a tile map is too large (fewer than 2^24 chunks of %d samples)", MDPT_TILE_FIT_CHUNK);
+    *max_chunks = most;
+    return 0;
+}
+
+int mdpt_post_tile_scratch_bytes(const mdpt_tile* tiles_host, int32_t T, size_t* bytes) {
+    if (!bytes) return fail(MDPT_E_INVALID, "null argument");
+    size_t max_chunks;
+    CHK(check_tiles(tiles_host, T, MDPT_DTYPE_BF16, 0, 0, &max_chunks));
+    *bytes = (size_t)T * max_chunks * 6 * sizeof(double);
+    return 0;
+}
+
+int mdpt_post_tile_fit(const mdpt_tile* tiles_host, const void* tiles_dev, int32_t T, int32_t map_dtype, const void* guide, int32_t guide_dtype,
+                       int32_t guide_h, int32_t guide_w, int32_t H, int32_t W, void* fit_f64, void* sums_f64, void* scratch, size_t scratch_bytes,
+                       void* stream) {
+    if (!tiles_dev || !guide || !fit_f64 || !sums_f64 || !scratch) return fail(MDPT_E_INVALID, "null argument");
+    if (!tensor_dtype_ok(map_dtype) || !tensor_dtype_ok(guide_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d / %d", map_dtype, guide_dtype);
+    if (H <= 0 || W <= 0 || guide_h <= 0 || guide_w <= 0) return fail(MDPT_E_INVALID, "bad size: photo %dx%d, guide %dx%d", H, W, guide_h, guide_w);
+    if (T > 65535) return fail(MDPT_E_INVALID, "%d tiles: the fit takes at most 65535 per call", T);
+    size_t max_chunks;
+    CHK(check_tiles(tiles_host, T, map_dtype, H, W, &max_chunks));
+    if ((((uintptr_t)tiles_dev | (uintptr_t)fit_f64 | (uintptr_t)sums_f64 | (uintptr_t)scratch) & 7) != 0 ||
+        ((uintptr_t)guide & (dtype_bytes(guide_dtype) - 1)) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table and the fp64 buffers need 8 bytes, the guide its element)");
+    const size_t need = (size_t)T * max_chunks * 6 * sizeof(double);
+    if (scratch_bytes < need) return fail(MDPT_E_INVALID, "tile scratch of %zu bytes, %zu needed (mdpt_post_tile_scratch_bytes)", scratch_bytes, need);
+    CHK(mdpt_launch_post_tile_fit((const PostTile*)tiles_dev, T, (int)max_chunks, map_dtype, guide, guide_dtype, guide_h, guide_w, H, W, (double*)scratch,
+                                  (double*)sums_f64, (double*)fit_f64, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_tile_blend(const mdpt_tile* tiles_host, const void* tiles_dev, int32_t T, int32_t map_dtype, int32_t H, int32_t W, const void* fit_f64,
+                         const void* sums_f64, double feather, void* out_f32, void* stream) {
+    if (!tiles_dev || !out_f32) return fail(MDPT_E_INVALID, "null argument");
+    if (!tensor_dtype_ok(map_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", map_dtype);
+    if (H <= 0 || W <= 0) return fail(MDPT_E_INVALID, "bad photo size %dx%d", H, W);
+    if (!(feather >= 0.0) || feather > 1e300) return fail(MDPT_E_INVALID, "the feather width must be finite and >= 0, got %g", feather);
+    // 64 x 16 pixels per workgroup, one grid axis: fewer than 2^24 workgroups of 256 threads (about 17 gigapixels)
+    if ((((size_t)W + 63) / 64) * (((size_t)H + 15) / 16) >= ((size_t)1 << 24)) return fail(MDPT_E_INVALID, "a photo of %dx%d is too large for one blend", H, W);
+    size_t max_chunks;
+    CHK(check_tiles(tiles_host, T, map_dtype, H, W, &max_chunks));
+    if ((((uintptr_t)tiles_dev | (uintptr_t)fit_f64 | (uintptr_t)sums_f64) & 7) != 0 || ((uintptr_t)out_f32 & 3) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table and the fp64 buffers need 8 bytes, the output 4)");
+    CHK(mdpt_launch_post_tile_blend((const PostTile*)tiles_dev, T, map_dtype, H, W, (const double*)fit_f64, (const double*)sums_f64, feather,
+                                    (float*)out_f32, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

@@ -1013,6 +1013,38 @@ class DPTModel(nn.Module):
         views = [images[i][y1:y2, x1:x2] for i, x1, y1, x2, y2 in regions]
         return self._run_view_chunks(views, chunks, p, img_dtype, boxed=True)
 
+    def inference_tiled(self, image_bgr, tiles=None, tile_hw=None, overlap=0.25, max_side_length: int | None = None, use_square_sizing: bool = True,
+                        batch_size: int = 32, align: str = "affine", return_parts: bool = False):
+        """Depth of one photo at the PHOTO's resolution, for detail beyond the model's tensor size (not in the reference, whose
+        .readme_assets/results_explainer.md explains why tile results cannot simply be pasted and names the fit that cures it) -> fp32 [1,H,W].
+        One inference_regions call - region 0 the whole image, which is the guide, then the tiles - and one postprocess.stitch_tiles call, which
+        fits every tile to the guide with one scale and one shift and feather-blends them on the device. image_bgr: a uint8 HxWx3 ndarray or CUDA
+        tensor on the model's device. Either tiles=(ny, nx), a grid of equal tiles whose neighbours share the fraction `overlap` of a side
+        (tiling.tile_grid_boxes), or tile_hw=(h, w) (or one side), tiles of that size whose neighbours overlap by at least `overlap` - a fraction of
+        the tile side below 1, else pixels (tiling.tile_boxes). max_side_length, use_square_sizing and batch_size are inference_regions', applied to
+        the guide and to every tile; align is stitch_tiles'. return_parts: -> (map, parts) with parts = dict(regions = the maps inference_regions
+        returned, guide first; boxes = the tiles' (x1, y1, x2, y2); fit, sums = stitch_tiles' fit, None with align="none")."""
+        from . import tiling
+        from .postprocess import stitch_tiles
+        if (tiles is None) == (tile_hw is None):
+            raise ValueError("inference_tiled takes either tiles=(ny, nx) or tile_hw=(h, w)")
+        if isinstance(image_bgr, (list, tuple)) or getattr(image_bgr, "ndim", 0) != 3:
+            raise TypeError("inference_tiled expects one uint8 HxWx3 BGR image (an ndarray or a CUDA tensor)")
+        h, w = int(image_bgr.shape[0]), int(image_bgr.shape[1])
+        if tiles is not None:
+            boxes = tiling.tile_grid_boxes((h, w), tiles, overlap)
+        else:
+            th, tw = tile_hw if isinstance(tile_hw, (tuple, list)) else (tile_hw, tile_hw)
+            th, tw = min(int(th), h), min(int(tw), w)
+            oy, ox = (int(round(overlap * th)), int(round(overlap * tw))) if 0 <= overlap < 1 else (int(overlap), int(overlap))
+            boxes = tiling.tile_boxes((h, w), (th, tw), (oy, ox))
+        regions = [(0, 0, 0, w, h)] + [(0, *b) for b in boxes]
+        maps = self.inference_regions([image_bgr], regions, max_side_length, use_square_sizing, batch_size)
+        out = stitch_tiles(maps[1:], boxes, (h, w), guide=maps[0] if align == "affine" else None, align=align, return_fit=return_parts)
+        if not return_parts:
+            return out
+        return out[0], {"regions": maps, "boxes": boxes, "fit": out[1], "sums": out[2]}
+
     def prepare_image_bgr(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True,
                           interpolation_mode: str = "bilinear", *, crop=None) -> Tensor:
         return self.patch_embed.prepare_image(image_bgr, max_side_length, use_square_sizing, interpolation_mode, crop=crop)

@@ -228,6 +228,9 @@ SYMBOLS = {
     "mdpt_post_mesh_grid": (ctypes.c_int, [_I, _I, _D, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mdpt_post_mesh_scratch_bytes": (ctypes.c_int, [_I, _I, _I, ctypes.POINTER(_SZ)]),
     "mdpt_post_mesh": (ctypes.c_int, [_VP, _I, _I, _I, _I, _I, _VP, _D, _D, _D, _D, _D, _D, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "mdpt_post_tile_scratch_bytes": (ctypes.c_int, [_VP, _I, ctypes.POINTER(_SZ)]),
+    "mdpt_post_tile_fit": (ctypes.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "mdpt_post_tile_blend": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

@@ -15,6 +15,9 @@ when the blocks' grids differ (SwinV2).
 For one image or several, --mesh DIR saves the 3D viewer's "Save 3D Model" result (postprocess.pack_depth_u24_frames -> depth_frames_to_mesh ->
 mesh_io): <name>.glb with the photo as its texture, or with --mesh_obj <name>.obj plus <name>_image.png; --mesh_faces, --mesh_fov and --mesh_points
 are the viewer's mesh density, FOV and point mode.
+For one image or several, --tiles NY NX saves the depth at the PHOTO's resolution from an NY x NX grid of overlapping tiles (DPTModel.inference_tiled:
+every tile fitted to the whole-image prediction with one scale and one shift, then feather-blended; --tile_overlap is the share of a tile side that
+neighbours have in common): <name>_tiled.npy, fp32 [H, W], in the current directory.
 --crop X1 Y1 X2 Y2 is the reference's --crop with a stored box: normalised corners, applied to every image before it is predicted
 (crop_slices_from_norm: a side under 5 px falls back to the image's full extent); every output is then that of the cropped image.
 
@@ -64,6 +67,8 @@ def main():
     ap.add_argument("--mesh_fov", type=float, default=None, metavar="DEG", help="mesh: field of view in degrees (default: the viewer's 50)")
     ap.add_argument("--mesh_obj", action="store_true", help="mesh: write <name>.obj and <name>_image.png instead of <name>.glb")
     ap.add_argument("--mesh_points", action="store_true", help="mesh: a point cloud (one vertex per face) instead of triangles")
+    ap.add_argument("--tiles", type=int, nargs=2, default=None, metavar=("NY", "NX"), help="save every image's depth at its own resolution from an NY x NX tile grid")
+    ap.add_argument("--tile_overlap", type=float, default=0.25, metavar="F", help="tiles: the share of a tile side that neighbouring tiles have in common")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mdpt_run_image needs an MI355X: no GPU visible (there is no CPU fallback)")
@@ -108,6 +113,7 @@ def main():
     save_cutouts(args, args.image_path or ["synthetic.npy"], [img], [depth])
     save_block_norms(model, args, args.image_path or ["synthetic.npy"], [img])
     save_meshes(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
+    save_tiled(model, args, args.image_path or ["synthetic.npy"], [img])
 
 
 def crop_argument(args):
@@ -164,6 +170,18 @@ def save_meshes(args, is_metric, paths, images, depths):
             print("saved", stem + ".glb", f"({xyz.shape[0]} vertices, {faces.shape[0]} faces)")
 
 
+def save_tiled(model, args, paths, images):
+    """--tiles: DPTModel.inference_tiled per image (one batched inference_regions call and one stitch each), the fp32 map at the image's own size"""
+    if not args.tiles:
+        return
+    for path, img in zip(paths, images):
+        tiled = model.inference_tiled(img, tiles=tuple(args.tiles), overlap=args.tile_overlap, max_side_length=args.size,
+                                      use_square_sizing=not args.use_aspect_ratio, batch_size=args.batch_size)
+        out = os.path.splitext(os.path.basename(path))[0] + "_tiled.npy"
+        np.save(out, tiled[0].cpu().numpy())
+        print("saved", out, f"({tiled.shape[2]}x{tiled.shape[1]} from {args.tiles[0]}x{args.tiles[1]} tiles)")
+
+
 def save_block_norms(model, args, paths, images):
     """--block_norms: one DPTModel.block_norms call per group of images that share a model tensor size"""
     if not args.block_norms:
@@ -217,6 +235,7 @@ def run_images(model, args, t0, is_metric=False):
     save_cutouts(args, args.image_path, images, depths)
     save_block_norms(model, args, args.image_path, images)
     save_meshes(args, is_metric, args.image_path, images, depths)
+    save_tiled(model, args, args.image_path, images)
 
 
 if __name__ == "__main__":
