@@ -548,6 +548,64 @@ int mdpt_post_tile_fit(const mdpt_tile* tiles_host, const void* tiles_dev, int32
 int mdpt_post_tile_blend(const mdpt_tile* tiles_host, const void* tiles_dev, int32_t T, int32_t map_dtype, int32_t H, int32_t W, const void* fit_f64,
                          const void* sums_f64, double feather, void* out_f32, void* stream);
 
+/* True depth from ground truth on the device (additive to ABI v6): P predictions aligned to measured depth maps that are partly valid and at their
+ * own resolutions, scored with the standard depth metrics, and mapped to true depth. A relative-depth model returns inverse depth with an unknown
+ * scale and shift per image; the reference's .readme_assets/results_explainer.md gives depth = 1 / (A V + B) ("True depth from DPT result") and, under
+ * "Fitting to (more) known data", names a least-squares fit of A and B and the matching of the ground truth's median and spread, with code for
+ * neither. fp64 arithmetic, nothing contracted, results rounded once; nothing is read back, nothing synchronises; every call is bit-deterministic
+ * (fixed chunks of 2048 truth pixels reduced with a fixed tree and added in chunk order by the next launch; integer atomics for the select's counts
+ * only; no workgroup waits for or reads another), and a pair's results do not depend on the other pairs of the call.
+ * A pair is an mdpt_depth_pair record: pred (device pointer, ph x pw elements of pred_dtype), truth (fp32, H x W), valid (uint8, H x W, or NULL:
+ * every pixel). Pairs of one call may all differ in size; H W < 2^31. The kernels read the table from DEVICE memory (pairs_dev: the caller's upload
+ * of the P records, 8-byte aligned); pairs_host is the same table on the host, read during the call for the argument checks only. P <= 65535.
+ * THE SAMPLE RULE, shared by fit and metrics: one sample per TRUTH pixel (Y, X). v = the prediction sampled bilinearly (fp64 weights, rows first)
+ * at u = (X + 0.5) pw / W - 0.5, w = (Y + 0.5) ph / H - 0.5 clamped to the map (the tile fit's resampler with the roles swapped). t = 1 / truth
+ * in MDPT_ALIGN_INVERSE space, t = truth in MDPT_ALIGN_DEPTH space (metric heads). The sample counts if truth is finite and > 0, tmin <= truth <=
+ * tmax (-inf / +inf: no bound), valid is NULL or non-zero there, and v is finite.
+ *   mdpt_post_align_scratch_bytes .. the device scratch fit and metrics need for this table (partial sums, the select's bins and state)
+ *   mdpt_post_align_fit ............ fit_f64 [P, 2] = {A, B} with t ~ A v + B, sums_f64 [P, 6].
+ *                                    MDPT_ALIGN_LSTSQ: sums = {n, Sv, St, Svv, Svt, Stt}; var = n Svv - Sv^2, A = (n Svt - Sv St) / var,
+ *                                    B = (St - A Sv) / n, the tile fit's scheme and solve rule: a degenerate pair (n < 2, var <= 0, A not finite
+ *                                    or <= 0) gets A = 0, B = St / n; n == 0 gives B = 0. Two launches.
+ *                                    MDPT_ALIGN_MEDIAN (the explainer's "median and spread", MiDaS's training normalisation), on the float32
+ *                                    roundings v32, t32 of the samples: med(x) the exact median, for even n ((double)lo + (double)hi) 0.5;
+ *                                    mad(x) = (1 / n) sum |x - med(x)| in fp64; A = mad(t) / mad(v), B = med(t) - A med(v); mad(v) == 0 or an A
+ *                                    that is not finite or <= 0 gives A = 0, B = med(t); n == 0 gives B = 0 and sums of zero. sums = {n, med v,
+ *                                    med t, mad v, mad t, 0}. The median is an exact radix select on order-preserving 32-bit keys of the floats
+ *                                    (sign flip; -0.0 sorts before +0.0), 8 bits a pass: a per-pair digit histogram (LDS bins, integer atomics,
+ *                                    flushed with global integer atomics) and a one-workgroup-per-pair select that narrows the prefix of both
+ *                                    middle ranks, (n - 1) / 2 and n / 2; v and t go through the same launches; the samples are recomputed in
+ *                                    every pass, nothing per pixel is stored. Eleven launches: clear, 4 x (histogram, select), deviation, solve.
+ *   mdpt_post_align_metrics ........ metrics_f64 [P, MDPT_ALIGN_NUM_METRICS] over the same samples, two launches. q = A v + B (fit_f64 == NULL:
+ *                                    A = 1, B = 0, which scores a metric head as it is); aligned depth d = 1 / q in INVERSE space, d = q in
+ *                                    DEPTH space; a sample whose q is not > 0 is counted in n_bad and left out. With g = truth, over the
+ *                                    n - n_bad scored samples: {n, n_bad, AbsRel mean |d - g| / g, SqRel mean (d - g)^2 / g, RMSE, RMSE-log
+ *                                    sqrt(mean (ln d - ln g)^2), log10 mean |log10 d - log10 g|, delta1, delta2, delta3 the share of samples with
+ *                                    max(d / g, g / d) below 1.25, 1.25^2, 1.25^3, SILog 100 sqrt(mean(e^2) - mean(e)^2), e = ln d - ln g (a
+ *                                    difference below zero by rounding counts as zero)}. n - n_bad == 0 gives NaN for the nine metrics.
+ *   mdpt_post_align_apply .......... out_f32: pair p's H x W map (the record's H, W are the OUTPUT size here; truth and valid are not read and may
+ *                                    be NULL) at out_f32 + out_offsets[p] elements (the offsets on the host for the checks and, the same int64
+ *                                    values, uploaded to the device, 8-byte aligned). Per output pixel: v by the sample rule's resampler,
+ *                                    q = A v + B (fit_f64 == NULL: A = 1, B = 0), INVERSE: 1 / q, and +inf where q <= 0; DEPTH: q; then clamped to
+ *                                    [dmin, dmax] where those are finite (-inf / +inf: no clamp), rounded to fp32 once. A v that is not finite
+ *                                    propagates through the arithmetic (NaN stays NaN). One launch: resize, affine map and reciprocal fused.
+ * Every call checks on the host that sizes are positive, that H W < 2^31, that pointers are aligned (predictions to their element, truth and
+ * out_f32 to 4 bytes, the table, the fp64 buffers, the offsets and the scratch to 8), that tmin <= tmax and dmin <= dmax (no NaN), and launches
+ * nothing otherwise. */
+#define MDPT_ALIGN_INVERSE 0
+#define MDPT_ALIGN_DEPTH 1
+#define MDPT_ALIGN_LSTSQ 0
+#define MDPT_ALIGN_MEDIAN 1
+#define MDPT_ALIGN_NUM_METRICS 11
+typedef struct mdpt_depth_pair { const void* pred; int32_t ph, pw; const void* truth; const void* valid; int32_t H, W; } mdpt_depth_pair;
+int mdpt_post_align_scratch_bytes(const mdpt_depth_pair* pairs_host, int32_t P, size_t* bytes);
+int mdpt_post_align_fit(const mdpt_depth_pair* pairs_host, const void* pairs_dev, int32_t P, int32_t pred_dtype, int32_t space, int32_t method, double tmin,
+                        double tmax, void* fit_f64, void* sums_f64, void* scratch, size_t scratch_bytes, void* stream);
+int mdpt_post_align_metrics(const mdpt_depth_pair* pairs_host, const void* pairs_dev, int32_t P, int32_t pred_dtype, int32_t space, double tmin,
+                            double tmax, const void* fit_f64, void* metrics_f64, void* scratch, size_t scratch_bytes, void* stream);
+int mdpt_post_align_apply(const mdpt_depth_pair* pairs_host, const void* pairs_dev, int32_t P, int32_t pred_dtype, int32_t space, const void* fit_f64,
+                          const int64_t* out_offsets_host, const void* out_offsets_dev, double dmin, double dmax, void* out_f32, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

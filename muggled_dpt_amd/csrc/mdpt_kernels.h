@@ -238,6 +238,26 @@ struct PostTile { const void* map; int h, w, x1, y1, x2, y2; };
 #define MDPT_TILE_FIT_CHUNK 2048
 __host__ __device__ inline size_t tile_fit_chunks(size_t map_elems) { return (map_elems + MDPT_TILE_FIT_CHUNK - 1) / MDPT_TILE_FIT_CHUNK; }
 
+// one prediction / ground-truth pair of the true-depth block (postprocess.hip align_* kernels; = mdpt_depth_pair of include/mdpt.h): the ph x pw
+// prediction (the table's dtype), the H x W fp32 truth and its uint8 validity map (null: every pixel). Device table, indexed by pair; apply reads
+// pred, ph, pw and H x W (its output size) only.
+struct AlignPair { const void* pred; int ph, pw; const float* truth; const unsigned char* valid; int H, W; };
+#define ALIGN_METRIC_SUMS 11   // = MDPT_ALIGN_NUM_METRICS: the partial sums of a chunk and the metrics of a pair
+#define ALIGN_HIST_WORDS 1024  // the radix select's bins of a pair: [2 streams][2 rank tracks][256 digits]
+#define ALIGN_STATE_WORDS 16   // its state: 4 prefixes, 4 ranks, n
+#define ALIGN_STRIDE_BLOCKS 1024 // workgroups a pair's grid-stride passes (the select's histogram, apply) are spread over, at most
+// ... for a call whose largest map has max_pixels pixels: one per 2048 pixels, capped
+inline int align_stride_blocks(size_t max_pixels) {
+    const size_t b = (max_pixels + 2047) / 2048;
+    return (int)(b < 1 ? 1 : (b > ALIGN_STRIDE_BLOCKS ? ALIGN_STRIDE_BLOCKS : b));
+}
+// the scratch of a table of P pairs whose largest truth has max_chunks chunks of MDPT_TILE_FIT_CHUNK pixels: [P, max_chunks, ALIGN_METRIC_SUMS]
+// fp64 partials (the fits use the front of it), then the select's bins and state
+inline size_t align_parts_doubles(size_t P, size_t max_chunks) { return P * max_chunks * ALIGN_METRIC_SUMS; }
+inline size_t align_scratch_bytes(size_t P, size_t max_chunks) {
+    return align_parts_doubles(P, max_chunks) * sizeof(double) + P * (ALIGN_HIST_WORDS + ALIGN_STATE_WORDS) * sizeof(unsigned);
+}
+
 // the same for every block of the encoder in ONE launch (the LUTs depend on weights and window sizes only, not on activations)
 struct SwinCpbBatch {
     const float* w1[32]; const float* b1[32]; const float* w2[32]; float* lut[32];
@@ -297,6 +317,18 @@ int mdpt_launch_post_tile_fit(const PostTile* tiles, int T, int max_chunks, int 
                               double* sums, double* fit, hipStream_t stream);
 int mdpt_launch_post_tile_blend(const PostTile* tiles, int T, int dt, int H, int W, const double* fit, const double* sums, double feather, float* out,
                                 hipStream_t stream);
+
+// true depth from ground truth: pairs = P AlignPair records on the device (predictions of dtype dt); inverse: t = 1 / truth and d = 1 / (A v + B),
+// else t = truth and d = A v + B; a truth pixel counts inside [tmin, tmax]. Fit: sums [P, 6], fit [P, 2] fp64; least squares (median == 0) is two
+// launches over parts, the median fit eleven (hist [P, ALIGN_HIST_WORDS], state [P, ALIGN_STATE_WORDS]). Metrics: [P, ALIGN_METRIC_SUMS] fp64, fit ==
+// null: A = 1, B = 0. Apply: out fp32, pair p's H x W map at out + offs[p], clamped to [dmin, dmax] where finite; max_pixels = the largest H W (it
+// sizes the grid). max_chunks = the chunks of the largest H x W. All bit-deterministic.
+int mdpt_launch_post_align_fit(const AlignPair* pairs, int P, int max_chunks, int dt, int inverse, int median, double tmin, double tmax, double* parts,
+                               unsigned* hist, unsigned* state, double* sums, double* fit, hipStream_t stream);
+int mdpt_launch_post_align_metrics(const AlignPair* pairs, int P, int max_chunks, int dt, int inverse, double tmin, double tmax, const double* fit,
+                                   double* parts, double* metrics, hipStream_t stream);
+int mdpt_launch_post_align_apply(const AlignPair* pairs, int P, size_t max_pixels, int dt, int inverse, const double* fit, const long long* offs, double dmin,
+                                 double dmax, float* out, hipStream_t stream);
 
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);

@@ -455,4 +455,96 @@ int mdpt_post_tile_blend(const mdpt_tile* tiles_host, const void* tiles_dev, int
     return 0;
 }
 
+// ---- true depth from ground truth (results_explainer.md "True depth from DPT result" / "Fitting to (more) known data")
+static_assert(sizeof(mdpt_depth_pair) == sizeof(AlignPair) && sizeof(mdpt_depth_pair) == 40, "mdpt_depth_pair of include/mdpt.h is AlignPair of mdpt_kernels.h");
+static_assert(MDPT_ALIGN_NUM_METRICS == ALIGN_METRIC_SUMS, "the metrics of a pair are its partial sums solved in place");
+
+// the host table: sizes positive, H W < 2^31, predictions aligned to their element, truth (need_truth) non-null and 4-byte aligned;
+// *max_chunks = the chunks of the largest truth
+static int check_pairs(const mdpt_depth_pair* pairs, int32_t P, int32_t pred_dtype, bool need_truth, size_t* max_chunks) {
+    if (!pairs) return fail(MDPT_E_INVALID, "null argument");
+    if (P <= 0 || P > 65535) return fail(MDPT_E_INVALID, "bad pair count %d (1 .. 65535 per call)", P);
+    size_t most = 0;
+    for (int p = 0; p < P; ++p) {
+        const mdpt_depth_pair& q = pairs[p];
+        if (!q.pred || ((uintptr_t)q.pred & (dtype_bytes(pred_dtype) - 1)) != 0) return fail(MDPT_E_INVALID, "null or misaligned prediction (pair %d)", p);
+        if (q.ph <= 0 || q.pw <= 0 || q.H <= 0 || q.W <= 0) return fail(MDPT_E_INVALID, "bad size: prediction %dx%d, truth %dx%d (pair %d)", q.ph, q.pw, q.H, q.W, p);
+        if ((size_t)q.H * q.W >= ((size_t)1 << 31)) return fail(MDPT_E_INVALID, "a truth of %dx%d is too large (H W < 2^31, pair %d)", q.H, q.W, p);
+        if (need_truth && (!q.truth || ((uintptr_t)q.truth & 3) != 0)) return fail(MDPT_E_INVALID, "null or misaligned truth (pair %d)", p);
+        const size_t c = tile_fit_chunks((size_t)q.H * q.W);
+        most = c > most ? c : most;
+    }
+    *max_chunks = most;
+    return 0;
+}
+
+static int check_align_common(int32_t pred_dtype, int32_t space, double tmin, double tmax) {
+    if (!tensor_dtype_ok(pred_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", pred_dtype);
+    if (space != MDPT_ALIGN_INVERSE && space != MDPT_ALIGN_DEPTH) return fail(MDPT_E_INVALID, "unknown alignment space %d", space);
+    if (!(tmin <= tmax)) return fail(MDPT_E_INVALID, "the truth range [%g, %g] is empty or NaN", tmin, tmax);
+    return 0;
+}
+
+int mdpt_post_align_scratch_bytes(const mdpt_depth_pair* pairs_host, int32_t P, size_t* bytes) {
+    if (!bytes) return fail(MDPT_E_INVALID, "null argument");
+    size_t max_chunks;
+    CHK(check_pairs(pairs_host, P, MDPT_DTYPE_BF16, false, &max_chunks));
+    *bytes = align_scratch_bytes((size_t)P, max_chunks);
+    return 0;
+}
+
+int mdpt_post_align_fit(const mdpt_depth_pair* pairs_host, const void* pairs_dev, int32_t P, int32_t pred_dtype, int32_t space, int32_t method, double tmin,
+                        double tmax, void* fit_f64, void* sums_f64, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!pairs_dev || !fit_f64 || !sums_f64 || !scratch) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_align_common(pred_dtype, space, tmin, tmax));
+    if (method != MDPT_ALIGN_LSTSQ && method != MDPT_ALIGN_MEDIAN) return fail(MDPT_E_INVALID, "unknown alignment method %d", method);
+    size_t max_chunks;
+    CHK(check_pairs(pairs_host, P, pred_dtype, true, &max_chunks));
+    if ((((uintptr_t)pairs_dev | (uintptr_t)fit_f64 | (uintptr_t)sums_f64 | (uintptr_t)scratch) & 7) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table, the fp64 buffers and the scratch need 8 bytes)");
+    const size_t need = align_scratch_bytes((size_t)P, max_chunks);
+    if (scratch_bytes < need) return fail(MDPT_E_INVALID, "alignment scratch of %zu bytes, %zu needed (mdpt_post_align_scratch_bytes)", scratch_bytes, need);
+    unsigned* hist = (unsigned*)((double*)scratch + align_parts_doubles((size_t)P, max_chunks));
+    CHK(mdpt_launch_post_align_fit((const AlignPair*)pairs_dev, P, (int)max_chunks, pred_dtype, space == MDPT_ALIGN_INVERSE, method == MDPT_ALIGN_MEDIAN, tmin,
+                                   tmax, (double*)scratch, hist, hist + (size_t)P * ALIGN_HIST_WORDS, (double*)sums_f64, (double*)fit_f64,
+                                   (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_align_metrics(const mdpt_depth_pair* pairs_host, const void* pairs_dev, int32_t P, int32_t pred_dtype, int32_t space, double tmin,
+                            double tmax, const void* fit_f64, void* metrics_f64, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!pairs_dev || !metrics_f64 || !scratch) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_align_common(pred_dtype, space, tmin, tmax));
+    size_t max_chunks;
+    CHK(check_pairs(pairs_host, P, pred_dtype, true, &max_chunks));
+    if ((((uintptr_t)pairs_dev | (uintptr_t)fit_f64 | (uintptr_t)metrics_f64 | (uintptr_t)scratch) & 7) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table, the fp64 buffers and the scratch need 8 bytes)");
+    const size_t need = align_scratch_bytes((size_t)P, max_chunks);
+    if (scratch_bytes < need) return fail(MDPT_E_INVALID, "alignment scratch of %zu bytes, %zu needed (mdpt_post_align_scratch_bytes)", scratch_bytes, need);
+    CHK(mdpt_launch_post_align_metrics((const AlignPair*)pairs_dev, P, (int)max_chunks, pred_dtype, space == MDPT_ALIGN_INVERSE, tmin, tmax,
+                                       (const double*)fit_f64, (double*)scratch, (double*)metrics_f64, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_align_apply(const mdpt_depth_pair* pairs_host, const void* pairs_dev, int32_t P, int32_t pred_dtype, int32_t space, const void* fit_f64,
+                          const int64_t* out_offsets_host, const void* out_offsets_dev, double dmin, double dmax, void* out_f32, void* stream) {
+    if (!pairs_dev || !out_offsets_host || !out_offsets_dev || !out_f32) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_align_common(pred_dtype, space, 0.0, 0.0));
+    if (dmin != dmin || dmax != dmax || dmin > dmax) return fail(MDPT_E_INVALID, "the clamp [%g, %g] is empty or NaN", dmin, dmax);
+    size_t max_chunks;
+    CHK(check_pairs(pairs_host, P, pred_dtype, false, &max_chunks));
+    for (int p = 0; p < P; ++p)
+        if (out_offsets_host[p] < 0) return fail(MDPT_E_INVALID, "negative output offset (pair %d)", p);
+    if ((((uintptr_t)pairs_dev | (uintptr_t)fit_f64 | (uintptr_t)out_offsets_dev) & 7) != 0 || ((uintptr_t)out_f32 & 3) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table, the fit and the offsets need 8 bytes, the output 4)");
+    size_t max_pixels = 0;
+    for (int p = 0; p < P; ++p) {
+        const size_t px = (size_t)pairs_host[p].H * pairs_host[p].W;
+        max_pixels = px > max_pixels ? px : max_pixels;
+    }
+    CHK(mdpt_launch_post_align_apply((const AlignPair*)pairs_dev, P, max_pixels, pred_dtype, space == MDPT_ALIGN_INVERSE, (const double*)fit_f64,
+                                     (const long long*)out_offsets_dev, dmin, dmax, (float*)out_f32, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

@@ -1165,9 +1165,10 @@ void mesh_launch_vertex_f32(const MeshJob&, unsigned, float*, float*, hipStream_
 // tile t's samples - MDPT_TILE_FIT_CHUNK of them, each thread its 8 in order, then block_sum_f64's fixed tree - into parts[t][c]; (2) in the next
 // launch one workgroup per tile adds the tile's partials in chunk order and solves. A launch boundary separates the producers from the consumer.
 
-// the guide (gh x gw of dtype gdt, covering the H x W photo) at photo position (X, Y): bilinear at u = X gw / W - 0.5, v = Y gh / H - 0.5, clamped to
-// the guide; fp64 weights, rows first
-__device__ __forceinline__ double guide_at(const void* g, int gdt, int gh, int gw, double X, double Y, int H, int W) {
+// a map (gh x gw of dtype gdt) covering an H x W frame, at frame position (X, Y): bilinear at u = X gw / W - 0.5, v = Y gh / H - 0.5, clamped to the
+// map; fp64 weights, rows first. The one resampler of the fits: the tile fit reads its guide through it (guide_at), the true-depth block its
+// prediction at the centre of a ground-truth pixel (align_sample / align_apply_kernel)
+__device__ __forceinline__ double bilinear_f64_at(const void* g, int gdt, int gh, int gw, double X, double Y, int H, int W) {
 #pragma clang fp contract(off)
     double u = X * (double)gw / (double)W - 0.5, v = Y * (double)gh / (double)H - 0.5;
     u = fmin(fmax(u, 0.0), (double)(gw - 1));
@@ -1179,6 +1180,11 @@ __device__ __forceinline__ double guide_at(const void* g, int gdt, int gh, int g
     const double g10 = ld_dt(g, (size_t)y1 * gw + x0, gdt), g11 = ld_dt(g, (size_t)y1 * gw + x1, gdt);
     const double top = g00 * (1.0 - ax) + g01 * ax, bot = g10 * (1.0 - ax) + g11 * ax;
     return top * (1.0 - ay) + bot * ay;
+}
+
+// the guide (gh x gw of dtype gdt, covering the H x W photo) at photo position (X, Y)
+__device__ __forceinline__ double guide_at(const void* g, int gdt, int gh, int gw, double X, double Y, int H, int W) {
+    return bilinear_f64_at(g, gdt, gh, gw, X, Y, H, W);
 }
 
 // (1) blockIdx.y = tile, blockIdx.x = chunk. Sample (j, i) of the map: x = m[j, i], y = the guide at the pixel's centre in the photo,
@@ -1210,6 +1216,23 @@ __global__ __launch_bounds__(256) void tile_fit_partial_kernel(const PostTile* _
     }
 }
 
+// the least-squares line y = s x + t of the sums {n, Sx, Sy, Sxx, Sxy}: var = n Sxx - Sx^2, s = (n Sxy - Sx Sy) / var, t = (Sy - s Sx) / n; a
+// degenerate set (n < 2, var <= 0, s not finite or <= 0) gets s = 0, t = Sy / n; n == 0: t = 0. (The tile fit's and the true-depth fit's one rule)
+__device__ __forceinline__ void affine_solve(double n, double sx, double sy, double sxx, double sxy, double& scale, double& shift) {
+#pragma clang fp contract(off)
+    scale = 0.0, shift = 0.0;
+    if (n > 0.0) {
+        const double var = n * sxx - sx * sx;
+        const double cand = (n * sxy - sx * sy) / var;
+        if (n >= 2.0 && var > 0.0 && isfinite(cand) && cand > 0.0) {
+            scale = cand;
+            shift = (sy - scale * sx) / n;
+        } else {
+            shift = sy / n;
+        }
+    }
+}
+
 // (2) one workgroup per tile: lane k adds partial sum k of the tile's chunks in chunk order -> sums[t]; then var = n Sxx - Sx^2,
 // s = (n Sxy - Sx Sy) / var, t = (Sy - s Sx) / n -> fit[t] = {s, t}. A degenerate tile (n < 2, var <= 0, s not finite or <= 0) gets s = 0 and the
 // guide's mean t = Sy / n; n == 0: t = 0, and the blend skips the tile (sums[t][0] == 0 marks it empty)
@@ -1228,18 +1251,8 @@ __global__ __launch_bounds__(64) void tile_fit_solve_kernel(const PostTile* __re
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
-    const double n = s[0], sx = s[1], sy = s[2], sxx = s[3], sxy = s[4];
-    double scale = 0.0, shift = 0.0;
-    if (n > 0.0) {
-        const double var = n * sxx - sx * sx;
-        const double cand = (n * sxy - sx * sy) / var;
-        if (n >= 2.0 && var > 0.0 && isfinite(cand) && cand > 0.0) {
-            scale = cand;
-            shift = (sy - scale * sx) / n;
-        } else {
-            shift = sy / n;
-        }
-    }
+    double scale, shift;
+    affine_solve(s[0], s[1], s[2], s[3], s[4], scale, shift);
     fit[2 * (size_t)t] = scale;
     fit[2 * (size_t)t + 1] = shift;
 }
@@ -1340,6 +1353,332 @@ __global__ __launch_bounds__(256) void tile_blend_kernel(const PostTile* __restr
     }
 }
 
+// ---- true depth from ground truth: a prediction aligned to a measured depth map that is partly valid and at its own resolution, scored with the
+// standard metrics, and mapped to true depth. The reference's .readme_assets/results_explainer.md gives depth = 1 / (A V + B) ("True depth from DPT
+// result") and names two ways to A and B when measurements exist ("Fitting to (more) known data": least squares, or matching the median and the
+// spread), with code for neither. A pair is an AlignPair (mdpt_kernels.h); the table lives in device memory and pairs may all differ in size.
+// Everything follows the tile fit: fp64, nothing contracted, rounded once, fixed chunks reduced by a fixed tree and added in chunk order by the
+// next launch, integer atomics only (the radix select's counts, which do not depend on order), no workgroup waits for or reads another.
+
+struct AlignSample { double v, t, g; };
+
+// THE sample rule of every kernel below: truth pixel e = Y W + X of pair p. g = truth[e] counts if it is finite, > 0, inside [tmin, tmax] (+-inf:
+// no bound) and valid[e] != 0 (valid == null: all); v = the prediction at the pixel's centre (bilinear_f64_at) must be finite; t = 1 / g in
+// inverse space, g in depth space. (truth is tested first: a pixel without a measurement costs no prediction read)
+__device__ __forceinline__ bool align_sample(const AlignPair& p, int dt, int inverse, double tmin, double tmax, size_t e, AlignSample& s) {
+#pragma clang fp contract(off)
+    const double g = (double)p.truth[e];
+    if (!(isfinite(g) && g > 0.0 && g >= tmin && g <= tmax)) return false;
+    if (p.valid && p.valid[e] == 0) return false;
+    const int Y = (int)(e / (size_t)p.W), X = (int)(e - (size_t)Y * p.W);
+    const double v = bilinear_f64_at(p.pred, dt, p.ph, p.pw, (double)X + 0.5, (double)Y + 0.5, p.H, p.W);
+    if (!isfinite(v)) return false;
+    s.v = v;
+    s.g = g;
+    s.t = inverse ? 1.0 / g : g;
+    return true;
+}
+
+// lane k < K of the block adds partial sum k of `chunks` chunks in chunk order -> s[k] (shared); the block is synchronised on return
+template <int K>
+__device__ __forceinline__ void chunk_order_sum(const double* __restrict__ parts, size_t chunks, double* s) {
+    if (threadIdx.x < K) {
+        double acc = 0.0;
+        for (size_t c = 0; c < chunks; ++c) acc += parts[c * K + threadIdx.x];
+        s[threadIdx.x] = acc;
+    }
+    __syncthreads();
+}
+
+// least squares (1): blockIdx.y = pair, blockIdx.x = chunk of MDPT_TILE_FIT_CHUNK truth pixels -> {n, Sv, St, Svv, Svt, Stt} of the chunk
+__global__ __launch_bounds__(256) void align_fit_partial_kernel(const AlignPair* __restrict__ pairs, int dt, int inverse, double tmin, double tmax,
+                                                                double* __restrict__ parts, int max_chunks) {
+#pragma clang fp contract(off)
+    const AlignPair p = pairs[blockIdx.y];
+    const size_t n = (size_t)p.H * p.W, base = (size_t)blockIdx.x * MDPT_TILE_FIT_CHUNK;
+    if (base >= n) return;  // (uniform over the block)
+    double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < MDPT_TILE_FIT_CHUNK / 256; ++k) {
+        const size_t e = base + (size_t)k * 256 + threadIdx.x;
+        if (e >= n) break;
+        AlignSample s;
+        if (align_sample(p, dt, inverse, tmin, tmax, e, s)) {
+            a[0] += 1.0; a[1] += s.v; a[2] += s.t;
+            a[3] += s.v * s.v; a[4] += s.v * s.t; a[5] += s.t * s.t;
+        }
+    }
+    block_sum_f64<6>(a);
+    if (threadIdx.x == 0) {
+        double* o = parts + ((size_t)blockIdx.y * max_chunks + blockIdx.x) * 6;
+        for (int k = 0; k < 6; ++k) o[k] = a[k];
+    }
+}
+
+// least squares (2): one workgroup per pair: the partials in chunk order -> sums[p], affine_solve -> fit[p] = {A, B}
+__global__ __launch_bounds__(64) void align_fit_solve_kernel(const AlignPair* __restrict__ pairs, const double* __restrict__ parts, int max_chunks,
+                                                             double* __restrict__ sums, double* __restrict__ fit) {
+    const int p = blockIdx.x;
+    __shared__ double s[6];
+    chunk_order_sum<6>(parts + (size_t)p * max_chunks * 6, tile_fit_chunks((size_t)pairs[p].H * pairs[p].W), s);
+    if (threadIdx.x < 6) sums[(size_t)p * 6 + threadIdx.x] = s[threadIdx.x];
+    if (threadIdx.x != 0) return;
+    double scale, shift;
+    affine_solve(s[0], s[1], s[2], s[3], s[4], scale, shift);
+    fit[2 * (size_t)p] = scale;
+    fit[2 * (size_t)p + 1] = shift;
+}
+
+// ---- the median fit: exact medians of the float32 roundings v32, t32 of the samples by a radix select over order-preserving 32-bit keys, 8 bits
+// a pass from the top. A pass is a histogram launch (every workgroup counts the digits of its samples in LDS and flushes the non-zero bins with
+// integer atomics) and a select launch (one workgroup per pair narrows the key prefix of BOTH middle ranks, (n - 1) / 2 and n / 2, of both streams,
+// and clears the pair's bins for the next pass). Bins: hist[p][2 s + r][256], s = 0 v / 1 t, r = the rank's track; while the two tracks of a stream
+// share their prefix only track 0 is counted. State: state[p][0..3] the prefixes, [4..7] the ranks left inside the prefix, [8] n. The samples are
+// recomputed in every pass: nothing per pixel is stored.
+
+// float -> key whose unsigned order is the float order (-0.0 before +0.0), and back
+__device__ __forceinline__ unsigned f32_key(float x) {
+    const unsigned b = __float_as_uint(x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_f32(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+__global__ __launch_bounds__(256) void align_select_clear_kernel(unsigned* __restrict__ hist, unsigned* __restrict__ state) {
+    unsigned* h = hist + (size_t)blockIdx.x * ALIGN_HIST_WORDS;
+    for (int i = threadIdx.x; i < ALIGN_HIST_WORDS; i += 256) h[i] = 0;
+    if (threadIdx.x < ALIGN_STATE_WORDS) state[(size_t)blockIdx.x * ALIGN_STATE_WORDS + threadIdx.x] = 0;
+}
+
+// blockIdx.y = pair, blockIdx.x strides over the pair's truth pixels. A thread keeps the bin of its last sample per stream and adds its run length
+// once the bin changes: the top digits of a depth map are nearly constant, and one LDS atomic per sample would serialise the wave on one address.
+__global__ __launch_bounds__(256) void align_hist_kernel(const AlignPair* __restrict__ pairs, int dt, int inverse, double tmin, double tmax,
+                                                         const unsigned* __restrict__ state, unsigned* __restrict__ hist, int shift) {
+    __shared__ unsigned bins[ALIGN_HIST_WORDS];
+    const AlignPair p = pairs[blockIdx.y];
+    const size_t n = (size_t)p.H * p.W;
+    if ((size_t)blockIdx.x * 256 >= n) return;  // (uniform over the block)
+    for (int i = threadIdx.x; i < ALIGN_HIST_WORDS; i += 256) bins[i] = 0;
+    const unsigned* st = state + (size_t)blockIdx.y * ALIGN_STATE_WORDS;
+    const unsigned pre[4] = {st[0], st[1], st[2], st[3]};
+    const unsigned mask = shift == 24 ? 0u : 0xffffffffu << (shift + 8);
+    __syncthreads();
+    int cur[2] = {-1, -1};
+    unsigned run[2] = {0, 0};
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+        AlignSample s;
+        if (!align_sample(p, dt, inverse, tmin, tmax, e, s)) continue;
+        const unsigned key[2] = {f32_key((float)s.v), f32_key((float)s.t)};
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const unsigned top = key[q] & mask;
+            const int track = top == pre[2 * q] ? 0 : (top == pre[2 * q + 1] ? 1 : -1);
+            if (track < 0) continue;
+            const int bin = (2 * q + track) * 256 + (int)((key[q] >> shift) & 255u);
+            if (bin != cur[q]) {
+                if (run[q]) atomicAdd(&bins[cur[q]], run[q]);
+                cur[q] = bin;
+                run[q] = 0;
+            }
+            ++run[q];
+        }
+    }
+    for (int q = 0; q < 2; ++q)
+        if (run[q]) atomicAdd(&bins[cur[q]], run[q]);
+    __syncthreads();
+    unsigned* h = hist + (size_t)blockIdx.y * ALIGN_HIST_WORDS;
+    for (int i = threadIdx.x; i < ALIGN_HIST_WORDS; i += 256)
+        if (bins[i]) atomicAdd(&h[i], bins[i]);
+}
+
+// one workgroup per pair; thread 2 s + r < 4 walks the 256 bins of its stream and track to the digit that holds its rank. After the last pass
+// (shift == 0) the prefixes are the keys of the two middle order statistics: med = ((double)lo + (double)hi) 0.5 -> sums[p] = {n, med v, med t}
+// (n == 0: zeros)
+__global__ __launch_bounds__(256) void align_select_kernel(unsigned* __restrict__ hist, unsigned* __restrict__ state, int shift, double* __restrict__ sums) {
+#pragma clang fp contract(off)
+    __shared__ unsigned bins[ALIGN_HIST_WORDS];
+    __shared__ unsigned key[4];
+    unsigned* h = hist + (size_t)blockIdx.x * ALIGN_HIST_WORDS;
+    unsigned* st = state + (size_t)blockIdx.x * ALIGN_STATE_WORDS;
+    for (int i = threadIdx.x; i < ALIGN_HIST_WORDS; i += 256) {
+        bins[i] = h[i];
+        h[i] = 0;
+    }
+    const int tr = threadIdx.x & 3, s2 = tr & 2;
+    const unsigned pre = st[tr], pre0 = st[s2], pre1 = st[s2 + 1], rank_in = st[4 + tr];
+    unsigned n = st[8];
+    __syncthreads();  // (the state is read by every thread before any thread writes it)
+    if (threadIdx.x < 4) {
+        const unsigned* b = bins + (pre0 == pre1 ? s2 : tr) * 256;
+        unsigned rank = rank_in;
+        if (shift == 24) {
+            n = 0;
+            for (int d = 0; d < 256; ++d) n += bins[d];  // (every sample has a v key: track 0 of stream v holds them all)
+            rank = n == 0 ? 0u : ((tr & 1) ? n / 2 : (n - 1) / 2);
+        }
+        unsigned below = 0;
+        int d = 0;
+        for (; d < 255; ++d) {
+            if (rank < below + b[d]) break;
+            below += b[d];
+        }
+        key[tr] = pre | ((unsigned)d << shift);
+        st[tr] = key[tr];
+        st[4 + tr] = rank - below;
+        if (tr == 0) st[8] = n;
+    }
+    __syncthreads();
+    if (shift == 0 && threadIdx.x < 3) {
+        double out = (double)n;
+        if (threadIdx.x > 0) {
+            const int q = 2 * ((int)threadIdx.x - 1);
+            out = n == 0 ? 0.0 : ((double)key_f32(key[q]) + (double)key_f32(key[q + 1])) * 0.5;
+        }
+        sums[(size_t)blockIdx.x * 6 + threadIdx.x] = out;
+    }
+}
+
+// mean absolute deviation (1): as align_fit_partial_kernel, {sum |v32 - med v|, sum |t32 - med t|} of the chunk
+__global__ __launch_bounds__(256) void align_mad_partial_kernel(const AlignPair* __restrict__ pairs, int dt, int inverse, double tmin, double tmax,
+                                                                const double* __restrict__ sums, double* __restrict__ parts, int max_chunks) {
+#pragma clang fp contract(off)
+    const AlignPair p = pairs[blockIdx.y];
+    const size_t n = (size_t)p.H * p.W, base = (size_t)blockIdx.x * MDPT_TILE_FIT_CHUNK;
+    if (base >= n) return;
+    const double mv = sums[(size_t)blockIdx.y * 6 + 1], mt = sums[(size_t)blockIdx.y * 6 + 2];
+    double a[2] = {0.0, 0.0};
+    for (int k = 0; k < MDPT_TILE_FIT_CHUNK / 256; ++k) {
+        const size_t e = base + (size_t)k * 256 + threadIdx.x;
+        if (e >= n) break;
+        AlignSample s;
+        if (align_sample(p, dt, inverse, tmin, tmax, e, s)) {
+            a[0] += fabs((double)(float)s.v - mv);
+            a[1] += fabs((double)(float)s.t - mt);
+        }
+    }
+    block_sum_f64<2>(a);
+    if (threadIdx.x == 0) {
+        double* o = parts + ((size_t)blockIdx.y * max_chunks + blockIdx.x) * 2;
+        o[0] = a[0];
+        o[1] = a[1];
+    }
+}
+
+// mean absolute deviation (2): mad = S / n -> sums[p][3..5] = {mad v, mad t, 0}; A = mad t / mad v, B = med t - A med v. mad v == 0, or an A that is
+// not finite or <= 0: A = 0, B = med t (n == 0: 0), the least-squares fit's degenerate rule with the median in the mean's place
+__global__ __launch_bounds__(64) void align_mad_solve_kernel(const AlignPair* __restrict__ pairs, const double* __restrict__ parts, int max_chunks,
+                                                             double* __restrict__ sums, double* __restrict__ fit) {
+#pragma clang fp contract(off)
+    const int p = blockIdx.x;
+    __shared__ double s[2];
+    chunk_order_sum<2>(parts + (size_t)p * max_chunks * 2, tile_fit_chunks((size_t)pairs[p].H * pairs[p].W), s);
+    if (threadIdx.x != 0) return;
+    double* o = sums + (size_t)p * 6;
+    const double n = o[0], mv = o[1], mt = o[2];
+    const double mad_v = n > 0.0 ? s[0] / n : 0.0, mad_t = n > 0.0 ? s[1] / n : 0.0;
+    o[3] = mad_v;
+    o[4] = mad_t;
+    o[5] = 0.0;
+    double a = 0.0, b = n > 0.0 ? mt : 0.0;
+    const double cand = mad_t / mad_v;
+    if (n > 0.0 && mad_v > 0.0 && isfinite(cand) && cand > 0.0) {
+        a = cand;
+        b = mt - a * mv;
+    }
+    fit[2 * (size_t)p] = a;
+    fit[2 * (size_t)p + 1] = b;
+}
+
+// metrics (1): as align_fit_partial_kernel. q = A v + B (fit == null: A = 1, B = 0); a sample whose q is not > 0 is counted as bad and left out;
+// d = 1 / q in inverse space, q in depth space -> {n, bad, sum |d - g| / g, sum (d - g)^2 / g, sum (d - g)^2, sum e^2, sum |log10 d - log10 g|,
+// count r < 1.25, < 1.25^2, < 1.25^3, sum e}, e = ln d - ln g, r = max(d / g, g / d)
+__global__ __launch_bounds__(256) void align_metrics_partial_kernel(const AlignPair* __restrict__ pairs, int dt, int inverse, double tmin, double tmax,
+                                                                    const double* __restrict__ fit, double* __restrict__ parts, int max_chunks) {
+#pragma clang fp contract(off)
+    const AlignPair p = pairs[blockIdx.y];
+    const size_t n = (size_t)p.H * p.W, base = (size_t)blockIdx.x * MDPT_TILE_FIT_CHUNK;
+    if (base >= n) return;
+    const double A = fit ? fit[2 * (size_t)blockIdx.y] : 1.0, B = fit ? fit[2 * (size_t)blockIdx.y + 1] : 0.0;
+    double a[ALIGN_METRIC_SUMS];
+#pragma unroll
+    for (int k = 0; k < ALIGN_METRIC_SUMS; ++k) a[k] = 0.0;
+    for (int k = 0; k < MDPT_TILE_FIT_CHUNK / 256; ++k) {
+        const size_t e = base + (size_t)k * 256 + threadIdx.x;
+        if (e >= n) break;
+        AlignSample s;
+        if (!align_sample(p, dt, inverse, tmin, tmax, e, s)) continue;
+        a[0] += 1.0;
+        const double q = A * s.v + B;
+        if (!(q > 0.0)) {
+            a[1] += 1.0;
+            continue;
+        }
+        const double d = inverse ? 1.0 / q : q, g = s.g, diff = d - g;
+        const double le = log(d) - log(g), r = fmax(d / g, g / d);
+        a[2] += fabs(diff) / g;
+        a[3] += diff * diff / g;
+        a[4] += diff * diff;
+        a[5] += le * le;
+        a[6] += fabs(log10(d) - log10(g));
+        a[7] += r < 1.25 ? 1.0 : 0.0;
+        a[8] += r < 1.5625 ? 1.0 : 0.0;
+        a[9] += r < 1.953125 ? 1.0 : 0.0;
+        a[10] += le;
+    }
+    block_sum_f64<ALIGN_METRIC_SUMS>(a);
+    if (threadIdx.x == 0) {
+        double* o = parts + ((size_t)blockIdx.y * max_chunks + blockIdx.x) * ALIGN_METRIC_SUMS;
+        for (int k = 0; k < ALIGN_METRIC_SUMS; ++k) o[k] = a[k];
+    }
+}
+
+// metrics (2): the partials in chunk order, then over the m = n - bad scored samples: {n, bad, AbsRel, SqRel, RMSE, RMSE-log, log10, delta1, delta2,
+// delta3, SILog = 100 sqrt(max(mean e^2 - (mean e)^2, 0))}; m == 0: NaN
+__global__ __launch_bounds__(64) void align_metrics_solve_kernel(const AlignPair* __restrict__ pairs, const double* __restrict__ parts, int max_chunks,
+                                                                 double* __restrict__ metrics) {
+#pragma clang fp contract(off)
+    const int p = blockIdx.x;
+    __shared__ double s[ALIGN_METRIC_SUMS];
+    chunk_order_sum<ALIGN_METRIC_SUMS>(parts + (size_t)p * max_chunks * ALIGN_METRIC_SUMS, tile_fit_chunks((size_t)pairs[p].H * pairs[p].W), s);
+    if (threadIdx.x != 0) return;
+    double* o = metrics + (size_t)p * ALIGN_METRIC_SUMS;
+    const double m = s[0] - s[1];
+    o[0] = s[0];
+    o[1] = s[1];
+    if (!(m > 0.0)) {
+        for (int k = 2; k < ALIGN_METRIC_SUMS; ++k) o[k] = NAN;
+        return;
+    }
+    const double me = s[10] / m;
+    o[2] = s[2] / m;
+    o[3] = s[3] / m;
+    o[4] = sqrt(s[4] / m);
+    o[5] = sqrt(s[5] / m);
+    o[6] = s[6] / m;
+    o[7] = s[7] / m;
+    o[8] = s[8] / m;
+    o[9] = s[9] / m;
+    o[10] = 100.0 * sqrt(fmax(s[5] / m - me * me, 0.0));
+}
+
+// true depth: out pixel (Y, X) of pair p's H x W output (at out + offs[p]) = the prediction at the pixel's centre, q = A v + B, d = 1 / q in inverse
+// space (q <= 0: +inf), q in depth space; then clamped to [dmin, dmax] where those are finite, rounded to fp32 once. NaN stays NaN.
+__global__ __launch_bounds__(256) void align_apply_kernel(const AlignPair* __restrict__ pairs, int dt, int inverse, const double* __restrict__ fit,
+                                                          const long long* __restrict__ offs, double dmin, double dmax, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const AlignPair p = pairs[blockIdx.y];
+    const size_t n = (size_t)p.H * p.W;
+    const double A = fit ? fit[2 * (size_t)blockIdx.y] : 1.0, B = fit ? fit[2 * (size_t)blockIdx.y + 1] : 0.0;
+    float* o = out + offs[blockIdx.y];
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+        const int Y = (int)(e / (size_t)p.W), X = (int)(e - (size_t)Y * p.W);
+        const double v = bilinear_f64_at(p.pred, dt, p.ph, p.pw, (double)X + 0.5, (double)Y + 0.5, p.H, p.W);
+        const double q = A * v + B;
+        double d = inverse ? (q <= 0.0 ? (double)INFINITY : 1.0 / q) : q;
+        if (isfinite(dmin) && d < dmin) d = dmin;
+        if (isfinite(dmax) && d > dmax) d = dmax;
+        o[e] = (float)d;
+    }
+}
+
 }  // namespace
 
 int mdpt_launch_post_tile_fit(const PostTile* tiles, int T, int max_chunks, int dt, const void* guide, int gdt, int gh, int gw, int H, int W, double* parts,
@@ -1362,6 +1701,65 @@ int mdpt_launch_post_tile_blend(const PostTile* tiles, int T, int dt, int H, int
     MdptProfScope prof("tile_blend_kernel", 0.0, stream);
     hipLaunchKernelGGL(tile_blend_kernel, dim3((unsigned)(blocks_x * blocks_y)), dim3(256), 0, stream, tiles, T, dt, H, W, fit, sums, feather + 1.0, out,
                        (int)blocks_x);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_align_fit(const AlignPair* pairs, int P, int max_chunks, int dt, int inverse, int median, double tmin, double tmax, double* parts,
+                               unsigned* hist, unsigned* state, double* sums, double* fit, hipStream_t stream) {
+    if (P <= 0 || P > 65535 || max_chunks <= 0 || max_chunks >= (1 << 24)) return (int)hipErrorInvalidValue;
+    if (!median) {
+        {
+            MdptProfScope prof("align_fit_partial_kernel", 0.0, stream);
+            hipLaunchKernelGGL(align_fit_partial_kernel, dim3(max_chunks, P), dim3(256), 0, stream, pairs, dt, inverse, tmin, tmax, parts, max_chunks);
+        }
+        MdptProfScope prof("align_fit_solve_kernel", 0.0, stream);
+        hipLaunchKernelGGL(align_fit_solve_kernel, dim3(P), dim3(64), 0, stream, pairs, (const double*)parts, max_chunks, sums, fit);
+        return (int)hipGetLastError();
+    }
+    // 1 clear + 4 x (histogram, select) + the deviation's partial and solve = 11 launches
+    {
+        MdptProfScope prof("align_select_clear_kernel", 0.0, stream);
+        hipLaunchKernelGGL(align_select_clear_kernel, dim3(P), dim3(256), 0, stream, hist, state);
+    }
+    const int hist_blocks = align_stride_blocks((size_t)max_chunks * MDPT_TILE_FIT_CHUNK);
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        {
+            MdptProfScope prof("align_hist_kernel", 0.0, stream);
+            hipLaunchKernelGGL(align_hist_kernel, dim3(hist_blocks, P), dim3(256), 0, stream, pairs, dt, inverse, tmin, tmax, (const unsigned*)state, hist,
+                               shift);
+        }
+        MdptProfScope prof("align_select_kernel", 0.0, stream);
+        hipLaunchKernelGGL(align_select_kernel, dim3(P), dim3(256), 0, stream, hist, state, shift, sums);
+    }
+    {
+        MdptProfScope prof("align_mad_partial_kernel", 0.0, stream);
+        hipLaunchKernelGGL(align_mad_partial_kernel, dim3(max_chunks, P), dim3(256), 0, stream, pairs, dt, inverse, tmin, tmax, (const double*)sums, parts,
+                           max_chunks);
+    }
+    MdptProfScope prof("align_mad_solve_kernel", 0.0, stream);
+    hipLaunchKernelGGL(align_mad_solve_kernel, dim3(P), dim3(64), 0, stream, pairs, (const double*)parts, max_chunks, sums, fit);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_align_metrics(const AlignPair* pairs, int P, int max_chunks, int dt, int inverse, double tmin, double tmax, const double* fit,
+                                   double* parts, double* metrics, hipStream_t stream) {
+    if (P <= 0 || P > 65535 || max_chunks <= 0 || max_chunks >= (1 << 24)) return (int)hipErrorInvalidValue;
+    {
+        MdptProfScope prof("align_metrics_partial_kernel", 0.0, stream);
+        hipLaunchKernelGGL(align_metrics_partial_kernel, dim3(max_chunks, P), dim3(256), 0, stream, pairs, dt, inverse, tmin, tmax, fit, parts, max_chunks);
+    }
+    MdptProfScope prof("align_metrics_solve_kernel", 0.0, stream);
+    hipLaunchKernelGGL(align_metrics_solve_kernel, dim3(P), dim3(64), 0, stream, pairs, (const double*)parts, max_chunks, metrics);
+    return (int)hipGetLastError();
+}
+
+int mdpt_launch_post_align_apply(const AlignPair* pairs, int P, size_t max_pixels, int dt, int inverse, const double* fit, const long long* offs, double dmin,
+                                 double dmax, float* out, hipStream_t stream) {
+    if (P <= 0 || P > 65535 || max_pixels == 0 || max_pixels >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
+    // (the blocks of a pair stride over its output pixels, 256 at a time: one block per 2048 pixels of the largest output, capped)
+    const int blocks = align_stride_blocks(max_pixels);
+    MdptProfScope prof("align_apply_kernel", 0.0, stream);
+    hipLaunchKernelGGL(align_apply_kernel, dim3(blocks, P), dim3(256), 0, stream, pairs, dt, inverse, fit, offs, dmin, dmax, out);
     return (int)hipGetLastError();
 }
 

@@ -1045,6 +1045,22 @@ class DPTModel(nn.Module):
             return out
         return out[0], {"regions": maps, "boxes": boxes, "fit": out[1], "sums": out[2]}
 
+    def evaluate_depth(self, images_bgr, truths, valid=None, method: str = "lstsq", truth_range=(None, None), max_side_length: int | None = None,
+                       use_square_sizing: bool = True, batch_size: int = 32):
+        """Images with measured depth maps (LiDAR, stereo, a benchmark's ground truth) -> (fit, metrics, true_depth_maps): one inference_images call,
+        then postprocess.fit_true_depth (fp64 [P,2] {A, B} per image), depth_metrics (fp64 [P,11], columns postprocess.DEPTH_METRIC_NAMES) and
+        true_depth (fp32 [1,H_i,W_i] at each truth's own size), all on the device with nothing read back (not in the reference, whose
+        .readme_assets/results_explainer.md describes the fit). truths / valid / method / truth_range are fit_true_depth's: one map per image at
+        its own resolution, where zero, NaN or an unset `valid` pixel means no measurement. A metric model (config is_metric) is fitted and scored in
+        depth space, every other model in inverse-depth space."""
+        from .postprocess import _align_pairs, depth_metrics, fit_true_depth, true_depth
+        space = "depth" if self.config.get("is_metric", False) else "inverse"
+        preds = self.inference_images(images_bgr, max_side_length, use_square_sizing, batch_size)
+        staged = _align_pairs(preds, truths, valid, "evaluate_depth")  # host truths are staged, and the pair table uploaded, once for both calls
+        fit = fit_true_depth(preds, truths, valid, space, method, truth_range, staged=staged)
+        metrics = depth_metrics(preds, truths, fit, valid, space, truth_range, staged=staged)
+        return fit, metrics, true_depth(preds, fit, staged[3], space)
+
     def prepare_image_bgr(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True,
                           interpolation_mode: str = "bilinear", *, crop=None) -> Tensor:
         return self.patch_embed.prepare_image(image_bgr, max_side_length, use_square_sizing, interpolation_mode, crop=crop)

@@ -50,6 +50,9 @@ POST_SEG_PARTS = 64  # MDPT_POST_SEG_PARTS
 BGR_RUNS, POST_RUNS = 64, 32  # MDPT_BGR_RUNS / MDPT_POST_RUNS (csrc/mdpt_kernels.h): images per launch of a per-image table
 INTERP_BILINEAR, INTERP_BICUBIC = 0, 1
 MESH_TRIANGLES, MESH_POINTS = 0, 1  # MDPT_MESH_*
+ALIGN_INVERSE, ALIGN_DEPTH = 0, 1  # MDPT_ALIGN_* spaces
+ALIGN_LSTSQ, ALIGN_MEDIAN = 0, 1  # MDPT_ALIGN_* methods
+ALIGN_NUM_METRICS = 11  # MDPT_ALIGN_NUM_METRICS
 
 
 def _hipcc() -> str:
@@ -231,6 +234,10 @@ SYMBOLS = {
     "mdpt_post_tile_scratch_bytes": (ctypes.c_int, [_VP, _I, ctypes.POINTER(_SZ)]),
     "mdpt_post_tile_fit": (ctypes.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
     "mdpt_post_tile_blend": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _VP]),
+    "mdpt_post_align_scratch_bytes": (ctypes.c_int, [_VP, _I, ctypes.POINTER(_SZ)]),
+    "mdpt_post_align_fit": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _D, _D, _VP, _VP, _VP, _SZ, _VP]),
+    "mdpt_post_align_metrics": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _D, _D, _VP, _VP, _VP, _SZ, _VP]),
+    "mdpt_post_align_apply": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _D, _D, _VP, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

@@ -69,6 +69,10 @@ def main():
     ap.add_argument("--mesh_points", action="store_true", help="mesh: a point cloud (one vertex per face) instead of triangles")
     ap.add_argument("--tiles", type=int, nargs=2, default=None, metavar=("NY", "NX"), help="save every image's depth at its own resolution from an NY x NX tile grid")
     ap.add_argument("--tile_overlap", type=float, default=0.25, metavar="F", help="tiles: the share of a tile side that neighbouring tiles have in common")
+    ap.add_argument("--truth", default=None, metavar="DIR", help="measured depth per image, DIR/<name>.npy (fp32, any size; zero or NaN: no measurement): "
+                    "fit the prediction to it, save <name>_true.npy (true depth at the truth's size) and <name>_metrics.json")
+    ap.add_argument("--truth_method", default="lstsq", choices=("lstsq", "median"), help="truth: least squares, or median and mean absolute deviation")
+    ap.add_argument("--truth_range", type=float, nargs=2, default=None, metavar=("MIN", "MAX"), help="truth: use measurements within MIN..MAX only")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mdpt_run_image needs an MI355X: no GPU visible (there is no CPU fallback)")
@@ -114,6 +118,7 @@ def main():
     save_block_norms(model, args, args.image_path or ["synthetic.npy"], [img])
     save_meshes(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
     save_tiled(model, args, args.image_path or ["synthetic.npy"], [img])
+    save_true_depth(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [depth])
 
 
 def crop_argument(args):
@@ -182,6 +187,29 @@ def save_tiled(model, args, paths, images):
         print("saved", out, f"({tiled.shape[2]}x{tiled.shape[1]} from {args.tiles[0]}x{args.tiles[1]} tiles)")
 
 
+def save_true_depth(args, is_metric, paths, depths):
+    """--truth: one fit_true_depth, one depth_metrics and one true_depth call over all images (what DPTModel.evaluate_depth runs after its
+    inference), the fit and the metrics read back once for the .json files"""
+    if not args.truth:
+        return
+    import json
+    from muggled_dpt_amd import postprocess as pp
+    stems = [os.path.splitext(os.path.basename(p))[0] for p in paths]
+    truths = [np.load(os.path.join(args.truth, stem + ".npy")).astype(np.float32) for stem in stems]
+    space = "depth" if is_metric else "inverse"
+    rng = (None, None) if args.truth_range is None else tuple(args.truth_range)
+    fit = pp.fit_true_depth(depths, truths, None, space, args.truth_method, rng)
+    metrics = pp.depth_metrics(depths, truths, fit, None, space, rng)
+    maps = pp.true_depth(depths, fit, [t.shape for t in truths], space)
+    fit, metrics = fit.cpu().tolist(), metrics.cpu().tolist()
+    for k, stem in enumerate(stems):
+        np.save(stem + "_true.npy", maps[k][0].cpu().numpy())
+        report = {"A": fit[k][0], "B": fit[k][1], "space": space, "method": args.truth_method, **dict(zip(pp.DEPTH_METRIC_NAMES, metrics[k]))}
+        with open(stem + "_metrics.json", "w") as fh:
+            json.dump(report, fh, indent=1)
+        print("saved", stem + "_true.npy", stem + "_metrics.json", f"(A {fit[k][0]:.6g}, B {fit[k][1]:.6g}, AbsRel {metrics[k][2]:.4g}, delta1 {metrics[k][7]:.4g})")
+
+
 def save_block_norms(model, args, paths, images):
     """--block_norms: one DPTModel.block_norms call per group of images that share a model tensor size"""
     if not args.block_norms:
@@ -236,6 +264,7 @@ def run_images(model, args, t0, is_metric=False):
     save_block_norms(model, args, args.image_path, images)
     save_meshes(args, is_metric, args.image_path, images, depths)
     save_tiled(model, args, args.image_path, images)
+    save_true_depth(args, is_metric, args.image_path, depths)
 
 
 if __name__ == "__main__":
