@@ -606,6 +606,40 @@ int mdpt_post_align_metrics(const mdpt_depth_pair* pairs_host, const void* pairs
 int mdpt_post_align_apply(const mdpt_depth_pair* pairs_host, const void* pairs_dev, int32_t P, int32_t pred_dtype, int32_t space, const void* fit_f64,
                           const int64_t* out_offsets_host, const void* out_offsets_dev, double dmin, double dmax, void* out_f32, void* stream);
 
+/* Rendering of depth meshes on the device (additive to ABI v6): the step of the reference's 3D viewer that needs a browser with WebGL there -
+ * 3dviewer/index.html:1158-1228 render_3d with the mesh shaders of shaders.js - for the slabs mdpt_post_mesh writes, read in place with their
+ * device-side counts: B meshes x V views in one call, four launches (clear, vertex stage, raster, resolve), nothing read back, nothing
+ * synchronises, bit-deterministic. Inputs: xyz_f32 [B,nv,3], uv_f32 [B,nv,2], faces_i32 [B,nf,3] (MDPT_MESH_TRIANGLES) or [B,nf,1] with nf == nv
+ * (MDPT_MESH_POINTS), counts_i32 [B,2] = {kept vertices, kept faces}, read on the device: vertices and faces at or beyond their image's count
+ * are not read, and a face that names a vertex outside the kept ones does nothing. One uint8 BGR texture [h,w,3] per mesh: an mdpt_texture table
+ * in DEVICE memory (tex_dev, 8-byte aligned; tex_host = the same records on the host, for the argument checks only). view_proj_f64 = device fp64
+ * [B,V,16] in the reference's layout, row vector times matrix: clip_j = x M[j] + y M[4+j] + z M[8+j] + M[12+j] (MAT4.multiply, uniformMatrix4fv).
+ *   vertex stage .. clip in fp64, nothing contracted; ndc = clip / w; screen x = (ndc_x + 1) / 2 W, y = (1 - ndc_y) / 2 H (pixel centres at + 0.5,
+ *                   row 0 at the top), each snapped to 1/256 pixel: rint(256 x), int32. Kept per vertex: the snapped x, y, 1 / w and
+ *                   z01 = (ndc_z + 1) / 2 in fp64. A vertex with w <= 0 or a snapped magnitude >= 2^30 is unusable and a face holding one is
+ *                   dropped whole (GL clips such a face against the near plane: a stated deviation).
+ *   coverage ...... int64 edge functions on the snapped coordinates at the pixel centres, top-left fill rule: a centre exactly on an edge belongs
+ *                   to the face whose interior is to its right or, on a horizontal edge, below. Exact, and watertight along shared edges.
+ *                   cull_back: faces that are not counter-clockwise with y up are skipped (gl.enable(CULL_FACE)); otherwise both windings draw.
+ *                   Faces without area never draw.
+ *   visibility .... z01 = (e0 z0 + e1 z1 + e2 z2) / (e0 + e1 + e2) in fp64 from the integer edge values e_k (opposite vertex k): linear in screen
+ *                   space, as GL's depth. Fragments outside [0, 1] are discarded. key = (fp32 bits of z01) << 32 | face index, merged into a
+ *                   uint64 z-buffer with a 64-bit integer atomic min: order-independent, ties go to the lower face index (LESS, drawn in order).
+ *   resolve ....... per pixel, for the winning face: b_k = (e_k / w_k) / sum_j (e_j / w_j) in fp64; uv = sum b_k uv_k; the texture sampled
+ *                   bilinearly as GL's LINEAR with CLAMP_TO_EDGE on level 0 (texel centres at + 0.5; v = 1 is the photo's first row), rounded to
+ *                   uint8 once (floor(c + 0.5)). Mipmapped minification (LINEAR_MIPMAP_LINEAR, textures.js:200) is NOT reproduced.
+ *   points ........ a square of point_size pixels centred on the snapped vertex, half = rint(128 point_size) in 1/256 pixel: the pixel centres
+ *                   with x - half <= centre < x + half (y alike), carrying the vertex's uv and z01.
+ * Outputs per mesh and view: color_bgra uint8 [B,V,H,W,4] (covered: alpha 255; background 0,0,0,0 = gl.clearColor(0,0,0,0)), 4-byte aligned;
+ * depth_f32 [B,V,H,W] or NULL: the clip-space w (background +inf); face_id_i32 [B,V,H,W] or NULL (background -1). Limits: B V <= 65535, sides of
+ * the output <= 32768, 0 < point_size <= 1024. scratch = mdpt_post_render_scratch_bytes (the z-buffer and the transformed vertices), 8-byte aligned. */
+typedef struct mdpt_texture { const void* bgr; int32_t h, w; } mdpt_texture;
+int mdpt_post_render_scratch_bytes(int32_t B, int32_t V, int32_t nv, int32_t nf, int32_t out_h, int32_t out_w, size_t* bytes);
+int mdpt_post_render(const void* xyz_f32, const void* uv_f32, const void* faces_i32, const void* counts_i32, int32_t B, int32_t nv, int32_t nf,
+                     int32_t mode, const mdpt_texture* tex_host, const void* tex_dev, const void* view_proj_f64, int32_t V, int32_t out_h, int32_t out_w,
+                     int32_t cull_back, double point_size, void* color_bgra, void* depth_f32, void* face_id_i32, void* scratch, size_t scratch_bytes,
+                     void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

@@ -230,6 +230,22 @@ struct MeshJob {
 };
 inline size_t mesh_blocks(size_t n) { return (n + 255) / 256; }  // the compaction's blocks: 256 vertices (or grid cells) each
 
+// one render call (postprocess.hip render_* kernels), by value: the slabs of mdpt_launch_post_mesh read in place (xyz [B, nv, 3], uv [B, nv, 2], faces
+// [B, nf, 3] or, for points, [B, nf = nv, 1], counts [B, 2] on the device), one texture per mesh (tex: B RenderTex records in DEVICE memory, =
+// mdpt_texture of include/mdpt.h), view_proj fp64 [B, V, 16] (clip = [x, y, z, 1] M), the H x W viewport, half = the points' half-size in 1/256
+// pixel, and the scratch: verts [B V, nv] transformed vertices, zbuf [B V, H W] keys
+struct RenderTex { const unsigned char* bgr; int h, w; };
+struct RenderVertex { int x, y; double invw, z01; };  // snapped screen position (x == RENDER_UNUSABLE: w <= 0 or off the fixed-point range)
+#define RENDER_UNUSABLE (-2147483647 - 1)
+#define RENDER_SMALL_BOX 64    // a face whose clipped box holds at most this many pixels is walked by its own lane, a larger one by its workgroup
+#define RENDER_MAX_SIDE 32768  // of the viewport: pixel centres stay below 2^23 in 1/256 pixel
+struct RenderJob {
+    const float* xyz; const float* uv; const int* faces; const int* counts; const RenderTex* tex; const double* view_proj;
+    int B, V, nv, nf, H, W, points, cull_back, half;
+    RenderVertex* verts; unsigned long long* zbuf;
+};
+inline size_t render_scratch_bytes(size_t B, size_t V, size_t nv, size_t H, size_t W) { return B * V * (nv * sizeof(RenderVertex) + H * W * 8); }
+
 // one tile of tiled high-resolution inference (postprocess.hip tile_* kernels; = mdpt_tile of include/mdpt.h): its h x w map (the table's dtype) and
 // its half-open pixel box in the photo. The table lives in DEVICE memory (any number of tiles); the kernels index it by tile.
 struct PostTile { const void* map; int h, w, x1, y1, x2, y2; };
@@ -309,6 +325,9 @@ int mdpt_launch_post_block_norm_tiles(const PostRunTable& t, unsigned char* out,
 // the kept vertices (xyz [B, nv, 3], uv [B, nv, 2]) and faces ([B, nf, 3] or, for points, [B, nv, 1]) packed at the front of each image's slab,
 // counts [B, 2] = {kept vertices, kept faces}, bounds [B, 2, 3] = {min xyz, max xyz}. Five launches (four for points), no single-pass scan.
 int mdpt_launch_post_mesh(const MeshJob& m, float* xyz, float* uv, unsigned* faces, int* counts, float* bounds, hipStream_t stream);
+// rendering of depth meshes (the 3D viewer's render_3d): RenderJob above -> color uint8 BGRA [B, V, H, W, 4] (background 0, 0, 0, 0) and, where not
+// null, depth fp32 [B, V, H, W] (clip-space w, background +inf) and ids int32 [B, V, H, W] (the face's index, background -1). Four launches.
+int mdpt_launch_post_render(const RenderJob& r, unsigned char* color, float* depth, int* ids, hipStream_t stream);
 // tiled high-resolution inference: tiles = T PostTile records on the device (maps of dtype dt). Fit: every tile's map against the guide (gh x gw,
 // dtype gdt, covering the H x W photo) over the tile's box -> sums [T, 6] fp64 {n, Sx, Sy, Sxx, Sxy, Syy}, fit [T, 2] fp64 {scale, shift}; parts =
 // [T, max_chunks, 6] fp64 scratch. Two launches, bit-deterministic. Blend: the feathered weighted mean of the fitted tiles -> out fp32 [H, W]; fit ==

@@ -547,4 +547,52 @@ int mdpt_post_align_apply(const mdpt_depth_pair* pairs_host, const void* pairs_d
     return 0;
 }
 
+// ---- rendering of depth meshes (3dviewer/index.html:1158-1228 render_3d, shaders.js mesh shaders)
+static_assert(sizeof(mdpt_texture) == sizeof(RenderTex) && sizeof(mdpt_texture) == 16, "mdpt_texture of include/mdpt.h is RenderTex of mdpt_kernels.h");
+
+static int check_render_sizes(int32_t B, int32_t V, int32_t nv, int32_t nf, int32_t out_h, int32_t out_w) {
+    if (B <= 0 || V <= 0 || (int64_t)B * V > 65535) return fail(MDPT_E_INVALID, "bad batch %d x %d views (the product must be 1 .. 65535 per call)", B, V);
+    if (nv <= 0 || nf <= 0) return fail(MDPT_E_INVALID, "bad mesh capacity: %d vertices, %d faces", nv, nf);
+    if (out_h <= 0 || out_w <= 0 || out_h > RENDER_MAX_SIDE || out_w > RENDER_MAX_SIDE)
+        return fail(MDPT_E_INVALID, "bad output size %dx%d (sides of 1 .. %d)", out_h, out_w, RENDER_MAX_SIDE);
+    return 0;
+}
+
+int mdpt_post_render_scratch_bytes(int32_t B, int32_t V, int32_t nv, int32_t nf, int32_t out_h, int32_t out_w, size_t* bytes) {
+    if (!bytes) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_render_sizes(B, V, nv, nf, out_h, out_w));
+    *bytes = render_scratch_bytes((size_t)B, (size_t)V, (size_t)nv, (size_t)out_h, (size_t)out_w);
+    return 0;
+}
+
+int mdpt_post_render(const void* xyz_f32, const void* uv_f32, const void* faces_i32, const void* counts_i32, int32_t B, int32_t nv, int32_t nf,
+                     int32_t mode, const mdpt_texture* tex_host, const void* tex_dev, const void* view_proj_f64, int32_t V, int32_t out_h, int32_t out_w,
+                     int32_t cull_back, double point_size, void* color_bgra, void* depth_f32, void* face_id_i32, void* scratch, size_t scratch_bytes,
+                     void* stream) {
+    if (!xyz_f32 || !uv_f32 || !faces_i32 || !counts_i32 || !tex_host || !tex_dev || !view_proj_f64 || !color_bgra || !scratch)
+        return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_render_sizes(B, V, nv, nf, out_h, out_w));
+    if (mode != MDPT_MESH_TRIANGLES && mode != MDPT_MESH_POINTS) return fail(MDPT_E_INVALID, "unknown mesh mode %d", mode);
+    if (mode == MDPT_MESH_POINTS && nf != nv) return fail(MDPT_E_INVALID, "a point list holds one face per vertex: nf %d, nv %d", nf, nv);
+    if (!(point_size > 0.0 && point_size <= 1024.0)) return fail(MDPT_E_INVALID, "point_size must be in (0, 1024], got %g", point_size);
+    for (int i = 0; i < B; ++i)
+        if (!tex_host[i].bgr || tex_host[i].h <= 0 || tex_host[i].w <= 0)
+            return fail(MDPT_E_INVALID, "null texture or bad texture size %dx%d (mesh %d)", tex_host[i].h, tex_host[i].w, i);
+    if ((((uintptr_t)tex_dev | (uintptr_t)view_proj_f64 | (uintptr_t)scratch) & 7) != 0 ||
+        (((uintptr_t)xyz_f32 | (uintptr_t)uv_f32 | (uintptr_t)faces_i32 | (uintptr_t)counts_i32 | (uintptr_t)color_bgra | (uintptr_t)depth_f32 |
+          (uintptr_t)face_id_i32) & 3) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table, the matrices and the scratch need 8 bytes, the slabs and the outputs 4)");
+    const size_t need = render_scratch_bytes((size_t)B, (size_t)V, (size_t)nv, (size_t)out_h, (size_t)out_w);
+    if (scratch_bytes < need) return fail(MDPT_E_INVALID, "render scratch of %zu bytes, %zu needed (mdpt_post_render_scratch_bytes)", scratch_bytes, need);
+    RenderJob r{};
+    r.xyz = (const float*)xyz_f32, r.uv = (const float*)uv_f32, r.faces = (const int*)faces_i32, r.counts = (const int*)counts_i32;
+    r.tex = (const RenderTex*)tex_dev, r.view_proj = (const double*)view_proj_f64;
+    r.B = B, r.V = V, r.nv = nv, r.nf = nf, r.H = out_h, r.W = out_w, r.points = mode == MDPT_MESH_POINTS, r.cull_back = cull_back != 0;
+    r.half = (int)nearbyint(point_size * 128.0);
+    r.zbuf = (unsigned long long*)scratch;
+    r.verts = (RenderVertex*)(r.zbuf + (size_t)B * V * out_h * out_w);
+    CHK(mdpt_launch_post_render(r, (unsigned char*)color_bgra, (float*)depth_f32, (int*)face_id_i32, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

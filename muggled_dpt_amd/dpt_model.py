@@ -1061,6 +1061,33 @@ class DPTModel(nn.Module):
         metrics = depth_metrics(preds, truths, fit, valid, space, truth_range, staged=staged)
         return fit, metrics, true_depth(preds, fit, staged[3], space)
 
+    def render_views(self, image_bgr: np.ndarray, view_proj=None, out_wh=(1280, 720), max_side_length: int | None = None,
+                     use_square_sizing: bool = True, fov_deg: float | None = None, min_depth: float | None = None, max_depth: float | None = None,
+                     edge_threshold: float | None = None, target_num_faces=None, mode: str = "triangles", cull: str = "back", point_size: float = 2.0,
+                     return_depth: bool = False, return_face_ids: bool = False, **camera):
+        """One photo -> its depth mesh rendered from V viewpoints, what the reference's 3D viewer shows and saves frame by frame: inference, then
+        postprocess.pack_depth_u24_frames (edge alpha), depth_frames_to_mesh and render_mesh with the photo as the texture, all on the device
+        with nothing read back. view_proj: [V,16] matrices (orbit_camera.viewer_view_proj / swing_views / stereo_views), or None: one view of
+        the viewer's start pose, **camera going to orbit_camera.viewer_view_proj (tilt_deg, view_offset, view_fov_deg, orthographic, camera).
+        The mesh controls default to the viewer's as it starts (postprocess.MESH_*), point_size to its slider's 2. -> render_mesh's result with
+        B = 1: color uint8 [1,V,h,w,4] and, as asked, depth / face ids [1,V,h,w]."""
+        from . import orbit_camera, postprocess as pp
+        fov_deg = pp.MESH_FOV_DEG if fov_deg is None else fov_deg
+        min_depth = pp.MESH_MIN_DEPTH if min_depth is None else min_depth
+        max_depth = pp.MESH_MAX_DEPTH if max_depth is None else max_depth
+        if view_proj is None:
+            view_proj = orbit_camera.viewer_view_proj(min_depth=min_depth, max_depth=max_depth, aspect=out_wh[0] / out_wh[1], **camera)[None]
+        elif camera:
+            raise TypeError(f"render_views: {sorted(camera)} only apply when view_proj is None")
+        is_metric = bool(self.config.get("is_metric", False))
+        prediction = self.inference(image_bgr, max_side_length, use_square_sizing)
+        frames = pp.pack_depth_u24_frames(prediction, is_metric=is_metric)
+        xyz, uv, faces, counts, _ = pp.depth_frames_to_mesh(
+            frames, (image_bgr.shape[1], image_bgr.shape[0]), fov_deg, min_depth, max_depth, is_metric,
+            pp.MESH_EDGE_THRESHOLD if edge_threshold is None else edge_threshold, pp.MESH_TARGET_FACES if target_num_faces is None else target_num_faces,
+            mode=mode)
+        return pp.render_mesh(xyz, uv, faces, counts, [image_bgr], view_proj, out_wh, cull, point_size, return_depth, return_face_ids)
+
     def prepare_image_bgr(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True,
                           interpolation_mode: str = "bilinear", *, crop=None) -> Tensor:
         return self.patch_embed.prepare_image(image_bgr, max_side_length, use_square_sizing, interpolation_mode, crop=crop)

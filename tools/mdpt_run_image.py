@@ -73,6 +73,13 @@ def main():
                     "fit the prediction to it, save <name>_true.npy (true depth at the truth's size) and <name>_metrics.json")
     ap.add_argument("--truth_method", default="lstsq", choices=("lstsq", "median"), help="truth: least squares, or median and mean absolute deviation")
     ap.add_argument("--truth_range", type=float, nargs=2, default=None, metavar=("MIN", "MAX"), help="truth: use measurements within MIN..MAX only")
+    ap.add_argument("--render", default=None, metavar="DIR", help="render every image's depth mesh from moving viewpoints (the 3D viewer's view) and "
+                    "save <name>_view###.png (RGBA) into DIR; the mesh follows --mesh_faces / --mesh_fov / --mesh_points")
+    ap.add_argument("--render_views", type=int, default=16, metavar="N", help="render: number of views on the swing")
+    ap.add_argument("--render_swing", type=float, nargs=2, default=(8.0, 4.0), metavar=("YAW", "PITCH"), help="render: half-axes of the swing in degrees")
+    ap.add_argument("--render_wh", type=int, nargs=2, default=(1280, 720), metavar=("W", "H"), help="render: output size")
+    ap.add_argument("--render_stereo", type=float, default=None, metavar="BASELINE", help="render: a left / right pair BASELINE world units apart "
+                    "instead of the swing (views 000 and 001)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mdpt_run_image needs an MI355X: no GPU visible (there is no CPU fallback)")
@@ -117,6 +124,7 @@ def main():
     save_cutouts(args, args.image_path or ["synthetic.npy"], [img], [depth])
     save_block_norms(model, args, args.image_path or ["synthetic.npy"], [img])
     save_meshes(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
+    save_renders(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
     save_tiled(model, args, args.image_path or ["synthetic.npy"], [img])
     save_true_depth(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [depth])
 
@@ -173,6 +181,34 @@ def save_meshes(args, is_metric, paths, images, depths):
         else:
             mesh_io.write_glb(stem + ".glb", xyz, uv, faces, rgb, bounds)
             print("saved", stem + ".glb", f"({xyz.shape[0]} vertices, {faces.shape[0]} faces)")
+
+
+def save_renders(args, is_metric, paths, images, depths):
+    """--render: pack_depth_u24_frames -> depth_frames_to_mesh -> render_mesh per image (photo sizes set the grids), every view of an image in one
+    call; the views are a closed swing around the viewer's start pose, or a stereo pair"""
+    if not args.render:
+        return
+    from muggled_dpt_amd import mesh_io, orbit_camera
+    from muggled_dpt_amd import postprocess as pp
+    os.makedirs(args.render, exist_ok=True)
+    w, h = args.render_wh
+    if args.render_stereo is not None:
+        views = orbit_camera.stereo_views(args.render_stereo, aspect=w / h)
+    else:
+        views = orbit_camera.swing_views(args.render_views, args.render_swing[0], args.render_swing[1], aspect=w / h)
+    for path, img, depth in zip(paths, images, depths):
+        frames = pp.pack_depth_u24_frames(depth, is_metric=is_metric)
+        xyz, uv, faces, counts, _ = pp.depth_frames_to_mesh(frames, (img.shape[1], img.shape[0]), pp.MESH_FOV_DEG if args.mesh_fov is None else args.mesh_fov,
+                                                           is_metric=is_metric,
+                                                           target_num_faces=pp.MESH_TARGET_FACES if args.mesh_faces is None else args.mesh_faces,
+                                                           mode="points" if args.mesh_points else "triangles")
+        color = pp.render_mesh(xyz, uv, faces, counts, [img], views, (w, h), point_size=2.0)[0]
+        rgba = color[..., [2, 1, 0, 3]].cpu().numpy()
+        stem = os.path.join(args.render, os.path.splitext(os.path.basename(path))[0])
+        for k in range(rgba.shape[0]):
+            with open(f"{stem}_view{k:03d}.png", "wb") as fh:
+                fh.write(mesh_io.encode_png(rgba[k]))
+        print("saved", f"{stem}_view000.png .. _view{rgba.shape[0] - 1:03d}.png", f"({w}x{h}, {float((rgba[..., 3] > 0).mean()):.3f} of the pixels covered)")
 
 
 def save_tiled(model, args, paths, images):
@@ -263,6 +299,7 @@ def run_images(model, args, t0, is_metric=False):
     save_cutouts(args, args.image_path, images, depths)
     save_block_norms(model, args, args.image_path, images)
     save_meshes(args, is_metric, args.image_path, images, depths)
+    save_renders(args, is_metric, args.image_path, images, depths)
     save_tiled(model, args, args.image_path, images)
     save_true_depth(args, is_metric, args.image_path, depths)
 
