@@ -606,6 +606,36 @@ int mdpt_post_align_metrics(const mdpt_depth_pair* pairs_host, const void* pairs
 int mdpt_post_align_apply(const mdpt_depth_pair* pairs_host, const void* pairs_dev, int32_t P, int32_t pred_dtype, int32_t space, const void* fit_f64,
                           const int64_t* out_offsets_host, const void* out_offsets_dev, double dmin, double dmax, void* out_f32, void* stream);
 
+/* Photo-guided depth upsampling on the device (additive to ABI v6): He & Sun's fast guided filter with the uint8 BGR photo as the guide, for the
+ * step that every route above takes bilinearly - a map of about model size brought back to the photo's size - so that depth edges follow the photo's
+ * edges instead of becoming ramps. P pairs of any sizes in one call, six launches whatever P is, nothing read back, nothing synchronises,
+ * bit-deterministic, every pair independent of the others in the call. A pair is an mdpt_guided_pair record: the h x w map (map_dtype), the photo of
+ * H x W pixels (H >= h, W >= w) whose rows start `pitch` bytes apart (pitch >= 3 W; no alignment is asked: the photo is read byte by byte, in place),
+ * the fp32 H x W output (4-byte aligned), and scratch_off, the byte offset of the pair's own scratch inside `scratch` (a multiple of 8; the pair
+ * needs mdpt_post_guided_scratch_bytes of its record alone from there, and the regions of a call must not overlap). The table is passed twice:
+ * pairs_dev in DEVICE memory (8-byte aligned), pairs_host the same records on the host, read during the call for the argument checks only.
+ * All arithmetic is fp64, nothing contracted:
+ *   cell sums ..... photo pixel (Y, X) belongs to cell (Y h / H, X w / W) in integer arithmetic; per cell the pixel count n and the channel sums
+ *                   S_c as 64-bit integers (exact); the low-resolution guide is g_c = (S_c / n) / 255, c = B, G, R.
+ *   coefficients .. the window of cell (j, i) is the cells within `radius` in both axes, clipped to the grid; a window mean is the sum over it divided
+ *                   by its own count, summed directly (along the row, then down the column, each in index order; no running sums). From the window
+ *                   means of g (3), g g^T (6), p (the map) and g p (3): Sigma = mean(g g^T) - mean(g) mean(g)^T + eps I,
+ *                   a = Sigma^-1 (mean(g p) - mean(g) mean(p)) by Cholesky, b = mean(p) - a . mean(g).
+ *   their means ... the same clipped window mean of (a_B, a_G, a_R, b) -> fp64 [h, w, 4], kept in the pair's scratch and, where coeffs_f64 is not NULL,
+ *                   also written there, pair p at 4 sum_{q < p} h_q w_q doubles (8-byte aligned).
+ *   apply ......... per photo pixel the four mean coefficients resampled bilinearly at the pixel's centre, u = (X + 0.5) w / W - 0.5 clamped to the grid
+ *                   (fp64 weights, rows first: the resampler of the tile fit and of mdpt_post_align_*), q = a_B B / 255 + a_G G / 255 + a_R R / 255 + b,
+ *                   rounded to fp32 once.
+ * radius 0 gives a = 0 exactly and the bilinear resize of the map; a flat photo gives the window mean of the map; a map that is an affine function of
+ * the low-resolution guide comes back as that function of the photo. A value that is not finite stays inside the windows that see it.
+ * Checks (MDPT_E_INVALID, nothing launched): null pointers, P outside 1 .. 65535, radius outside 0 .. 64, eps <= 0 or not finite, sizes <= 0,
+ * H < h or W < w, pitch < 3 W, H W or h w >= 2^31, misaligned map / output / table / scratch / coefficients, a scratch region outside
+ * scratch_bytes or overlapping another. mdpt_post_guided_scratch_bytes reads only h and w of the records: the bytes of P regions laid end to end. */
+typedef struct mdpt_guided_pair { const void* map; int32_t h, w; const void* photo; int64_t pitch; int32_t H, W; void* out; int64_t scratch_off; } mdpt_guided_pair;
+int mdpt_post_guided_scratch_bytes(const mdpt_guided_pair* pairs_host, int32_t P, size_t* bytes);
+int mdpt_post_guided_upsample(const mdpt_guided_pair* pairs_host, const void* pairs_dev, int32_t P, int32_t map_dtype, int32_t radius, double eps,
+                              void* scratch, size_t scratch_bytes, void* coeffs_f64, void* stream);
+
 /* Rendering of depth meshes on the device (additive to ABI v6): the step of the reference's 3D viewer that needs a browser with WebGL there -
  * 3dviewer/index.html:1158-1228 render_3d with the mesh shaders of shaders.js - for the slabs mdpt_post_mesh writes, read in place with their
  * device-side counts: B meshes x V views in one call, four launches (clear, vertex stage, raster, resolve), nothing read back, nothing

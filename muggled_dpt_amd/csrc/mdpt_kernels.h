@@ -274,6 +274,17 @@ inline size_t align_scratch_bytes(size_t P, size_t max_chunks) {
     return align_parts_doubles(P, max_chunks) * sizeof(double) + P * (ALIGN_HIST_WORDS + ALIGN_STATE_WORDS) * sizeof(unsigned);
 }
 
+// one map / photo pair of the photo-guided upsampling (postprocess.hip guided_* kernels; = mdpt_guided_pair of include/mdpt.h): the h x w map (the
+// table's dtype), the uint8 BGR photo of H x W pixels whose rows lie `pitch` bytes apart (any alignment), the fp32 H x W output, and where the pair's
+// scratch starts (bytes from the call's scratch pointer, a multiple of 8). Device table, indexed by pair.
+struct GuidedPair { const void* map; int h, w; const unsigned char* photo; long long pitch; int H, W; float* out; long long scratch_off; };
+#define GUIDED_MAX_RADIUS 64
+#define GUIDED_MOMENTS 13  // window sums of a cell: g (3), g g^T (6: BB BG BR GG GR RR), p, g p (3)
+// a pair's scratch in 8-byte words per cell: the integer cell sums {n, SB, SG, SR}, the coefficients {aB, aG, aR, b} as four planes, their window means
+// interleaved [h, w, 4], and the row sums of whichever window pass is running (13 planes, the coefficient pass uses the first 4)
+#define GUIDED_WORDS_PER_CELL (4 + 4 + 4 + GUIDED_MOMENTS)
+inline size_t guided_pair_scratch_bytes(size_t h, size_t w) { return h * w * GUIDED_WORDS_PER_CELL * 8; }
+
 // the same for every block of the encoder in ONE launch (the LUTs depend on weights and window sizes only, not on activations)
 struct SwinCpbBatch {
     const float* w1[32]; const float* b1[32]; const float* w2[32]; float* lut[32];
@@ -348,6 +359,13 @@ int mdpt_launch_post_align_metrics(const AlignPair* pairs, int P, int max_chunks
                                    double* parts, double* metrics, hipStream_t stream);
 int mdpt_launch_post_align_apply(const AlignPair* pairs, int P, size_t max_pixels, int dt, int inverse, const double* fit, const long long* offs, double dmin,
                                  double dmax, float* out, hipStream_t stream);
+
+// photo-guided upsampling (He & Sun's fast guided filter with the photo as guide): pairs = P GuidedPair records on the device (maps of dtype dt), each
+// pair's scratch at scratch + scratch_off. Six launches whatever P is (cell sums, moment rows, moment columns + solve, coefficient rows, coefficient
+// columns, apply); coeffs != null: pair p's mean coefficients fp64 [h, w, 4] also at coeffs + 4 sum_{q < p} h_q w_q. max_* = the largest of the table
+// (they size the grids). Bit-deterministic.
+int mdpt_launch_post_guided(const GuidedPair* pairs, int P, int dt, int radius, double eps, int max_h, int max_w, int max_H, int max_W, char* scratch,
+                            double* coeffs, hipStream_t stream);
 
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);

@@ -1,6 +1,9 @@
 // libmdpt: the depth post-processing entry points of include/mdpt.h (mdpt_post_*). None of them takes a handle, a plan or a workspace: argument
 // checks, the image tables of the per-image kernels, and one launcher call (postprocess.hip) each.
 #include "mdpt_internal.h"
+#include <algorithm>
+#include <utility>
+#include <vector>
 
 extern "C" {
 
@@ -544,6 +547,65 @@ int mdpt_post_align_apply(const mdpt_depth_pair* pairs_host, const void* pairs_d
     }
     CHK(mdpt_launch_post_align_apply((const AlignPair*)pairs_dev, P, max_pixels, pred_dtype, space == MDPT_ALIGN_INVERSE, (const double*)fit_f64,
                                      (const long long*)out_offsets_dev, dmin, dmax, (float*)out_f32, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- photo-guided upsampling (the fast guided filter with the photo as guide)
+static_assert(sizeof(mdpt_guided_pair) == sizeof(GuidedPair) && sizeof(mdpt_guided_pair) == 56, "mdpt_guided_pair of include/mdpt.h is GuidedPair of mdpt_kernels.h");
+
+// the host table's map sizes: positive, h w < 2^31; *bytes = the scratch of the P regions laid end to end
+static int check_guided_sizes(const mdpt_guided_pair* pairs, int32_t P, size_t* bytes) {
+    if (!pairs) return fail(MDPT_E_INVALID, "null argument");
+    if (P <= 0 || P > 65535) return fail(MDPT_E_INVALID, "bad pair count %d (1 .. 65535 per call)", P);
+    size_t total = 0;
+    for (int p = 0; p < P; ++p) {
+        const mdpt_guided_pair& q = pairs[p];
+        if (q.h <= 0 || q.w <= 0 || (size_t)q.h * q.w >= ((size_t)1 << 31)) return fail(MDPT_E_INVALID, "bad map size %dx%d (pair %d; h w < 2^31)", q.h, q.w, p);
+        total += guided_pair_scratch_bytes((size_t)q.h, (size_t)q.w);
+    }
+    *bytes = total;
+    return 0;
+}
+
+int mdpt_post_guided_scratch_bytes(const mdpt_guided_pair* pairs_host, int32_t P, size_t* bytes) {
+    if (!bytes) return fail(MDPT_E_INVALID, "null argument");
+    return check_guided_sizes(pairs_host, P, bytes);
+}
+
+int mdpt_post_guided_upsample(const mdpt_guided_pair* pairs_host, const void* pairs_dev, int32_t P, int32_t map_dtype, int32_t radius, double eps,
+                              void* scratch, size_t scratch_bytes, void* coeffs_f64, void* stream) {
+    if (!pairs_host || !pairs_dev || !scratch) return fail(MDPT_E_INVALID, "null argument");
+    if (!tensor_dtype_ok(map_dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", map_dtype);
+    if (radius < 0 || radius > GUIDED_MAX_RADIUS) return fail(MDPT_E_INVALID, "radius %d: the window radius must be 0 .. %d cells", radius, GUIDED_MAX_RADIUS);
+    if (!(eps > 0.0) || eps > 1e300) return fail(MDPT_E_INVALID, "eps must be finite and > 0, got %g", eps);
+    size_t packed;
+    CHK(check_guided_sizes(pairs_host, P, &packed));
+    if ((((uintptr_t)pairs_dev | (uintptr_t)scratch | (uintptr_t)coeffs_f64) & 7) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table, the scratch and the coefficients need 8 bytes)");
+    int max_h = 0, max_w = 0, max_H = 0, max_W = 0;
+    std::vector<std::pair<size_t, size_t>> regions;
+    for (int p = 0; p < P; ++p) {
+        const mdpt_guided_pair& q = pairs_host[p];
+        if (!q.map || !q.photo || !q.out) return fail(MDPT_E_INVALID, "null map, photo or output (pair %d)", p);
+        if (((uintptr_t)q.map & (dtype_bytes(map_dtype) - 1)) != 0 || ((uintptr_t)q.out & 3) != 0)
+            return fail(MDPT_E_INVALID, "misaligned map or output (pair %d: the map needs its element, the output 4 bytes)", p);
+        if (q.H < q.h || q.W < q.w)
+            return fail(MDPT_E_INVALID, "the %dx%d photo of pair %d is smaller than its %dx%d map: guided upsampling only enlarges", q.H, q.W, p, q.h, q.w);
+        if ((size_t)q.H * q.W >= ((size_t)1 << 31)) return fail(MDPT_E_INVALID, "a photo of %dx%d is too large (H W < 2^31, pair %d)", q.H, q.W, p);
+        if (q.pitch < 3 * (int64_t)q.W) return fail(MDPT_E_INVALID, "a row pitch of %lld bytes is less than the %d pixels of a row (pair %d)", (long long)q.pitch, q.W, p);
+        const size_t need = guided_pair_scratch_bytes((size_t)q.h, (size_t)q.w);
+        if (q.scratch_off < 0 || (q.scratch_off & 7) != 0 || (size_t)q.scratch_off > scratch_bytes || scratch_bytes - (size_t)q.scratch_off < need)
+            return fail(MDPT_E_INVALID, "the scratch region of pair %d (offset %lld, %zu bytes) is misaligned or outside the %zu bytes given "
+                        "(mdpt_post_guided_scratch_bytes)", p, (long long)q.scratch_off, need, scratch_bytes);
+        regions.emplace_back((size_t)q.scratch_off, (size_t)q.scratch_off + need);
+        max_h = q.h > max_h ? q.h : max_h, max_w = q.w > max_w ? q.w : max_w;
+        max_H = q.H > max_H ? q.H : max_H, max_W = q.W > max_W ? q.W : max_W;
+    }
+    std::sort(regions.begin(), regions.end());
+    for (size_t k = 1; k < regions.size(); ++k)
+        if (regions[k].first < regions[k - 1].second) return fail(MDPT_E_INVALID, "the scratch regions of two pairs overlap (at byte %zu)", regions[k].first);
+    CHK(mdpt_launch_post_guided((const GuidedPair*)pairs_dev, P, map_dtype, radius, eps, max_h, max_w, max_H, max_W, (char*)scratch, (double*)coeffs_f64,
+                                (hipStream_t)stream));
     return 0;
 }
 

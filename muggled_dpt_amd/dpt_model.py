@@ -1061,6 +1061,16 @@ class DPTModel(nn.Module):
         metrics = depth_metrics(preds, truths, fit, valid, space, truth_range, staged=staged)
         return fit, metrics, true_depth(preds, fit, staged[3], space)
 
+    def inference_guided(self, images_bgr, radius: int = 8, eps: float = 1e-4, max_side_length: int | None = None, use_square_sizing: bool = True,
+                         batch_size: int = 32) -> list[Tensor]:
+        """Depth of every photo at the PHOTO's own size with the photo as the guide of the enlargement -> a list of fp32 [1,H_i,W_i] maps in input
+        order (not in the reference, whose demos resize the model's map bilinearly): one inference_images call, then one
+        postprocess.guided_upsample_images call over all maps and photos (six launches, nothing read back). images_bgr as inference_images takes
+        them; no photo may be smaller than the model's map of it. radius (cells of the map) and eps are guided_upsample_images'."""
+        from .postprocess import guided_upsample_images
+        preds = self.inference_images(images_bgr, max_side_length, use_square_sizing, batch_size)
+        return guided_upsample_images(preds, list(images_bgr), radius, eps)
+
     def render_views(self, image_bgr: np.ndarray, view_proj=None, out_wh=(1280, 720), max_side_length: int | None = None,
                      use_square_sizing: bool = True, fov_deg: float | None = None, min_depth: float | None = None, max_depth: float | None = None,
                      edge_threshold: float | None = None, target_num_faces=None, mode: str = "triangles", cull: str = "back", point_size: float = 2.0,

@@ -53,6 +53,7 @@ MESH_TRIANGLES, MESH_POINTS = 0, 1  # MDPT_MESH_*
 ALIGN_INVERSE, ALIGN_DEPTH = 0, 1  # MDPT_ALIGN_* spaces
 ALIGN_LSTSQ, ALIGN_MEDIAN = 0, 1  # MDPT_ALIGN_* methods
 ALIGN_NUM_METRICS = 11  # MDPT_ALIGN_NUM_METRICS
+GUIDED_MAX_RADIUS = 64  # the largest window radius of mdpt_post_guided_upsample
 
 
 def _hipcc() -> str:
@@ -238,6 +239,8 @@ SYMBOLS = {
     "mdpt_post_align_fit": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _D, _D, _VP, _VP, _VP, _SZ, _VP]),
     "mdpt_post_align_metrics": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _D, _D, _VP, _VP, _VP, _SZ, _VP]),
     "mdpt_post_align_apply": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _D, _D, _VP, _VP]),
+    "mdpt_post_guided_scratch_bytes": (ctypes.c_int, [_VP, _I, ctypes.POINTER(_SZ)]),
+    "mdpt_post_guided_upsample": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _D, _VP, _SZ, _VP, _VP]),
     "mdpt_post_render_scratch_bytes": (ctypes.c_int, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(_SZ)]),
     "mdpt_post_render": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _I, _I, _I, _I, _D, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),

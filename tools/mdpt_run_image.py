@@ -18,6 +18,9 @@ are the viewer's mesh density, FOV and point mode.
 For one image or several, --tiles NY NX saves the depth at the PHOTO's resolution from an NY x NX grid of overlapping tiles (DPTModel.inference_tiled:
 every tile fitted to the whole-image prediction with one scale and one shift, then feather-blended; --tile_overlap is the share of a tile side that
 neighbours have in common): <name>_tiled.npy, fp32 [H, W], in the current directory.
+For one image or several, --guided RADIUS EPS saves the depth at the PHOTO's resolution with the photo as the guide of the enlargement
+(postprocess.guided_upsample_images, one call for the whole list; RADIUS in cells of the model's map, EPS the variance below which the photo's texture
+is ignored, e.g. 8 1e-4; no photo may be smaller than the model's map of it): <name>_guided.npy, fp32 [H, W], in the current directory.
 --crop X1 Y1 X2 Y2 is the reference's --crop with a stored box: normalised corners, applied to every image before it is predicted
 (crop_slices_from_norm: a side under 5 px falls back to the image's full extent); every output is then that of the cropped image.
 
@@ -69,6 +72,8 @@ def main():
     ap.add_argument("--mesh_points", action="store_true", help="mesh: a point cloud (one vertex per face) instead of triangles")
     ap.add_argument("--tiles", type=int, nargs=2, default=None, metavar=("NY", "NX"), help="save every image's depth at its own resolution from an NY x NX tile grid")
     ap.add_argument("--tile_overlap", type=float, default=0.25, metavar="F", help="tiles: the share of a tile side that neighbouring tiles have in common")
+    ap.add_argument("--guided", nargs=2, default=None, metavar=("RADIUS", "EPS"), help="save every image's depth at its own resolution, enlarged with "
+                    "the photo as the guide (fast guided filter): window radius in map cells and regularisation, e.g. 8 1e-4")
     ap.add_argument("--truth", default=None, metavar="DIR", help="measured depth per image, DIR/<name>.npy (fp32, any size; zero or NaN: no measurement): "
                     "fit the prediction to it, save <name>_true.npy (true depth at the truth's size) and <name>_metrics.json")
     ap.add_argument("--truth_method", default="lstsq", choices=("lstsq", "median"), help="truth: least squares, or median and mean absolute deviation")
@@ -127,6 +132,7 @@ def main():
     save_renders(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
     save_tiled(model, args, args.image_path or ["synthetic.npy"], [img])
     save_true_depth(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [depth])
+    save_guided(args, args.image_path or ["synthetic.npy"], [img], [depth])
 
 
 def crop_argument(args):
@@ -246,6 +252,18 @@ def save_true_depth(args, is_metric, paths, depths):
         print("saved", stem + "_true.npy", stem + "_metrics.json", f"(A {fit[k][0]:.6g}, B {fit[k][1]:.6g}, AbsRel {metrics[k][2]:.4g}, delta1 {metrics[k][7]:.4g})")
 
 
+def save_guided(args, paths, images, depths):
+    """--guided: one postprocess.guided_upsample_images call over all images, the fp32 map at each image's own size"""
+    if not args.guided:
+        return
+    from muggled_dpt_amd.postprocess import guided_upsample_images
+    maps = guided_upsample_images(depths, images, int(args.guided[0]), float(args.guided[1]))
+    for path, m in zip(paths, maps):
+        out = os.path.splitext(os.path.basename(path))[0] + "_guided.npy"
+        np.save(out, m[0].cpu().numpy())
+        print("saved", out, f"({m.shape[2]}x{m.shape[1]}, radius {int(args.guided[0])}, eps {float(args.guided[1]):g})")
+
+
 def save_block_norms(model, args, paths, images):
     """--block_norms: one DPTModel.block_norms call per group of images that share a model tensor size"""
     if not args.block_norms:
@@ -302,6 +320,7 @@ def run_images(model, args, t0, is_metric=False):
     save_renders(args, is_metric, args.image_path, images, depths)
     save_tiled(model, args, args.image_path, images)
     save_true_depth(args, is_metric, args.image_path, depths)
+    save_guided(args, args.image_path, images, depths)
 
 
 if __name__ == "__main__":
