@@ -670,6 +670,28 @@ int mdpt_post_render(const void* xyz_f32, const void* uv_f32, const void* faces_
                      int32_t cull_back, double point_size, void* color_bgra, void* depth_f32, void* face_id_i32, void* scratch, size_t scratch_bytes,
                      void* stream);
 
+/* Hole filling of rendered views on the device (additive to ABI v6; not in the reference, whose viewer shows the holes): hierarchical (push-pull)
+ * filling with a preference for the far side, for the background pixels mdpt_post_render leaves behind depth edges and outside the photo's
+ * frustum. N images of one size in one call: color_bgra uint8 [N,H,W,4], depth_f32 [N,H,W] (for a rendered view the clip-space w, +inf on the
+ * background). A pixel is valid iff alpha != 0 and 0 < depth < inf. Level 0 is the image, level l + 1 has ceil(h_l / 2) x ceil(w_l / 2) nodes, up
+ * to the 1 x 1 level L; a node holds three colour channels and a depth as fp32, depth 0 = invalid.
+ *   selection (push and pull): of up to four contributors, dmax = the largest valid depth; contributor k is kept iff it is valid and
+ *                   (double)d_k >= (1.0 - band) * (double)dmax. band = 1: plain push-pull; band = 0: the farthest and its exact ties only.
+ *   push l -> l + 1: node (Y, X) from the children (2Y + dy, 2X + dx) that exist, in the order (0,0) (0,1) (1,0) (1,1): no valid child -> invalid,
+ *                   else every channel and the depth = the fp64 sum of the kept children in that order / their count, rounded once to fp32.
+ *   pull l + 1 -> l, top down: a valid node keeps its value; an invalid node (y, x) takes Ya = y >> 1, Yb = clamp(Ya + (y odd ? 1 : -1)), x alike,
+ *                   the parents (Ya,Xa) (Ya,Xb) (Yb,Xa) (Yb,Xb) with weights 9/16 3/16 3/16 1/16 (a clamped index may name a parent twice):
+ *                   sum w_k v_k / sum w_k over the kept parents in fp64 in that order, rounded once: to fp32 on levels >= 1; on level 0 the
+ *                   colour is floor(v + 0.5) clamped to 0 .. 255 with alpha 255 and the depth fp32. None valid: the node stays invalid.
+ * Outputs (buffers of their own): out_bgra [N,H,W,4]; out_depth_f32 [N,H,W] or NULL. A pixel that was valid is copied byte for byte and bit for bit;
+ * an image without a valid pixel comes out as background (0,0,0,0, depth +inf). No atomics; bit-deterministic; nothing is read back and nothing
+ * synchronises; the number of launches follows from H and W alone: with t = the first level of at most 32 x 32 nodes, ceil(t / 3) push launches,
+ * one launch for the levels t .. L, t pull launches (9 for 1920x1080). scratch = mdpt_post_fill_scratch_bytes (levels 1 .. L, 16 bytes per node),
+ * 16-byte aligned; what it held before does not matter. Limits: N <= 65535, sides <= 32768, 0 <= band <= 1. */
+int mdpt_post_fill_scratch_bytes(int32_t N, int32_t H, int32_t W, size_t* bytes);
+int mdpt_post_fill_holes(const void* color_bgra, const void* depth_f32, int32_t N, int32_t H, int32_t W, double band, void* out_bgra, void* out_depth_f32,
+                         void* scratch, size_t scratch_bytes, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

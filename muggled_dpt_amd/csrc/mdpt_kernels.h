@@ -246,6 +246,44 @@ struct RenderJob {
 };
 inline size_t render_scratch_bytes(size_t B, size_t V, size_t nv, size_t H, size_t W) { return B * V * (nv * sizeof(RenderVertex) + H * W * 8); }
 
+// hole filling of rendered views (postprocess.hip fill_* kernels): the push-pull pyramid of N images of H x W. Level 0 is the image, level l has
+// ceil(H / 2^l) x ceil(W / 2^l) nodes up to the 1 x 1 level L; a node = 16 bytes {three colour channels, depth} fp32, depth 0 = invalid. The scratch
+// holds levels 1 .. L of every image, image after image, level after level; top = the first level of at most FILL_TOP_SIDE nodes a side.
+#define FILL_TOP_SIDE 32    // levels of at most this many nodes a side are one workgroup's, in LDS
+#define FILL_PUSH_LEVELS 3  // a push workgroup owns an aligned 32 x 32 block of its base level and makes up to this many levels above it
+#define FILL_MAX_LEVELS 16  // sides of at most RENDER_MAX_SIDE = 2^15: L <= 15
+__host__ __device__ inline int fill_level_side(int side, int l) { return (int)(((long long)side + (1ll << l) - 1) >> l); }
+struct FillPlan {
+    int H, W, L, top;
+    size_t off[FILL_MAX_LEVELS + 1];  // off[l] = level l's first node within an image's scratch (l >= 1); off[L + 1] = the nodes of one image
+};
+inline FillPlan fill_plan(int H, int W) {
+    FillPlan p{};
+    p.H = H, p.W = W, p.top = -1;
+    size_t at = 0;
+    for (int l = 0;; ++l) {
+        const int h = fill_level_side(H, l), w = fill_level_side(W, l);
+        if (p.top < 0 && h <= FILL_TOP_SIDE && w <= FILL_TOP_SIDE) p.top = l;
+        p.off[l] = at;
+        if (l >= 1) at += (size_t)h * w;
+        if (h == 1 && w == 1) {
+            p.L = l;
+            break;
+        }
+    }
+    p.off[p.L + 1] = at;
+    return p;
+}
+inline size_t fill_scratch_bytes(size_t N, int H, int W) {
+    const FillPlan p = fill_plan(H, W);
+    return N * (p.off[p.L + 1] ? p.off[p.L + 1] : 1) * 16;  // (a 1 x 1 image has no level above it: one node, never touched)
+}
+struct FillJob {
+    const unsigned char* color; const float* depth; unsigned char* out; float* out_depth; void* scratch;
+    int N; double keep;  // keep = 1 - band
+    FillPlan plan;
+};
+
 // one tile of tiled high-resolution inference (postprocess.hip tile_* kernels; = mdpt_tile of include/mdpt.h): its h x w map (the table's dtype) and
 // its half-open pixel box in the photo. The table lives in DEVICE memory (any number of tiles); the kernels index it by tile.
 struct PostTile { const void* map; int h, w, x1, y1, x2, y2; };
@@ -339,6 +377,9 @@ int mdpt_launch_post_mesh(const MeshJob& m, float* xyz, float* uv, unsigned* fac
 // rendering of depth meshes (the 3D viewer's render_3d): RenderJob above -> color uint8 BGRA [B, V, H, W, 4] (background 0, 0, 0, 0) and, where not
 // null, depth fp32 [B, V, H, W] (clip-space w, background +inf) and ids int32 [B, V, H, W] (the face's index, background -1). Four launches.
 int mdpt_launch_post_render(const RenderJob& r, unsigned char* color, float* depth, int* ids, hipStream_t stream);
+// hole filling of rendered views (depth-banded push-pull): FillJob above. ceil(top / FILL_PUSH_LEVELS) push launches, one launch for the levels
+// top .. L, top pull launches: the count follows from H and W alone. No atomics, bit-deterministic, the scratch's contents before do not matter.
+int mdpt_launch_post_fill(const FillJob& j, hipStream_t stream);
 // tiled high-resolution inference: tiles = T PostTile records on the device (maps of dtype dt). Fit: every tile's map against the guide (gh x gw,
 // dtype gdt, covering the H x W photo) over the tile's box -> sums [T, 6] fp64 {n, Sx, Sy, Sxx, Sxy, Syy}, fit [T, 2] fp64 {scale, shift}; parts =
 // [T, max_chunks, 6] fp64 scratch. Two launches, bit-deterministic. Blend: the feathered weighted mean of the fitted tiles -> out fp32 [H, W]; fit ==

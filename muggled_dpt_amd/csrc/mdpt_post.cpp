@@ -657,4 +657,36 @@ int mdpt_post_render(const void* xyz_f32, const void* uv_f32, const void* faces_
     return 0;
 }
 
+// ---- hole filling of rendered views (depth-banded push-pull; not in the reference)
+static int check_fill_sizes(int32_t N, int32_t H, int32_t W) {
+    if (N <= 0 || N > 65535) return fail(MDPT_E_INVALID, "bad image count %d (1 .. 65535 per call)", N);
+    if (H <= 0 || W <= 0 || H > RENDER_MAX_SIDE || W > RENDER_MAX_SIDE) return fail(MDPT_E_INVALID, "bad image size %dx%d (sides of 1 .. %d)", H, W, RENDER_MAX_SIDE);
+    return 0;
+}
+
+int mdpt_post_fill_scratch_bytes(int32_t N, int32_t H, int32_t W, size_t* bytes) {
+    if (!bytes) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_fill_sizes(N, H, W));
+    *bytes = fill_scratch_bytes((size_t)N, H, W);
+    return 0;
+}
+
+int mdpt_post_fill_holes(const void* color_bgra, const void* depth_f32, int32_t N, int32_t H, int32_t W, double band, void* out_bgra, void* out_depth_f32,
+                         void* scratch, size_t scratch_bytes, void* stream) {
+    if (!color_bgra || !depth_f32 || !out_bgra || !scratch) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_fill_sizes(N, H, W));
+    if (!(band >= 0.0 && band <= 1.0)) return fail(MDPT_E_INVALID, "band must be in [0, 1], got %g", band);
+    if ((((uintptr_t)color_bgra | (uintptr_t)depth_f32 | (uintptr_t)out_bgra | (uintptr_t)out_depth_f32) & 3) != 0 || ((uintptr_t)scratch & 15) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the images and the depths need 4 bytes, the scratch 16)");
+    if (out_bgra == color_bgra || (out_depth_f32 && out_depth_f32 == depth_f32))
+        return fail(MDPT_E_INVALID, "the outputs must be buffers of their own, not the inputs");
+    const size_t need = fill_scratch_bytes((size_t)N, H, W);
+    if (scratch_bytes < need) return fail(MDPT_E_INVALID, "fill scratch of %zu bytes, %zu needed (mdpt_post_fill_scratch_bytes)", scratch_bytes, need);
+    FillJob j{};
+    j.color = (const unsigned char*)color_bgra, j.depth = (const float*)depth_f32, j.out = (unsigned char*)out_bgra, j.out_depth = (float*)out_depth_f32;
+    j.scratch = scratch, j.N = N, j.keep = 1.0 - band, j.plan = fill_plan(H, W);
+    CHK(mdpt_launch_post_fill(j, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

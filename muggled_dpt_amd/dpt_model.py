@@ -1074,13 +1074,14 @@ class DPTModel(nn.Module):
     def render_views(self, image_bgr: np.ndarray, view_proj=None, out_wh=(1280, 720), max_side_length: int | None = None,
                      use_square_sizing: bool = True, fov_deg: float | None = None, min_depth: float | None = None, max_depth: float | None = None,
                      edge_threshold: float | None = None, target_num_faces=None, mode: str = "triangles", cull: str = "back", point_size: float = 2.0,
-                     return_depth: bool = False, return_face_ids: bool = False, **camera):
+                     return_depth: bool = False, return_face_ids: bool = False, fill_holes=None, **camera):
         """One photo -> its depth mesh rendered from V viewpoints, what the reference's 3D viewer shows and saves frame by frame: inference, then
         postprocess.pack_depth_u24_frames (edge alpha), depth_frames_to_mesh and render_mesh with the photo as the texture, all on the device
         with nothing read back. view_proj: [V,16] matrices (orbit_camera.viewer_view_proj / swing_views / stereo_views), or None: one view of
         the viewer's start pose, **camera going to orbit_camera.viewer_view_proj (tilt_deg, view_offset, view_fov_deg, orthographic, camera).
         The mesh controls default to the viewer's as it starts (postprocess.MESH_*), point_size to its slider's 2. -> render_mesh's result with
-        B = 1: color uint8 [1,V,h,w,4] and, as asked, depth / face ids [1,V,h,w]."""
+        B = 1: color uint8 [1,V,h,w,4] and, as asked, depth / face ids [1,V,h,w]. fill_holes: None, or the band of postprocess.fill_holes
+        applied to every view (render_mesh's fill_holes): no background is left where the view has any coverage."""
         from . import orbit_camera, postprocess as pp
         fov_deg = pp.MESH_FOV_DEG if fov_deg is None else fov_deg
         min_depth = pp.MESH_MIN_DEPTH if min_depth is None else min_depth
@@ -1096,7 +1097,8 @@ class DPTModel(nn.Module):
             frames, (image_bgr.shape[1], image_bgr.shape[0]), fov_deg, min_depth, max_depth, is_metric,
             pp.MESH_EDGE_THRESHOLD if edge_threshold is None else edge_threshold, pp.MESH_TARGET_FACES if target_num_faces is None else target_num_faces,
             mode=mode)
-        return pp.render_mesh(xyz, uv, faces, counts, [image_bgr], view_proj, out_wh, cull, point_size, return_depth, return_face_ids)
+        return pp.render_mesh(xyz, uv, faces, counts, [image_bgr], view_proj, out_wh, cull, point_size, return_depth, return_face_ids,
+                              fill_holes=fill_holes)
 
     def prepare_image_bgr(self, image_bgr: np.ndarray, max_side_length: int | None = None, use_square_sizing: bool = True,
                           interpolation_mode: str = "bilinear", *, crop=None) -> Tensor:

@@ -243,6 +243,8 @@ SYMBOLS = {
     "mdpt_post_guided_upsample": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _D, _VP, _SZ, _VP, _VP]),
     "mdpt_post_render_scratch_bytes": (ctypes.c_int, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(_SZ)]),
     "mdpt_post_render": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _I, _I, _I, _I, _D, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "mdpt_post_fill_scratch_bytes": (ctypes.c_int, [_I, _I, _I, ctypes.POINTER(_SZ)]),
+    "mdpt_post_fill_holes": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _D, _VP, _VP, _VP, _SZ, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

@@ -10,7 +10,8 @@ through mesh_io), and - not in the reference, which only describes the fit - the
 (stitch_tiles; layouts in tiling.py, DPTModel.inference_tiled makes the whole call), and the alignment of predictions to measured depth maps with
 the standard metrics and true depth (fit_true_depth / depth_metrics / true_depth; DPTModel.evaluate_depth makes the whole call), and the 3D viewer's
 WebGL drawing of the mesh from any number of viewpoints (render_mesh; cameras in orbit_camera.py, DPTModel.render_views makes the whole call), and
-the enlargement of a map to its photo's size with the photo as the guide (guided_upsample_images; DPTModel.inference_guided makes the whole call).
+the enlargement of a map to its photo's size with the photo as the guide (guided_upsample_images; DPTModel.inference_guided makes the whole call), and - not in the reference - the filling of the holes a moved camera
+uncovers in rendered views (fill_holes; render_mesh and DPTModel.render_views take it as an option).
 
 Every function takes the CUDA tensor the model returned and launches HIP kernels (libmdpt: mdpt_post_*) on the current torch
 stream; results stay on the device (the reference's convert_to_uint8 does the same, postprocess.py:85-87). min / max never visit
@@ -1046,7 +1047,7 @@ def _render_args(xyz, uv, faces, counts, view_proj, out_wh, cull, point_size, ma
 
 
 def render_mesh(xyz: Tensor, uv: Tensor, faces: Tensor, counts: Tensor, textures_bgr, view_proj, out_wh, cull: str = "back", point_size: float = 1.0,
-                return_depth: bool = False, return_face_ids: bool = False, max_scratch_bytes: int = RENDER_MAX_SCRATCH_BYTES):
+                return_depth: bool = False, return_face_ids: bool = False, max_scratch_bytes: int = RENDER_MAX_SCRATCH_BYTES, fill_holes=None):
     """The slabs depth_frames_to_mesh returns (its bounds are not needed), read in place with their device-side counts, rendered from V viewpoints
     each: what the reference's 3D viewer draws with WebGL (3dviewer/index.html:1158-1228 render_3d, the mesh shaders of shaders.js) and saves frame
     by frame through canvas.toDataURL(). textures_bgr: one uint8 [h,w,3] BGR image per mesh, any sizes - host arrays (staged through pinned memory)
@@ -1061,8 +1062,16 @@ def render_mesh(xyz: Tensor, uv: Tensor, faces: Tensor, counts: Tensor, textures
     a uint64 z-buffer merged with integer atomic min, perspective-correct fp64 barycentrics, bilinear texture sample, one rounding. Deviations from
     GL: a face with a vertex at w <= 0 is dropped, not clipped against the near plane; mipmapped minification (LINEAR_MIPMAP_LINEAR,
     textures.js:200) and anti-aliasing are NOT reproduced (level 0, one sample per pixel). Four launches per chunk of views; the views are chunked
-    so that the scratch (8 bytes per output pixel and 24 per vertex, per mesh and view) stays within max_scratch_bytes where one view allows."""
+    so that the scratch (8 bytes per output pixel and 24 per vertex, per mesh and view) stays within max_scratch_bytes where one view allows.
+    fill_holes: None, or the band of fill_holes below, applied to every view after the render: the colour and, when asked for, the depth are the
+    filled ones (exactly what fill_holes makes of this call's result without it); face ids stay -1 on filled pixels."""
     what = "render_mesh"
+    if fill_holes is not None:
+        band = _fill_band(fill_holes, what, "fill_holes")
+        out = render_mesh(xyz, uv, faces, counts, textures_bgr, view_proj, out_wh, cull, point_size, True, return_face_ids, max_scratch_bytes)
+        filled = _fill_holes(out[0], out[1], band, return_depth, max_scratch_bytes)
+        out = ((filled[0], filled[1]) if return_depth else (filled,)) + tuple(out[2:])
+        return out[0] if len(out) == 1 else out
     b, nv, nf, points, n_views, views, w, h, point_size = _render_args(xyz, uv, faces, counts, view_proj, out_wh, cull, point_size, max_scratch_bytes, what)
     photos, on_device = _cutout_photos(textures_bgr, b, what)
     _need_cuda([xyz, uv, faces, counts], what)
@@ -1113,6 +1122,74 @@ def render_mesh(xyz: Tensor, uv: Tensor, faces: Tensor, counts: Tensor, textures
     del staged  # (the caching allocator reuses it in stream order only)
     out = (color,) + ((depth,) if return_depth else ()) + ((ids,) if return_face_ids else ())
     return out[0] if len(out) == 1 else out
+
+
+# ---- hole filling of rendered views: depth-banded push-pull (not in the reference, whose viewer shows the holes)
+
+FILL_BAND = 0.1  # a user-facing choice, not a measured optimum
+
+
+def _fill_band(band, what: str, name: str = "band") -> float:
+    if isinstance(band, bool) or not isinstance(band, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{what}: {name} must be a number in [0, 1], got {type(band)}")
+    band = float(band)
+    if not 0.0 <= band <= 1.0:
+        raise ValueError(f"{what}: {name} must be in [0, 1], got {band}")
+    return band
+
+
+def fill_holes(color: Tensor, depth: Tensor, band: float = FILL_BAND, return_depth: bool = False, max_scratch_bytes: int = RENDER_MAX_SCRATCH_BYTES):
+    """The holes of rendered views filled on the device: hierarchical (push-pull) hole filling with a preference for the far side, for what
+    render_mesh leaves as background - the ground behind every foreground object once the camera leaves the photo's viewpoint (the mesh's edge
+    threshold cuts those faces away on purpose) and everything outside the photo's frustum. Not in the reference, whose viewer shows the holes.
+    color: uint8 [...,h,w,4] BGRA, depth: fp32 [...,h,w] with the same leading dims (render_mesh's colour and depth: clip-space w, +inf on the
+    background), CUDA tensors on one device. A pixel is valid iff alpha != 0 and 0 < depth < inf; valid pixels come back byte for byte, the others
+    take the mean of the valid pixels around them through an image pyramid (include/mdpt.h, mdpt_post_fill_holes, has the definition), alpha 255.
+    Wherever up to four pyramid nodes are combined, only those whose depth is at least (1 - band) times the farthest one's are kept: a
+    disocclusion is background, so it is continued from the background side of the hole and not from the object that uncovered it. band = 1 is
+    plain push-pull, band = 0 keeps the farthest only; the default of 0.1 is a choice, not a measured optimum. With an orthographic camera w is
+    constant and the band does nothing. An image without a valid pixel stays background (0,0,0,0, depth +inf).
+    -> the filled colour [...,h,w,4] and, with return_depth, the filled depth [...,h,w] (a tuple). Nothing is read back, nothing synchronises; no
+    atomics, bit-deterministic; the number of launches follows from (h, w) alone (9 for 1920x1080). The images are chunked so that the scratch
+    (16 bytes per pyramid node above the image: about 16 / 3 bytes per pixel) stays within max_scratch_bytes where one image allows."""
+    what = "fill_holes"
+    for t, name in ((color, "color"), (depth, "depth")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {name} must be a tensor, got {type(t)}")
+    if color.dtype != torch.uint8 or color.dim() < 3 or color.shape[-1] != 4 or 0 in color.shape:
+        raise ValueError(f"{what}: color must be uint8 [...,h,w,4] BGRA, got {color.dtype} {tuple(color.shape)}")
+    if depth.dtype != torch.float32 or tuple(depth.shape) != tuple(color.shape[:-1]):
+        raise ValueError(f"{what}: depth must be float32 {list(color.shape[:-1])}, got {depth.dtype} {tuple(depth.shape)}")
+    band = _fill_band(band, what)
+    h, w = int(color.shape[-3]), int(color.shape[-2])
+    if not (0 < w <= 32768 and 0 < h <= 32768):
+        raise ValueError(f"{what}: images must have sides of 1 .. 32768, got {h}x{w}")
+    if int(max_scratch_bytes) <= 0:
+        raise ValueError(f"{what}: max_scratch_bytes must be positive, got {max_scratch_bytes}")
+    _need_cuda([color, depth], what)
+    dev = color.device
+    if depth.device != dev:
+        raise RuntimeError(f"{what}: the tensors are on different devices")
+    lead = tuple(color.shape[:-3])
+    src_c, src_d = color.detach().reshape(-1, h, w, 4).contiguous(), depth.detach().reshape(-1, h, w).contiguous()
+    n = int(src_c.shape[0])
+    import ctypes
+    lib = native.load()
+    per_image = ctypes.c_size_t()
+    native.check(lib, lib.mdpt_post_fill_scratch_bytes(1, h, w, ctypes.byref(per_image)))
+    chunk = max(1, min(n, int(max_scratch_bytes) // per_image.value, 65535))
+    out_c = torch.empty_like(src_c)
+    out_d = torch.empty_like(src_d) if return_depth else None
+    scratch = torch.empty(chunk * per_image.value // 16, 4, device=dev, dtype=torch.float32)
+    for n0 in range(0, n, chunk):
+        k = min(chunk, n - n0)
+        _launch(dev, "mdpt_post_fill_holes", src_c[n0:].data_ptr(), src_d[n0:].data_ptr(), k, h, w, band, out_c[n0:].data_ptr(),
+                None if out_d is None else out_d[n0:].data_ptr(), scratch.data_ptr(), k * per_image.value)
+    out_c = out_c.reshape(*lead, h, w, 4)
+    return (out_c, out_d.reshape(*lead, h, w)) if return_depth else out_c
+
+
+_fill_holes = fill_holes  # (render_mesh's argument of that name hides the function there)
 
 
 # ---- tiled high-resolution inference: the maps of overlapping tiles of one photo put together into one map at the photo's resolution

@@ -85,6 +85,8 @@ def main():
     ap.add_argument("--render_wh", type=int, nargs=2, default=(1280, 720), metavar=("W", "H"), help="render: output size")
     ap.add_argument("--render_stereo", type=float, default=None, metavar="BASELINE", help="render: a left / right pair BASELINE world units apart "
                     "instead of the swing (views 000 and 001)")
+    ap.add_argument("--render_fill", type=float, nargs="?", const=0.1, default=None, metavar="BAND", help="render: fill the holes of every view "
+                    "(depth-banded push-pull, BAND in 0..1, default 0.1): the PNGs then have alpha 255 everywhere")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mdpt_run_image needs an MI355X: no GPU visible (there is no CPU fallback)")
@@ -208,7 +210,7 @@ def save_renders(args, is_metric, paths, images, depths):
                                                            is_metric=is_metric,
                                                            target_num_faces=pp.MESH_TARGET_FACES if args.mesh_faces is None else args.mesh_faces,
                                                            mode="points" if args.mesh_points else "triangles")
-        color = pp.render_mesh(xyz, uv, faces, counts, [img], views, (w, h), point_size=2.0)[0]
+        color = pp.render_mesh(xyz, uv, faces, counts, [img], views, (w, h), point_size=2.0, fill_holes=args.render_fill)[0]
         rgba = color[..., [2, 1, 0, 3]].cpu().numpy()
         stem = os.path.join(args.render, os.path.splitext(os.path.basename(path))[0])
         for k in range(rgba.shape[0]):
