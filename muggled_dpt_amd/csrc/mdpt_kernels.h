@@ -189,7 +189,7 @@ struct BgrRunTable { BgrRun run[MDPT_BGR_RUNS]; int n; };
 // HIP passes at most 4 KB of kernel arguments: the table plus the other arguments of prepare_patchify_kernel (two pointers, five ints, six floats)
 static_assert(sizeof(BgrRunTable) <= 3072, "BgrRunTable must leave room for the other kernel arguments below HIP's 4 KB limit");
 
-// image table of the per-image display tail (postprocess.hip seg_* and colorize kernels), by value like BgrRunTable: run r holds `count`
+// image table of the per-image display tail (post_display.inc seg_* and colorize kernels), by value like BgrRunTable: run r holds `count`
 // packed images of ih x iw elements from `in` (image j at in + j ih iw) whose outputs are oh x ow (the resize target; = ih x iw for the
 // kernels that do not resize) and start at element `off` of the packed output (image j at off + j oh ow). The images of a launch are the
 // runs' images in order (blockIdx.y = image); a uniform batch is one run.
@@ -210,14 +210,14 @@ inline PostRunTable uniform_table(const void* in, int B, int ih, int iw, int oh,
 // [B, MDPT_POST_SEG_PARTS, 2] fp64 {min, max} partials of the plane-removed map (null for the kernel that computes them)
 struct PlaneMap { const void* in; int dt, B, h, w; const unsigned* parts; const double* coef; double factor; const double* vparts; };
 
-// photo table of the depth-masking cutout (postprocess.hip mask_cutout_kernel), by value: photo k is img (ih x iw x 3 BGR bytes), cut out by its
+// photo table of the depth-masking cutout (post_still.inc mask_cutout_kernel), by value: photo k is img (ih x iw x 3 BGR bytes), cut out by its
 // prepared map (h x w, dtype dt of the table) with that map's min/max partials, plane coef and plane-removed min/max partials; its outputs start at
 // pixel `off` of the packed BGRA / mask outputs (blockIdx.y = photo)
 #define MDPT_MASK_IMAGES 32
 struct MaskImage { const void* map; const unsigned* parts; const double* coef; const double* vparts; const unsigned char* img; size_t off; int h, w, ih, iw; };
 struct MaskTable { MaskImage im[MDPT_MASK_IMAGES]; int n, dt; };
 
-// one depth-to-mesh call (postprocess.hip mesh_* kernels), by value: B frames [H, W, 4] of 24-bit depth + alpha bytes, a plane grid of nx x ny
+// one depth-to-mesh call (post_mesh.inc mesh_* kernels), by value: B frames [H, W, 4] of 24-bit depth + alpha bytes, a plane grid of nx x ny
 // vertices (vertex i = c + r nx at (c x_step - 1, 1 - r y_step), or at vertex_xy[i] when the fp64 [nx ny, 2] table is given), the camera of the
 // viewer's vertex shader (depth = a + b d, or 1 / (a + b d) for relative models; alpha_min = edge_threshold * 255) and the scratch planes of the
 // multi-launch compaction: vmap [B, nx ny] (-1 = dropped vertex, else its new index), vcnt / fcnt = per-block kept counts -> exclusive offsets,
@@ -230,7 +230,7 @@ struct MeshJob {
 };
 inline size_t mesh_blocks(size_t n) { return (n + 255) / 256; }  // the compaction's blocks: 256 vertices (or grid cells) each
 
-// one render call (postprocess.hip render_* kernels), by value: the slabs of mdpt_launch_post_mesh read in place (xyz [B, nv, 3], uv [B, nv, 2], faces
+// one render call (post_render.inc render_* kernels), by value: the slabs of mdpt_launch_post_mesh read in place (xyz [B, nv, 3], uv [B, nv, 2], faces
 // [B, nf, 3] or, for points, [B, nf = nv, 1], counts [B, 2] on the device), one texture per mesh (tex: B RenderTex records in DEVICE memory, =
 // mdpt_texture of include/mdpt.h), view_proj fp64 [B, V, 16] (clip = [x, y, z, 1] M), the H x W viewport, half = the points' half-size in 1/256
 // pixel, and the scratch: verts [B V, nv] transformed vertices, zbuf [B V, H W] keys
@@ -246,7 +246,7 @@ struct RenderJob {
 };
 inline size_t render_scratch_bytes(size_t B, size_t V, size_t nv, size_t H, size_t W) { return B * V * (nv * sizeof(RenderVertex) + H * W * 8); }
 
-// hole filling of rendered views (postprocess.hip fill_* kernels): the push-pull pyramid of N images of H x W. Level 0 is the image, level l has
+// hole filling of rendered views (post_fill.inc fill_* kernels): the push-pull pyramid of N images of H x W. Level 0 is the image, level l has
 // ceil(H / 2^l) x ceil(W / 2^l) nodes up to the 1 x 1 level L; a node = 16 bytes {three colour channels, depth} fp32, depth 0 = invalid. The scratch
 // holds levels 1 .. L of every image, image after image, level after level; top = the first level of at most FILL_TOP_SIDE nodes a side.
 #define FILL_TOP_SIDE 32    // levels of at most this many nodes a side are one workgroup's, in LDS
@@ -284,7 +284,7 @@ struct FillJob {
     FillPlan plan;
 };
 
-// one tile of tiled high-resolution inference (postprocess.hip tile_* kernels; = mdpt_tile of include/mdpt.h): its h x w map (the table's dtype) and
+// one tile of tiled high-resolution inference (post_tiles.inc tile_* kernels; = mdpt_tile of include/mdpt.h): its h x w map (the table's dtype) and
 // its half-open pixel box in the photo. The table lives in DEVICE memory (any number of tiles); the kernels index it by tile.
 struct PostTile { const void* map; int h, w, x1, y1, x2, y2; };
 // samples of one tile map that one workgroup of the fit reduces (256 threads x 8): the partial sums of tile t's chunk c are the 6 doubles at
@@ -292,7 +292,7 @@ struct PostTile { const void* map; int h, w, x1, y1, x2, y2; };
 #define MDPT_TILE_FIT_CHUNK 2048
 __host__ __device__ inline size_t tile_fit_chunks(size_t map_elems) { return (map_elems + MDPT_TILE_FIT_CHUNK - 1) / MDPT_TILE_FIT_CHUNK; }
 
-// one prediction / ground-truth pair of the true-depth block (postprocess.hip align_* kernels; = mdpt_depth_pair of include/mdpt.h): the ph x pw
+// one prediction / ground-truth pair of the true-depth block (post_align.inc align_* kernels; = mdpt_depth_pair of include/mdpt.h): the ph x pw
 // prediction (the table's dtype), the H x W fp32 truth and its uint8 validity map (null: every pixel). Device table, indexed by pair; apply reads
 // pred, ph, pw and H x W (its output size) only.
 struct AlignPair { const void* pred; int ph, pw; const float* truth; const unsigned char* valid; int H, W; };
@@ -312,7 +312,7 @@ inline size_t align_scratch_bytes(size_t P, size_t max_chunks) {
     return align_parts_doubles(P, max_chunks) * sizeof(double) + P * (ALIGN_HIST_WORDS + ALIGN_STATE_WORDS) * sizeof(unsigned);
 }
 
-// one map / photo pair of the photo-guided upsampling (postprocess.hip guided_* kernels; = mdpt_guided_pair of include/mdpt.h): the h x w map (the
+// one map / photo pair of the photo-guided upsampling (post_guided.inc guided_* kernels; = mdpt_guided_pair of include/mdpt.h): the h x w map (the
 // table's dtype), the uint8 BGR photo of H x W pixels whose rows lie `pitch` bytes apart (any alignment), the fp32 H x W output, and where the pair's
 // scratch starts (bytes from the call's scratch pointer, a multiple of 8). Device table, indexed by pair.
 struct GuidedPair { const void* map; int h, w; const unsigned char* photo; long long pitch; int H, W; float* out; long long scratch_off; };
@@ -331,7 +331,7 @@ struct SwinCpbBatch {
 };
 
 // ------------------------------------------------------------------------------------------------
-// depth post-processing (postprocess.hip); scratch2 = 2 uints of device scratch for the min/max reduction
+// depth post-processing (postprocess.hip: the post_*.inc files, each launcher below its kernels); scratch2 = 2 uints of device scratch for the min/max reduction
 // ------------------------------------------------------------------------------------------------
 int mdpt_launch_post_minmax(const float* in, size_t n, float* minmax_out, unsigned* scratch2, hipStream_t stream);
 int mdpt_launch_post_scale(const float* in, float* out, int B, int ih, int iw, int oh, int ow, float* minmax_out,

@@ -22,9 +22,9 @@ LIB_PATH = os.path.join(CSRC, "libmdpt.so")
 OPERAND_SOURCES = ("gemm.hip", "conv3h.hip", "attention.hip", "elementwise.hip", "swin.hip", "head.hip")
 PLAIN_SOURCES = ("postprocess.hip", "stream_probe.hip", "mdpt_api.cpp", "mdpt_post.cpp", "mdpt_inventory.cpp", "mdpt_stages.cpp", "mdpt_debug.cpp", "mdpt_prof.cpp")
 SOURCES = OPERAND_SOURCES + PLAIN_SOURCES
-HEADERS = ("gemm_common.inc", "gemm_epilogue_strip.inc", "gemm_lockstep.inc", "gemm8_epilogues.inc", "gemm8.inc", "mdpt_kernels.h", "mdpt_launchers.inc", "op_types.h", "mdpt_prof.h", "mdpt_internal.h", "mdpt_swin_plan.inc", "mdpt_swin_stages.inc", "ln_row.h",
-           "up_bf16.h",
-           os.path.join(REPO, "include", "mdpt.h"))
+# everything a source may #include: every header and .inc of csrc/ (read from the directory, so that a new one cannot be forgotten; sorted:
+# source_hash() covers the names) and the public header. _stale() and source_hash() go over SOURCES + HEADERS
+HEADERS = tuple(sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))) + (os.path.join(REPO, "include", "mdpt.h"),)
 # (source, extra flags, object stem)
 UNITS = tuple((s, (), os.path.splitext(s)[0]) for s in SOURCES) + tuple((s, ("-DMDPT_OP_F16",), os.path.splitext(s)[0] + "_f16")
                                                                         for s in OPERAND_SOURCES)
@@ -83,6 +83,15 @@ def source_hash() -> str:
     return h.hexdigest()[:16]
 
 
+def _build_jobs() -> int:
+    """Compilers to run at once: MAX_JOBS when set (a shared machine grants fewer CPUs than os.cpu_count() shows), else one per unit up to the CPUs."""
+    try:
+        jobs = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:
+        jobs = min(len(UNITS), os.cpu_count() or 8)
+    return max(1, jobs)
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP sources for gfx950 into csrc/libmdpt.so (cross-compiles without a GPU)."""
     if not force and not _stale():
@@ -114,7 +123,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
     tmp = LIB_PATH + tag + ".tmp"
     try:
-        with ThreadPoolExecutor(max_workers=min(len(UNITS), max(2, (os.cpu_count() or 8)))) as ex:
+        with ThreadPoolExecutor(max_workers=_build_jobs()) as ex:
             objs = list(ex.map(compile_one, UNITS))
         r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", tmp, "-ldl"], capture_output=True, text=True)
         if r.returncode != 0:
