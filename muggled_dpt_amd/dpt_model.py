@@ -1053,10 +1053,11 @@ class DPTModel(nn.Module):
         .readme_assets/results_explainer.md describes the fit). truths / valid / method / truth_range are fit_true_depth's: one map per image at
         its own resolution, where zero, NaN or an unset `valid` pixel means no measurement. A metric model (config is_metric) is fitted and scored in
         depth space, every other model in inverse-depth space."""
-        from .postprocess import _align_pairs, depth_metrics, fit_true_depth, true_depth
+        from .postprocess import depth_metrics, fit_true_depth, true_depth
+        from .postprocess.align import align_pairs
         space = "depth" if self.config.get("is_metric", False) else "inverse"
         preds = self.inference_images(images_bgr, max_side_length, use_square_sizing, batch_size)
-        staged = _align_pairs(preds, truths, valid, "evaluate_depth")  # host truths are staged, and the pair table uploaded, once for both calls
+        staged = align_pairs(preds, truths, valid, "evaluate_depth")  # host truths are staged, and the pair table uploaded, once for both calls
         fit = fit_true_depth(preds, truths, valid, space, method, truth_range, staged=staged)
         metrics = depth_metrics(preds, truths, fit, valid, space, truth_range, staged=staged)
         return fit, metrics, true_depth(preds, fit, staged[3], space)
