@@ -8,6 +8,7 @@ int MDPT_FN(mdpt_launch_attention)(const AttnParams& p, hipStream_t stream);
 // diagnostic: explicit softmax(q k^T + bias [+ shift mask]) as fp32 [B, heads, N, N] from the same Q / K planes (head dim 64 families;
 // SwinV2 windows: B = images * windows, head dim 32)
 int MDPT_FN(mdpt_launch_attn_weights)(const AttnParams& p, float* out_bhnn, hipStream_t stream);
+// ---- ew_norm.inc
 // LayerNorm over the last dim (eps 1e-6): fp32 rows -> bf16 hi (+lo) (+ optional fp32 copy)
 // out_f8 / out_a8 (here and below): the lo plane in the fp8 form an F8 consumer reads (GemmParams::out_f8, f8_cross.h)
 int MDPT_FN(mdpt_launch_layernorm)(const float* x, const float* gamma, const float* beta, op_t* out_hi, op_t* out_lo,
@@ -18,6 +19,18 @@ int MDPT_FN(mdpt_launch_layernorm_addp)(float* x, const float* part, size_t part
 // finishing kernel of a K split whose ranges all stored partial planes (GemmParams::ks_all): sum in the order z = 0, 1, ... (+ bias) -> fp32 rows / planes
 int MDPT_FN(mdpt_launch_ksplit_finish)(const float* part, size_t part_stride, int nparts, const float* bias, float* out_f32, op_t* out_hi, op_t* out_lo,
                                       int relu_planes, int M, int N, int ldc, hipStream_t stream, size_t out_f8 = 0, int out_a8 = 0);
+// per-token L2 norm of fp32 rows [B, npad, F]: rows skip .. skip + ntok - 1 of every image -> norm_out [B, ntok] and / or channel `chan` of
+// the same rows -> chan_out [B, ntok] (either may be null); one wave per row, no atomics, batch-invariant summation order
+int MDPT_FN(mdpt_launch_row_norm)(const float* in, float* norm_out, float* chan_out, int chan, int B, int ntok, int npad, int skip, int F,
+                                  hipStream_t stream);
+// ViT-G SwiGLU gate: fp32 [rows, 2h] -> silu(first half) * second half as bf16 hi (+lo) [rows, hp] (pad columns zero)
+int MDPT_FN(mdpt_launch_swiglu)(const float* in, op_t* out_hi, op_t* out_lo, size_t rows, int h, int hp, hipStream_t stream);
+// token-mean compensation of the weight rounding (fp16 modes): per-image column means of an operand plane over every step-th real row,
+// written as the [B, K] A operand of the small GEMM against the weight residue (lo) plane
+int MDPT_FN(mdpt_launch_colmean)(const op_t* A, int lda, int B, int rows_per_img, int nreal, int step, int K, op_t* mean, hipStream_t stream);
+// ... and that product itself: out[b][n] = bias[n] + sum_k mean[b][k] * w_lo[n][k] (fp32 table, row stride N; K % 32 == 0)
+int MDPT_FN(mdpt_launch_wrc_table)(const op_t* mean, const op_t* w_lo, const float* bias, float* out, int B, int N, int K, hipStream_t stream, const float* wscale = nullptr);
+// ---- ew_tokens.inc
 // NCHW image (fp32 / bf16 / fp16: img_dtype) -> im2col rows [B*Np, Kp] bf16 hi (+lo), k = c*P*P + ky*P + kx, zero padded to Kp
 // poison != null: word b is set when image b holds a NaN / inf (mdpt_forward's non-finite propagation)
 int MDPT_FN(mdpt_launch_patchify)(const void* img, int img_dtype, op_t* out_hi, op_t* out_lo, int B, int H, int W, int P, int Kp,
@@ -31,11 +44,27 @@ int MDPT_FN(mdpt_launch_init_tokens)(float* resid, const float* cls_token, const
                             hipStream_t stream);
 // zero the pad columns [N, npadv) of the transposed-V planes
 int MDPT_FN(mdpt_launch_zero_vt_pad)(op_t* vt_hi, op_t* vt_lo, int rows, int N, int npadv, hipStream_t stream);
+int MDPT_FN(mdpt_launch_tokens_import)(const float* in, op_t* out_hi, op_t* out_lo, int B, int N, int npad, int F,
+                              hipStream_t stream, size_t out_f8 = 0, int out_a8 = 0);
+int MDPT_FN(mdpt_launch_tokens_export)(const op_t* in_hi, const op_t* in_lo, const float* in_f32, float* out, int B, int N,
+                              int npad, int F, int skip_cls, hipStream_t stream, size_t lo_f8 = 0);  // lo_f8: in_lo is an e5m2 residue plane (Planes::f8)
+// stage-level encoder entry: resid[b, 1+t, :] = tokens[b, t, :] + pos[t, :]
+int MDPT_FN(mdpt_launch_tokens_to_resid)(const float* tokens, const float* pos, float* resid, int B, int Np, int npad, int F,
+                                hipStream_t stream);
+// BEiT relative position bias (reference v31_beit/components/relative_positional_encoder.py:117-309): bilinear-resize the
+// learned [(2Gh-1)(2Gw-1)+3, heads] table to the current grid and lay it out per head as an extended LUT so that the bias of
+// (query q, key k) is ext[tq[q] - tk[k]] including the three cls cases; also fills the per-token index terms tq / tk.
+int MDPT_FN(mdpt_launch_beit_relpos)(const float* ref_lut, float* ext_lut, int* tq, int* tk, int heads, int Gh, int Gw, int gh, int gw,
+                            int N, int ntok_pad, hipStream_t stream);
+int MDPT_FN(mdpt_beit_relpos_elen)(int gh, int gw);
+int MDPT_FN(mdpt_launch_beit_relpos_batch)(const BeitRelposBatch& b, hipStream_t stream);
+// ---- ew_resize.inc
 // bilinear align_corners=True resize of fp32 NHWC [B,Hi,Wi,C] -> [B,Ho,Wo,C] as bf16 hi (+lo) and/or fp32
 int MDPT_FN(mdpt_launch_upsample)(const float* in, op_t* out_hi, op_t* out_lo, float* out_f32, int B, int Hi, int Wi, int Ho,
                          int Wo, int C, hipStream_t stream, size_t out_f8 = 0, int out_a8 = 0);
 // the same resize of a bf16 NHWC map to a bf16 NHWC map (C % 8 == 0), arithmetic of up_bf16.h
 int MDPT_FN(mdpt_launch_upsample_bf16)(const op_t* in, op_t* out, int B, int Hi, int Wi, int Ho, int Wo, int C, hipStream_t stream);
+// ---- ew_pack.inc
 // row_scale != null (MDPT_PACK_LINEAR only): row n is multiplied by row_scale[n] in fp32 BEFORE the bf16 split (a per-output-feature
 // layer scale folded into the weights: diag(gamma) W)
 int MDPT_FN(mdpt_launch_pack_weight)(const void* src, int src_dtype, op_t* dst_hi, op_t* dst_lo, int kind, int N, int K, int Np, int Kp,
@@ -53,22 +82,14 @@ int MDPT_FN(mdpt_launch_weight_scale)(const void* src, int src_dtype, int N, int
 // fp32 vector copy with zero padding (biases); `rep` repeats are not needed: plain copy
 int MDPT_FN(mdpt_launch_pad_copy_f32)(const void* src, int src_dtype, float* dst, int n, int np, hipStream_t stream, const void* scale = nullptr,
                              int scale_dtype = 0, float mul = 1.0f);  // dst = float(src) (* float(scale)) (* mul)
-// layout conversions for the stage-level API / debug taps
+int MDPT_FN(mdpt_launch_memset_f32)(float* dst, float value, size_t n, hipStream_t stream);
+int MDPT_FN(mdpt_launch_add_f32)(float* dst, const float* src, size_t n, hipStream_t stream);  // dst += src
+// ---- ew_layout.inc: layout conversions for the stage-level API / debug taps
 int MDPT_FN(mdpt_launch_nhwc_to_nchw)(const float* in_f32, const op_t* in_hi, const op_t* in_lo, float* out, int B, int H, int W,
                              int C, int Cp, hipStream_t stream);
-int MDPT_FN(mdpt_launch_tokens_export)(const op_t* in_hi, const op_t* in_lo, const float* in_f32, float* out, int B, int N,
-                              int npad, int F, int skip_cls, hipStream_t stream, size_t lo_f8 = 0);  // lo_f8: in_lo is an e5m2 residue plane (Planes::f8)
-// per-token L2 norm of fp32 rows [B, npad, F]: rows skip .. skip + ntok - 1 of every image -> norm_out [B, ntok] and / or channel `chan` of
-// the same rows -> chan_out [B, ntok] (either may be null); one wave per row, no atomics, batch-invariant summation order
-int MDPT_FN(mdpt_launch_row_norm)(const float* in, float* norm_out, float* chan_out, int chan, int B, int ntok, int npad, int skip, int F,
-                                  hipStream_t stream);
-int MDPT_FN(mdpt_launch_tokens_import)(const float* in, op_t* out_hi, op_t* out_lo, int B, int N, int npad, int F,
-                              hipStream_t stream, size_t out_f8 = 0, int out_a8 = 0);
 int MDPT_FN(mdpt_launch_nchw_to_nhwc)(const float* in, float* out_f32, op_t* out_hi, op_t* out_lo, int relu_bf16, int B, int H,
                              int W, int C, int Cp, hipStream_t stream, size_t out_f8 = 0, int out_a8 = 0);
-// stage-level encoder entry: resid[b, 1+t, :] = tokens[b, t, :] + pos[t, :]
-int MDPT_FN(mdpt_launch_tokens_to_resid)(const float* tokens, const float* pos, float* resid, int B, int Np, int npad, int F,
-                                hipStream_t stream);
+// ---- ew_prepare.inc
 // uint8 HWC BGR -> normalised fp32 [3,oh,ow] RGB through PyTorch-compatible antialiased bilinear resize; bgr = the first pixel of an ih x iw box of an
 // image whose rows are `pitch` bytes apart (3 iw: a packed image)
 int MDPT_FN(mdpt_launch_prepare_image)(const unsigned char* bgr, size_t pitch, void* out, int out_dtype, int ih, int iw, int oh, int ow, const float mean[3],
@@ -76,20 +97,11 @@ int MDPT_FN(mdpt_launch_prepare_image)(const unsigned char* bgr, size_t pitch, v
 // ... fused with patchify for the frames of a BgrRunTable (at most 65535), written from im2col row 0 of out_hi / out_lo
 int MDPT_FN(mdpt_launch_prepare_patchify)(const BgrRunTable& t, int img_dtype, op_t* out_hi, op_t* out_lo, int H, int W, int P, int Kp,
                                          const float mean[3], const float inv_std[3], int interp, hipStream_t stream);  // interp: 0 bilinear, 1 bicubic (both antialiased)
-// BEiT relative position bias (reference v31_beit/components/relative_positional_encoder.py:117-309): bilinear-resize the
-// learned [(2Gh-1)(2Gw-1)+3, heads] table to the current grid and lay it out per head as an extended LUT so that the bias of
-// (query q, key k) is ext[tq[q] - tk[k]] including the three cls cases; also fills the per-token index terms tq / tk.
-int MDPT_FN(mdpt_launch_beit_relpos)(const float* ref_lut, float* ext_lut, int* tq, int* tk, int heads, int Gh, int Gw, int gh, int gw,
-                            int N, int ntok_pad, hipStream_t stream);
-int MDPT_FN(mdpt_beit_relpos_elen)(int gh, int gw);
-int MDPT_FN(mdpt_launch_beit_relpos_batch)(const BeitRelposBatch& b, hipStream_t stream);
-int MDPT_FN(mdpt_launch_memset_f32)(float* dst, float value, size_t n, hipStream_t stream);
-int MDPT_FN(mdpt_launch_add_f32)(float* dst, const float* src, size_t n, hipStream_t stream);  // dst += src
-// ViT-G SwiGLU gate: fp32 [rows, 2h] -> silu(first half) * second half as bf16 hi (+lo) [rows, hp] (pad columns zero)
-int MDPT_FN(mdpt_launch_swiglu)(const float* in, op_t* out_hi, op_t* out_lo, size_t rows, int h, int hp, hipStream_t stream);
+// ---- head.hip
 bool MDPT_FN(mdpt_head_tail_supported)(int cin);
 bool MDPT_FN(mdpt_head_tail_scale_ok)(int Hi, int Wi, int Ho, int Wo);
 int MDPT_FN(mdpt_launch_head_tail)(const HeadTailParams& p, int cin, hipStream_t stream);
+// ---- swin.hip
 // out = LN_eps(x [+ part]) (+ add): fp32 rows -> fp32 (may alias add) and/or bf16 hi (+lo); part = partial sums of a K-split GEMM's second range
 int MDPT_FN(mdpt_launch_ln_res)(const float* x, const float* add, const float* gamma, const float* beta, float eps, float* out_f32,
                        op_t* out_hi, op_t* out_lo, int rows, int F, hipStream_t stream, int ld_planes = 0, const float* part = nullptr);
@@ -110,8 +122,3 @@ int MDPT_FN(mdpt_launch_swin_qkv_prep)(const float* qkv, const int* rowmap, cons
 int MDPT_FN(mdpt_launch_swin_merge_gather)(const float* tok, op_t* out_hi, op_t* out_lo, int B, int gh, int gw, int C,
                                   hipStream_t stream);
 int MDPT_FN(mdpt_launch_f32_to_planes)(const float* in, op_t* out_hi, op_t* out_lo, size_t rows, int F, int ld, hipStream_t stream);
-// token-mean compensation of the weight rounding (fp16 modes): per-image column means of an operand plane over every step-th real row,
-// written as the [B, K] A operand of the small GEMM against the weight residue (lo) plane
-int MDPT_FN(mdpt_launch_colmean)(const op_t* A, int lda, int B, int rows_per_img, int nreal, int step, int K, op_t* mean, hipStream_t stream);
-// ... and that product itself: out[b][n] = bias[n] + sum_k mean[b][k] * w_lo[n][k] (fp32 table, row stride N; K % 32 == 0)
-int MDPT_FN(mdpt_launch_wrc_table)(const op_t* mean, const op_t* w_lo, const float* bias, float* out, int B, int N, int K, hipStream_t stream, const float* wscale = nullptr);

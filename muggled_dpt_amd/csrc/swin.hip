@@ -10,37 +10,12 @@
 //   * patch merge gather (TL, BL, TR, BR concat)  (components/patch_merge.py:49-103)
 // All are coalesced streaming kernels; the matmuls around them run in gemm.hip / attention.hip.
 
-#include "mdpt_kernels.h"
 #include <algorithm>
-#include "mdpt_prof.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "ew_common.inc"  // split_store4, wave_sum, grid_for, ew_launch, ln_dispatch
 
 namespace {
 
-__device__ __forceinline__ void split_store4(op_t* hi, op_t* lo, size_t off, f32x4 v) {
-    opx4 h;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) h[e] = to_op(v[e]);
-    *(opx4*)(hi + off) = h;
-    if (lo) {
-        opx4 l;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) l[e] = to_op(v[e] - (float)h[e]);
-        *(opx4*)(lo + off) = l;
-    }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-inline int grid_for(size_t total, int block = 256) {
-    size_t g = (total + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g));
-}
+constexpr int SWIN_GRID_CAP = 65535;  // of the grid-stride launches of this file
 
 // ---------------------------------------------------------------------------------------------------
 // y = LN(x) (+ add); one wave per row held in registers. out_f32 may alias `add` (in-place residual update).
@@ -306,61 +281,48 @@ __global__ __launch_bounds__(256) void f32_to_planes_kernel(const float* __restr
 
 }  // namespace
 
-#define LAUNCH_RET() return (int)hipGetLastError()
-
 int MDPT_FN(mdpt_launch_ln_res)(const float* x, const float* add, const float* gamma, const float* beta, float eps, float* out_f32, op_t* out_hi,
                        op_t* out_lo, int rows, int F, hipStream_t stream, int ld_planes, const float* part) {
     if (ld_planes <= 0) ld_planes = F;
     if ((F & 3) || F > 2048 || ld_planes < F || (ld_planes & 3)) return (int)hipErrorInvalidValue;
     if (rows <= 0) return 0;
-    MdptProfScope prof("ln_res_kernel", 0.0, stream);
-    const dim3 grid((rows + 3) / 4), block(256);
-#define LN_CASE(NV) hipLaunchKernelGGL(ln_res_kernel<NV>, grid, block, 0, stream, x, add, gamma, beta, eps, out_f32, out_hi, out_lo, rows, F, ld_planes, part)
-    if (F <= 256) LN_CASE(1);
-    else if (F <= 512) LN_CASE(2);
-    else if (F <= 1024) LN_CASE(4);
-    else if (F <= 1536) LN_CASE(6);
-    else LN_CASE(8);
-#undef LN_CASE
-    LAUNCH_RET();
+    return ln_dispatch(F, [&](auto nv) {
+        return ew_launch("ln_res_kernel", 0.0, ln_res_kernel<decltype(nv)::value>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, add, gamma, beta, eps, out_f32, out_hi,
+                         out_lo, rows, F, ld_planes, part);
+    });
 }
 
 int MDPT_FN(mdpt_launch_swin_window_map)(int* rowmap, int* region, int* tq, int* tk, int gh, int gw, int wh, int ww, int sh, int sw, int region_ld,
                                 int ntok_pad, hipStream_t stream, int* tokmap, int tok_stride, int* vtokmap, int vtok_stride) {
     if (wh <= 0 || ww <= 0 || gh % wh || gw % ww || region_ld < wh * ww) return (int)hipErrorInvalidValue;
     const size_t work = (size_t)gh * gw > (size_t)ntok_pad ? (size_t)gh * gw : (size_t)ntok_pad;
-    hipLaunchKernelGGL(swin_window_map_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, stream, rowmap, region, tq, tk, gh, gw, wh,
-                       ww, sh, sw, region_ld, ntok_pad, tokmap, tok_stride, vtokmap, vtok_stride);
-    LAUNCH_RET();
+    return ew_launch(swin_window_map_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, stream, rowmap, region, tq, tk, gh, gw, wh, ww, sh, sw, region_ld,
+                     ntok_pad, tokmap, tok_stride, vtokmap, vtok_stride);
 }
 
 int MDPT_FN(mdpt_launch_swin_cpb)(const float* w1, const float* b1, const float* w2, float* lut, int heads, int hidden, int wh, int ww, int pretrained,
                          hipStream_t stream) {
     const int R = (2 * wh - 1) * (2 * ww - 1);
-    MdptProfScope prof("swin_cpb_kernel", 0.0, stream);
-    hipLaunchKernelGGL(swin_cpb_kernel, dim3((R + kCpbPos - 1) / kCpbPos), dim3(256), (size_t)kCpbPos * hidden * 4, stream, w1, b1, w2, lut, heads,
-                       hidden, wh, ww, pretrained);
-    LAUNCH_RET();
+    return ew_launch("swin_cpb_kernel", 0.0, swin_cpb_kernel, dim3((R + kCpbPos - 1) / kCpbPos), dim3(256), (size_t)kCpbPos * hidden * 4, stream, w1, b1, w2, lut, heads,
+                     hidden, wh, ww, pretrained);
 }
 
 int MDPT_FN(mdpt_launch_swin_cpb_batch)(const SwinCpbBatch& b, hipStream_t stream) {
     if (b.n < 1 || b.n > 32) return (int)hipErrorInvalidValue;
     int rmax = 0;
     for (int l = 0; l < b.n; ++l) rmax = std::max(rmax, (2 * b.wh[l] - 1) * (2 * b.ww[l] - 1));
-    MdptProfScope prof("swin_cpb_batch_kernel", 0.0, stream);
-    hipLaunchKernelGGL(swin_cpb_batch_kernel, dim3((rmax + kCpbPos - 1) / kCpbPos, b.n), dim3(256), (size_t)kCpbPos * b.hidden * 4, stream, b);
-    LAUNCH_RET();
+    return ew_launch("swin_cpb_batch_kernel", 0.0, swin_cpb_batch_kernel, dim3((rmax + kCpbPos - 1) / kCpbPos, b.n), dim3(256), (size_t)kCpbPos * b.hidden * 4, stream, b);
 }
 
 int MDPT_FN(mdpt_launch_swin_qkv_prep)(const float* qkv, const int* rowmap, const float* logit_scale, op_t* q_hi, op_t* q_lo, op_t* k_hi,
                               op_t* k_lo, op_t* vt_hi, op_t* vt_lo, int B, int N, int nw, int wa, int npad, int npadv, int heads,
                               hipStream_t stream, bool qk) {
     if (qk) {
-        MdptProfScope prof_qk("swin_qk_prep", 0.0, stream);
-        hipLaunchKernelGGL(swin_qk_prep_kernel, dim3(grid_for((size_t)B * nw * wa * 2 * heads * 8)), dim3(256), 0, stream, qkv, rowmap, logit_scale,
-                           q_hi, q_lo, k_hi, k_lo, B, N, nw, wa, npad, heads);
+        const int e = ew_launch("swin_qk_prep", 0.0, swin_qk_prep_kernel, dim3(grid_for((size_t)B * nw * wa * 2 * heads * 8, SWIN_GRID_CAP)), dim3(256), 0, stream, qkv,
+                                rowmap, logit_scale, q_hi, q_lo, k_hi, k_lo, B, N, nw, wa, npad, heads);
+        if (e) return e;  // (the code the function returned before, when the error stayed pending until after the second launch)
     }
-    MdptProfScope prof("swin_v_prep", 0.0, stream);
+    MdptProfScope prof("swin_v_prep", 0.0, stream);  // by hand: the scope opens before the argument check, as it always has
     const size_t v_lds = (size_t)(vt_lo ? 2 : 1) * 32 * (npadv + 8) * 2;
     if (v_lds > 160 * 1024 || (npadv & 63)) return (int)hipErrorInvalidValue;
     static bool attr_done = false;
@@ -369,22 +331,17 @@ int MDPT_FN(mdpt_launch_swin_qkv_prep)(const float* qkv, const int* rowmap, cons
         if (e != hipSuccess) return (int)e;
         attr_done = true;
     }
-    hipLaunchKernelGGL(swin_v_prep_kernel, dim3((unsigned)((size_t)B * nw * heads)), dim3(256), v_lds, stream, qkv, rowmap, vt_hi, vt_lo, B, N, nw, wa,
-                       npadv, heads);
-    LAUNCH_RET();
+    return ew_launch(swin_v_prep_kernel, dim3((unsigned)((size_t)B * nw * heads)), dim3(256), v_lds, stream, qkv, rowmap, vt_hi, vt_lo, B, N, nw, wa, npadv, heads);
 }
 
 int MDPT_FN(mdpt_launch_swin_merge_gather)(const float* tok, op_t* out_hi, op_t* out_lo, int B, int gh, int gw, int C, hipStream_t stream) {
     if ((gh & 1) || (gw & 1) || (C & 3)) return (int)hipErrorInvalidValue;
-    MdptProfScope prof("swin_merge_gather_kernel", 0.0, stream);
-    hipLaunchKernelGGL(swin_merge_gather_kernel, dim3(grid_for((size_t)B * gh * gw * (C / 4))), dim3(256), 0, stream, tok, out_hi, out_lo, B, gh,
-                       gw, C);
-    LAUNCH_RET();
+    return ew_launch("swin_merge_gather_kernel", 0.0, swin_merge_gather_kernel, dim3(grid_for((size_t)B * gh * gw * (C / 4), SWIN_GRID_CAP)), dim3(256), 0, stream, tok,
+                     out_hi, out_lo, B, gh, gw, C);
 }
 
 int MDPT_FN(mdpt_launch_f32_to_planes)(const float* in, op_t* out_hi, op_t* out_lo, size_t rows, int F, int ld, hipStream_t stream) {
     if ((F & 3) || ld < F || (ld & 3)) return (int)hipErrorInvalidValue;
     const size_t n4 = rows * (size_t)(F / 4);
-    hipLaunchKernelGGL(f32_to_planes_kernel, dim3(grid_for(n4)), dim3(256), 0, stream, in, out_hi, out_lo, n4, F / 4, ld);
-    LAUNCH_RET();
+    return ew_launch(f32_to_planes_kernel, dim3(grid_for(n4, SWIN_GRID_CAP)), dim3(256), 0, stream, in, out_hi, out_lo, n4, F / 4, ld);
 }

@@ -119,7 +119,8 @@ def test_slabs_are_read_in_place_and_texture_views_are_accepted():
     wide = [torch.from_numpy(np.concatenate([t, t], axis=1)).cuda() for t in textures]
     got = pp.render_mesh(xyz, uv, faces, counts, [w[:, :t.shape[1]] for w, t in zip(wide, textures)], rr.case_views("tri", (37, 29)), (37, 29))
     assert torch.equal(got, want)
-    assert all(t.data_ptr() == p and torch.equal(t, c) for t, (p, c) in zip((xyz, uv, faces, counts), before))
+    # (bit for bit: the slabs' tails are unspecified and may hold NaN left by whichever test owned the memory before, which compares unequal to itself)
+    assert all(t.data_ptr() == p and torch.equal(t.view(torch.int32), c.view(torch.int32)) for t, (p, c) in zip((xyz, uv, faces, counts), before))
 
 
 def test_render_views_is_the_four_step_composition():

@@ -28,9 +28,9 @@ def test_every_quoted_include_is_a_tracked_dependency():
                 assert found, f"{os.path.relpath(path, native.REPO)} includes {name}, which is in none of the include directories"
                 assert os.path.realpath(found[0]) in covered, f"{name} (included by {os.path.relpath(path, native.REPO)}) is not in native.HEADERS"
                 todo.append(found[0])
-    # what started this test: the fp8 cross terms, the dtype loads, and the files postprocess.hip is made of
+    # what started this test: the fp8 cross terms, the dtype loads, and the files postprocess.hip and elementwise.hip are made of
     names = {os.path.basename(p) for p in seen}
-    assert {"f8_cross.h", "dt_io.h", "post_common.inc", "mdpt.h"} <= names
+    assert {"f8_cross.h", "dt_io.h", "post_common.inc", "ew_common.inc", "mdpt.h"} <= names
 
 
 def test_no_dependency_is_listed_twice_and_the_order_is_fixed():
