@@ -692,6 +692,39 @@ int mdpt_post_fill_scratch_bytes(int32_t N, int32_t H, int32_t W, size_t* bytes)
 int mdpt_post_fill_holes(const void* color_bgra, const void* depth_f32, int32_t N, int32_t H, int32_t W, double band, void* out_bgra, void* out_depth_f32,
                          void* scratch, size_t scratch_bytes, void* stream);
 
+/* Temporally stable video depth on the device (additive to ABI v6; not in the reference, whose video demo normalises every frame on its own). The
+ * relative-depth families return each map up to a scale and a shift of its own; these three stages align a clip's maps to one another, filter them
+ * over time and display them with a carried range. T frames of one size per call ([T,h,w], fp32 / bf16 / fp16); a clip of any length streams through
+ * in calls, the state between calls being five small device buffers that nothing reads back: the raw last frame [h,w] (the frames' dtype), the
+ * last output fp32 [h,w], ab fp64 [2], the display range fp32 [2] and started int32 [2] ({chain, range}: 0 = nothing before this call).
+ *   fit:     pair t: x = frame t, y = frame t - 1 (t = 0: prev_frame; started == 0: a START, no pair), over the pixels where both are finite. Round 0:
+ *            w = 1; round k = 1 .. rounds: w = 1 / (1 + r^2 / (c^2 s^2)), r = a x + b - y, {a, b, s^2} of round k - 1. Each round: the weighted sums
+ *            {n, Sx, Sy, Sxx, Sxy, Syy} (2048-pixel chunks, a fixed tree inside a chunk, chunks added in order), var = n Sxx - Sx^2, cov = n Sxy - Sx Sy,
+ *            a = cov / var, b = (Sy - a Sx) / n, s^2 = max(0, (Syy - a Sxy - b Sy) / n). s^2 <= 2^-40 Syy / n: the frames agree exactly, the fit is kept.
+ *            CUT (kept too): fewer than two samples, var <= 0, a <= 0, a result that is not finite, and for the final fit var_y <= 0 or
+ *            cov^2 < cut_corr^2 var var_y. sums_f64 (or NULL) [rounds + 1, T, 6]: a kept pair repeats its last sums, a start has zeros.
+ *   chain:   one lane, in order from ab_in: A_t = A_{t-1} a_t, B_t = A_{t-1} b_t + B_{t-1}, sigma_t = A_{t-1} s_t; a start, a cut, a result that is not
+ *            finite or an A_t outside [2^-20, 2^20] re-anchors: A = 1, B = 0, sigma = 0, cut = 1. table_f64 [T,4] = {A, B, sigma, cut}; ab_out = the last.
+ *            2 (rounds + 1) + 1 launches whatever T. prev_frame and ab_in are not read where started == 0 (they must still be valid buffers).
+ *   filter:  per pixel, in frame order, o_prev from prev_out_f32 [h,w]: s = A_t p + B_t; at a cut, or where o_prev or p is not finite: o = s; else
+ *            d = s - o_prev, g = d^2 / (d^2 + (tau sigma_t)^2) (0 / 0 = 0), k = alpha + (1 - alpha) g, o = o_prev + k d, and o = s where k == 1; fp64,
+ *            rounded once to fp32, that fp32 being the next o_prev. out_f32 [T,h,w]. One launch; 0 < alpha <= 1, tau >= 0.
+ *   display: mdpt_post_minmax_seg / _u8_hist_seg / _colorize's arithmetic (out_h = out_w = 0: no resize) with the range (lo_t, hi_t) in place of the
+ *            frame's own min / max {m_t, M_t}: lo_t = fp32(lo_{t-1} + range_rate (m_t - lo_{t-1})) in fp64, hi alike; the frame's own at a cut, with
+ *            started == 0, with range_rate == 1, and where one of the four is not finite; values outside the range clamp. out_bgr uint8 [T,H,W,3],
+ *            ranges_f32 (or NULL) [T,2], range_out_f32 [2] = the last. Four launches. No histogram equalisation.
+ * Bit-deterministic, no atomics, nothing synchronises. scratch = mdpt_post_video_scratch_bytes (covers all three for these sizes), 8-byte aligned.
+ * Limits: T <= 65535, h w < 2^31, 0 <= rounds <= 8, c > 0, 0 <= cut_corr <= 1, 0 < range_rate <= 1. */
+int mdpt_post_video_scratch_bytes(int32_t T, int32_t h, int32_t w, int32_t out_h, int32_t out_w, size_t* bytes);
+int mdpt_post_video_fit(const void* frames, int32_t dtype, int32_t T, int32_t h, int32_t w, const void* prev_frame, const void* ab_in_f64, const void* started_i32,
+                        int32_t rounds, double c, double cut_corr, void* table_f64, void* ab_out_f64, void* sums_f64, void* scratch, size_t scratch_bytes,
+                        void* stream);
+int mdpt_post_video_filter(const void* frames, int32_t dtype, int32_t T, int32_t h, int32_t w, const void* table_f64, const void* prev_out_f32, double alpha,
+                           double tau, void* out_f32, void* stream);
+int mdpt_post_video_display(const void* stable_f32, int32_t T, int32_t h, int32_t w, const void* table_f64, const void* range_in_f32, const void* started_i32,
+                            int32_t out_h, int32_t out_w, int32_t reverse, const void* cmap_bgr, double range_rate, void* out_bgr, void* ranges_f32,
+                            void* range_out_f32, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

@@ -408,6 +408,19 @@ int mdpt_launch_post_align_apply(const AlignPair* pairs, int P, size_t max_pixel
 int mdpt_launch_post_guided(const GuidedPair* pairs, int P, int dt, int radius, double eps, int max_h, int max_w, int max_H, int max_W, char* scratch,
                             double* coeffs, hipStream_t stream);
 
+// temporally stable video depth (post_video.inc): frames = [T, hw] of dtype dt, prev = the raw last frame of the call before, started[0] != 0: there
+// was one (else frame 0 starts the chain). Fit: table [T, 4] fp64 {A, B, sigma, cut}, ab_out [2] the last (A, B), sums (null: not wanted) [rounds + 1, T, 6];
+// scratch = video_fit_scratch_doubles. 2 (rounds + 1) + 1 launches whatever T. Filter: one launch. Display: stable fp32 [T, h, w] -> BGR [T, oh, ow, 3]
+// with the carried range (scaled null: no resize); four launches. All bit-deterministic, no atomics.
+inline size_t video_fit_scratch_doubles(size_t T, size_t hw) { return T * tile_fit_chunks(hw) * 6 + T * 4; }
+int mdpt_launch_post_video_fit(const void* frames, int dt, int T, size_t hw, const void* prev, const double* ab_in, const int* started, int rounds, double c,
+                               double cut_corr, double* table, double* ab_out, double* sums, double* scratch, hipStream_t stream);
+int mdpt_launch_post_video_filter(const void* frames, int dt, int T, size_t hw, const double* table, const float* prev_out, double alpha, double tau, float* out,
+                                  hipStream_t stream);
+int mdpt_launch_post_video_display(const float* stable, int T, int h, int w, int oh, int ow, const double* table, const float* range_in, const int* started,
+                                   double rho, int reverse, const unsigned char* cmap, float* scaled, unsigned* parts, unsigned* rparts, unsigned char* u8,
+                                   unsigned char* out, float* ranges, float* range_out, hipStream_t stream);
+
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);
 

@@ -689,4 +689,92 @@ int mdpt_post_fill_holes(const void* color_bgra, const void* depth_f32, int32_t 
     return 0;
 }
 
+// ---- temporally stable video depth (frame-to-frame fit, temporal filter, carried display range; not in the reference)
+static int check_video_sizes(int32_t T, int32_t h, int32_t w) {
+    if (T <= 0 || T > 65535) return fail(MDPT_E_INVALID, "bad frame count %d (1 .. 65535 per call)", T);
+    if (h <= 0 || w <= 0 || (size_t)h * w >= ((size_t)1 << 31)) return fail(MDPT_E_INVALID, "bad frame size %dx%d (h w < 2^31)", h, w);
+    return 0;
+}
+
+// the display's scratch: the frames' and the carried ranges' partials, the resized fp32 frames (resize only), the uint8 frames - in that order
+static size_t video_display_scratch_bytes(size_t T, size_t out_px, bool resize) {
+    return 2 * T * MDPT_POST_SEG_PARTS * 2 * sizeof(unsigned) + (resize ? T * out_px * sizeof(float) : 0) + T * out_px;
+}
+
+static int check_video_out(int32_t h, int32_t w, int32_t out_h, int32_t out_w, size_t* out_px) {
+    if ((out_h == 0) != (out_w == 0) || out_h < 0 || out_w < 0) return fail(MDPT_E_INVALID, "bad display size %dx%d (0x0: the frames' own)", out_h, out_w);
+    *out_px = out_h ? (size_t)out_h * out_w : (size_t)h * w;
+    if (*out_px > (size_t)INT32_MAX) return fail(MDPT_E_INVALID, "a display frame of %dx%d is too large (fewer than 2^31 pixels)", out_h, out_w);
+    return 0;
+}
+
+int mdpt_post_video_scratch_bytes(int32_t T, int32_t h, int32_t w, int32_t out_h, int32_t out_w, size_t* bytes) {
+    if (!bytes) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_video_sizes(T, h, w));
+    size_t out_px;
+    CHK(check_video_out(h, w, out_h, out_w, &out_px));
+    const size_t fit = video_fit_scratch_doubles((size_t)T, (size_t)h * w) * sizeof(double);
+    const size_t display = video_display_scratch_bytes((size_t)T, out_px, out_h != 0);
+    *bytes = ((fit > display ? fit : display) + 7) & ~(size_t)7;
+    return 0;
+}
+
+int mdpt_post_video_fit(const void* frames, int32_t dtype, int32_t T, int32_t h, int32_t w, const void* prev_frame, const void* ab_in_f64, const void* started_i32,
+                        int32_t rounds, double c, double cut_corr, void* table_f64, void* ab_out_f64, void* sums_f64, void* scratch, size_t scratch_bytes,
+                        void* stream) {
+    if (!frames || !prev_frame || !ab_in_f64 || !started_i32 || !table_f64 || !ab_out_f64 || !scratch) return fail(MDPT_E_INVALID, "null argument");
+    if (!tensor_dtype_ok(dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dtype);
+    CHK(check_video_sizes(T, h, w));
+    if (rounds < 0 || rounds > 8) return fail(MDPT_E_INVALID, "rounds must be 0 .. 8, got %d", rounds);
+    if (!(c > 0.0) || c > 1e150) return fail(MDPT_E_INVALID, "c must be finite and > 0, got %g", c);
+    if (!(cut_corr >= 0.0 && cut_corr <= 1.0)) return fail(MDPT_E_INVALID, "cut_corr must be in [0, 1], got %g", cut_corr);
+    if ((((uintptr_t)ab_in_f64 | (uintptr_t)table_f64 | (uintptr_t)ab_out_f64 | (uintptr_t)sums_f64 | (uintptr_t)scratch) & 7) != 0 ||
+        ((uintptr_t)started_i32 & 3) != 0 || (((uintptr_t)frames | (uintptr_t)prev_frame) & (dtype_bytes(dtype) - 1)) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the fp64 buffers and the scratch need 8 bytes, the flag 4, the frames their element)");
+    const size_t need = video_fit_scratch_doubles((size_t)T, (size_t)h * w) * sizeof(double);
+    if (scratch_bytes < need) return fail(MDPT_E_INVALID, "video scratch of %zu bytes, %zu needed (mdpt_post_video_scratch_bytes)", scratch_bytes, need);
+    CHK(mdpt_launch_post_video_fit(frames, dtype, T, (size_t)h * w, prev_frame, (const double*)ab_in_f64, (const int*)started_i32, rounds, c, cut_corr,
+                                   (double*)table_f64, (double*)ab_out_f64, (double*)sums_f64, (double*)scratch, (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_video_filter(const void* frames, int32_t dtype, int32_t T, int32_t h, int32_t w, const void* table_f64, const void* prev_out_f32, double alpha,
+                           double tau, void* out_f32, void* stream) {
+    if (!frames || !table_f64 || !prev_out_f32 || !out_f32) return fail(MDPT_E_INVALID, "null argument");
+    if (!tensor_dtype_ok(dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dtype);
+    CHK(check_video_sizes(T, h, w));
+    if (!(alpha > 0.0 && alpha <= 1.0)) return fail(MDPT_E_INVALID, "alpha must be in (0, 1], got %g", alpha);
+    if (!(tau >= 0.0) || tau > 1e150) return fail(MDPT_E_INVALID, "tau must be finite and >= 0, got %g", tau);
+    if (((uintptr_t)table_f64 & 7) != 0 || (((uintptr_t)prev_out_f32 | (uintptr_t)out_f32) & 3) != 0 || ((uintptr_t)frames & (dtype_bytes(dtype) - 1)) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table needs 8 bytes, the fp32 buffers 4, the frames their element)");
+    if (out_f32 == frames || out_f32 == prev_out_f32) return fail(MDPT_E_INVALID, "the output must be a buffer of its own");
+    CHK(mdpt_launch_post_video_filter(frames, dtype, T, (size_t)h * w, (const double*)table_f64, (const float*)prev_out_f32, alpha, tau, (float*)out_f32,
+                                      (hipStream_t)stream));
+    return 0;
+}
+
+int mdpt_post_video_display(const void* stable_f32, int32_t T, int32_t h, int32_t w, const void* table_f64, const void* range_in_f32, const void* started_i32,
+                            int32_t out_h, int32_t out_w, int32_t reverse, const void* cmap_bgr, double range_rate, void* out_bgr, void* ranges_f32,
+                            void* range_out_f32, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!stable_f32 || !table_f64 || !range_in_f32 || !started_i32 || !out_bgr || !range_out_f32 || !scratch) return fail(MDPT_E_INVALID, "null argument");
+    CHK(check_video_sizes(T, h, w));
+    size_t out_px;
+    CHK(check_video_out(h, w, out_h, out_w, &out_px));
+    if (!(range_rate > 0.0 && range_rate <= 1.0)) return fail(MDPT_E_INVALID, "range_rate must be in (0, 1], got %g", range_rate);
+    if (((uintptr_t)table_f64 & 7) != 0 ||
+        (((uintptr_t)stable_f32 | (uintptr_t)range_in_f32 | (uintptr_t)started_i32 | (uintptr_t)ranges_f32 | (uintptr_t)range_out_f32 | (uintptr_t)scratch) & 3) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table needs 8 bytes, the fp32 buffers, the flag and the scratch 4)");
+    const bool resize = out_h != 0;
+    const size_t need = video_display_scratch_bytes((size_t)T, out_px, resize);
+    if (scratch_bytes < need) return fail(MDPT_E_INVALID, "video scratch of %zu bytes, %zu needed (mdpt_post_video_scratch_bytes)", scratch_bytes, need);
+    unsigned* parts = (unsigned*)scratch;
+    unsigned* rparts = parts + (size_t)T * MDPT_POST_SEG_PARTS * 2;
+    float* scaled = resize ? (float*)(rparts + (size_t)T * MDPT_POST_SEG_PARTS * 2) : nullptr;
+    unsigned char* u8 = (unsigned char*)(rparts + (size_t)T * MDPT_POST_SEG_PARTS * 2) + (resize ? (size_t)T * out_px * sizeof(float) : 0);
+    CHK(mdpt_launch_post_video_display((const float*)stable_f32, T, h, w, resize ? out_h : h, resize ? out_w : w, (const double*)table_f64,
+                                       (const float*)range_in_f32, (const int*)started_i32, range_rate, reverse != 0, (const unsigned char*)cmap_bgr, scaled, parts,
+                                       rparts, u8, (unsigned char*)out_bgr, (float*)ranges_f32, (float*)range_out_f32, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

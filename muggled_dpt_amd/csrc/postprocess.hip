@@ -15,3 +15,4 @@
 #include "post_guided.inc"   // photo-guided upsampling
 #include "post_render.inc"   // rendering of depth meshes
 #include "post_fill.inc"     // hole filling of rendered views
+#include "post_video.inc"    // temporally stable video depth: frame-to-frame fit, temporal filter, carried display range

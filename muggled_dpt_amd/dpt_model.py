@@ -928,6 +928,27 @@ class DPTModel(nn.Module):
                                      mean3, std3, native.INTERP_BILINEAR, out, native.dtype_code(out.dtype), size_hw=(h, w), batch=b)
             return out
 
+    def inference_video(self, frames_bgr, state=None, batch_size: int = 32, max_side_length: int | None = None, use_square_sizing: bool = True,
+                        **stabilize):
+        """The frames of a clip (inference_batch's input: one size), in order -> (stable fp32 [T,H',W'], table fp64 [T,4], state): inference_batch in
+        chunks of at most batch_size frames, each chunk through video.stabilize_video (whose keywords - rounds, c, cut_corr, alpha, tau - pass
+        through), the state carried from chunk to chunk and returned for the clip's next call. The maps of a clip share a scale and a shift and
+        are filtered over time (muggled_dpt_amd.video); the result is that of stabilize_video on the inference_batch maps of the same chunks, and
+        does not depend on batch_size where inference_batch's rows do not (the default, batch-invariant modes). Not in the reference."""
+        from .video import stabilize_video
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size <= 0:
+            raise ValueError(f"inference_video: batch_size must be a positive integer, got {batch_size!r}")
+        total = len(frames_bgr)
+        if total == 0:
+            raise ValueError("inference_video got no frames")
+        stable, tables = [], []
+        for at in range(0, total, batch_size):
+            maps = self.inference_batch(frames_bgr[at:at + batch_size], max_side_length, use_square_sizing)
+            out, table, state = stabilize_video(maps, state, **stabilize)
+            stable.append(out)
+            tables.append(table)
+        return torch.cat(stable), torch.cat(tables), state
+
     def _run_view_chunks(self, views: list, chunks, p, img_dtype, boxed: bool = False) -> list[Tensor]:
         """The runner of the table routes (inference_images, inference_regions). views: uint8 [h,w,3] views, all host ndarrays (views of images
         included) or all device tensors _in_place() accepted; chunks: the forward plan [((H, W), [view indices]), ...] (image_chunks). One batched

@@ -254,6 +254,10 @@ SYMBOLS = {
     "mdpt_post_render": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _I, _I, _I, _I, _D, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "mdpt_post_fill_scratch_bytes": (ctypes.c_int, [_I, _I, _I, ctypes.POINTER(_SZ)]),
     "mdpt_post_fill_holes": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _D, _VP, _VP, _VP, _SZ, _VP]),
+    "mdpt_post_video_scratch_bytes": (ctypes.c_int, [_I, _I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "mdpt_post_video_fit": (ctypes.c_int, [_VP, _I, _I, _I, _I, _VP, _VP, _VP, _I, _D, _D, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "mdpt_post_video_filter": (ctypes.c_int, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _D, _VP, _VP]),
+    "mdpt_post_video_display": (ctypes.c_int, [_VP, _I, _I, _I, _VP, _VP, _VP, _I, _I, _I, _VP, _D, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

@@ -21,6 +21,10 @@ neighbours have in common): <name>_tiled.npy, fp32 [H, W], in the current direct
 For one image or several, --guided RADIUS EPS saves the depth at the PHOTO's resolution with the photo as the guide of the enlargement
 (postprocess.guided_upsample_images, one call for the whole list; RADIUS in cells of the model's map, EPS the variance below which the photo's texture
 is ignored, e.g. 8 1e-4; no photo may be smaller than the model's map of it): <name>_guided.npy, fp32 [H, W], in the current directory.
+--stable [ALPHA] takes the images, in order, as the frames of ONE clip (they share a size): DPTModel.inference_video aligns every frame's map to the
+frame before it and filters the clip over time (muggled_dpt_amd.video; ALPHA = the filter's weight, default 0.3), video_display shows it with a
+carried range: <name>_stable.npy (fp32, the model's map size) and <name>_stable.png (the photo's size) into --output (a directory; default: the
+current one). Nothing else is written in that mode.
 --crop X1 Y1 X2 Y2 is the reference's --crop with a stored box: normalised corners, applied to every image before it is predicted
 (crop_slices_from_norm: a side under 5 px falls back to the image's full extent); every output is then that of the cropped image.
 
@@ -87,6 +91,9 @@ def main():
                     "instead of the swing (views 000 and 001)")
     ap.add_argument("--render_fill", type=float, nargs="?", const=0.1, default=None, metavar="BAND", help="render: fill the holes of every view "
                     "(depth-banded push-pull, BAND in 0..1, default 0.1): the PNGs then have alpha 255 everywhere")
+    ap.add_argument("--stable", type=float, nargs="?", const=0.3, default=None, metavar="ALPHA", help="the images, in order, are the frames of one clip "
+                    "(one size): save every frame's temporally stable depth <name>_stable.npy (fp32) and its display frame <name>_stable.png, "
+                    "normalised by a carried range, into --output (a directory; default: the working directory); ALPHA = the filter's weight, default 0.3")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mdpt_run_image needs an MI355X: no GPU visible (there is no CPU fallback)")
@@ -100,6 +107,8 @@ def main():
         from muggled_dpt_amd.synthetic import make_synthetic_original_state_dict
         cfg, model = make_depthanythingv2_dpt_from_original_state_dict(make_synthetic_original_state_dict(args.synthetic, 0))
     model.to("cuda", torch.float32 if args.fp32 else torch.bfloat16)
+    if args.stable is not None:
+        return run_clip(model, args)
     if args.image_path and len(args.image_path) > 1:
         return run_images(model, args, t0, bool(cfg.get("is_metric", False)))
     if args.image_path:
@@ -323,6 +332,28 @@ def run_images(model, args, t0, is_metric=False):
     save_tiled(model, args, args.image_path, images)
     save_true_depth(args, is_metric, args.image_path, depths)
     save_guided(args, args.image_path, images, depths)
+
+
+def run_clip(model, args):
+    """--stable: the images as the frames of one clip through DPTModel.inference_video, the display frames through video.video_display"""
+    from muggled_dpt_amd import mesh_io
+    from muggled_dpt_amd.video import video_display
+    if not args.image_path:
+        raise SystemExit("--stable needs the clip's frames: -i FRAME.npy for every frame, in order")
+    frames = [np.load(p) for p in args.image_path]
+    if len({f.shape for f in frames}) != 1:
+        raise SystemExit(f"--stable: the frames of a clip share one size, got {sorted({f.shape for f in frames})}")
+    stable, table, _ = model.inference_video(frames, None, args.batch_size, args.size, not args.use_aspect_ratio, alpha=args.stable)
+    shown, _ = video_display(stable, table, None, (frames[0].shape[1], frames[0].shape[0]), args.reverse)
+    out_dir = args.output or "."
+    os.makedirs(out_dir, exist_ok=True)
+    cuts = table[:, 3].cpu().numpy()
+    for k, path in enumerate(args.image_path):
+        stem = os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0] + "_stable")
+        np.save(stem + ".npy", stable[k].cpu().numpy())
+        with open(stem + ".png", "wb") as fh:
+            fh.write(mesh_io.encode_png(shown[k].cpu().numpy()))
+        print("saved", stem + ".npy", stem + ".png", "(the chain re-anchors here)" if cuts[k] and k else "")
 
 
 if __name__ == "__main__":
