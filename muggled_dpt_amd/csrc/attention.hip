@@ -28,10 +28,9 @@
 #include "mdpt_kernels.h"
 #include "mdpt_prof.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
 namespace {
+
+#include "mfma_common.inc"  // vector types, glds16
 
 constexpr float kLog2e = 1.4426950408889634f;
 // Deferred running maximum of the online softmax: the reference point m of a query row only moves when a tile's maximum exceeds it by
@@ -40,11 +39,6 @@ constexpr float kLog2e = 1.4426950408889634f;
 // queries moves in almost every tile, so the skip never fired). p = exp(s - m) <= e^5.5 is harmless in fp32 / bf16 and the final
 // O / l is the same number mathematically; a lane's decision depends on its own query only (batch-invariant bits).
 constexpr float kDeferMax = 5.5f;
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 __device__ __forceinline__ opx8 cat44(opx4 a, opx4 b) {
     opx8 r;
@@ -396,7 +390,6 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
         // ends up with the standard B fragment (keys 16kb + 8*hi + 0..7): lower lanes keep (0,1),(2,3) and receive
         // (4,5),(6,7) from lane+32; upper lanes receive (8,9),(10,11) and keep (12,13),(14,15). Vt fragments are then
         // plain conflict-free ds_read_b128, shared by all query blocks.
-        typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
@@ -504,7 +497,6 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
             // 16-byte stores (fewest store instructions for the bytes moved): this lane owns
             // d = 8g + 4*half + 0..3 for g = 0..3; one v_permlane32_swap per packed register pair hands the lower lane the
             // whole d = 8g .. 8g+7 run of the even g and the upper lane that of the odd g
-            typedef __attribute__((ext_vector_type(4))) unsigned u32x4s;
 #pragma unroll
             for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -535,8 +527,8 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
                         }
                     }
                     const size_t o = orow + db * 32 + 8 * (2 * gp + half);
-                    *(u32x4s*)(p.out_hi + o) = u32x4s{oh[0], oh[1], oh[2], oh[3]};
-                    if (X3) *(u32x4s*)(p.out_lo + o) = u32x4s{ol[0], ol[1], ol[2], ol[3]};
+                    *(u32x4*)(p.out_hi + o) = u32x4{oh[0], oh[1], oh[2], oh[3]};
+                    if (X3) *(u32x4*)(p.out_lo + o) = u32x4{ol[0], ol[1], ol[2], ol[3]};
                 }
         }
     }
@@ -643,22 +635,13 @@ int MDPT_FN(mdpt_launch_attention)(const AttnParams& p, hipStream_t stream) {
         const unsigned lds_s = (unsigned)(4 * ring + extra);
         MdptProfScope prof_s(bias ? "attn_kernel<false, 1, 1, 64, split>" : "attn_kernel<false, 1, 0, 64, split>",
                              4.0 * p.B * p.heads * (double)p.N * p.N * hd, stream);
-        static bool attr0 = false, attr1 = false;
         if (bias) {
-            auto kern = attn_kernel<false, 1, 1, 64, true>;
-            if (!attr1) {
-                hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return (int)e;
-                attr1 = true;
-            }
+            constexpr auto kern = attn_kernel<false, 1, 1, 64, true>;
+            if (const int e = mdpt_lds_limit<kern>(160 * 1024)) return e;
             hipLaunchKernelGGL(kern, dim3((unsigned)blocks32), dim3(256), lds_s, stream, ps);
         } else {
-            auto kern = attn_kernel<false, 1, 0, 64, true>;
-            if (!attr0) {
-                hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return (int)e;
-                attr0 = true;
-            }
+            constexpr auto kern = attn_kernel<false, 1, 0, 64, true>;
+            if (const int e = mdpt_lds_limit<kern>(160 * 1024)) return e;
             hipLaunchKernelGGL(kern, dim3((unsigned)blocks32), dim3(256), lds_s, stream, ps);
         }
         return (int)hipGetLastError();
@@ -677,13 +660,8 @@ int MDPT_FN(mdpt_launch_attention)(const AttnParams& p, hipStream_t stream) {
 #define ATTN_LAUNCH(X3_, QB_, MODE_, HD_, GRID_) ATTN_LAUNCH_R(X3_, QB_, MODE_, HD_, GRID_, false)
 #define ATTN_LAUNCH_R(X3_, QB_, MODE_, HD_, GRID_, RUN4_)                                                               \
     do {                                                                                                                \
-        auto kern = attn_kernel<X3_, QB_, MODE_, HD_, false, RUN4_>;                                                    \
-        static bool attr_done = false;                                                                                  \
-        if (!attr_done) {                                                                                               \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            if (e != hipSuccess) return (int)e;                                                                         \
-            attr_done = true;                                                                                           \
-        }                                                                                                               \
+        constexpr auto kern = attn_kernel<X3_, QB_, MODE_, HD_, false, RUN4_>;                                          \
+        if (const int e = mdpt_lds_limit<kern>(160 * 1024)) return e;                                                   \
         hipLaunchKernelGGL(kern, GRID_, block, lds, stream, pq);                                                        \
     } while (0)
     // window attention with 4-key bias runs (AttnParams::bias_run4: the caller guarantees window width and token count are multiples of 4)

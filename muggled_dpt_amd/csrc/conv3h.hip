@@ -38,10 +38,9 @@
 
 #pragma clang fp contract(off)
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
 namespace {
+
+#include "mfma_common.inc"  // vector types, glds16 / plane_rsrc / memtime_now, PIN / BAR / WAIT_*, xcd_tile, stamp_record
 
 constexpr int HROW = 18 * 128;                 // bytes per halo row: 18 pixels x 64 channels bf16
 constexpr int HALO_INSTR = 41;                 // ceil(18 * 18 * 128 / 1024) LDS-DMA instructions per halo patch
@@ -51,21 +50,6 @@ constexpr int OFF_H = 2 * BTILE, OFF_SCR = OFF_H + 2 * HALO_BYTES;
 constexpr int LDS_BYTES = OFF_SCR + 1024;
 constexpr int UPW = 10;                        // side of the coarse patch of the bilinear add (16 fine pixels span <= 9.x coarse ones)
 static_assert(UPW * UPW * 1024 <= LDS_BYTES, "coarse patch must fit the ring");
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ unsigned long long memtime_now() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const void* base, size_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)(unsigned)(bytes < 0xFFFFFFF0ull ? bytes : 0xFFFFFFF0ull), 0x00020000);
-}
 
 // NP = 3: split precision (x = hi + lo planes for the input and the weights, hi / lo output planes): the K loop runs three times,
 // A_lo * W_hi, A_hi * W_lo, A_hi * W_hi, into the same fp32 accumulators - the pass order of the implicit-GEMM kernels. A pass is just
@@ -103,12 +87,7 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
     // ---- tile -> (image, tile row, tile column); the dispatcher places block b on XCD b % 8: every XCD gets a contiguous run of tiles
     //      (neighbouring tiles share halo rows / columns in that XCD's L2)
     const int tiles_x = (p.W + 15) >> 4, tiles_y = (p.H + 15) >> 4;
-    int tile;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7;
-        tile = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
-    }
+    const int tile = xcd_tile();
     const int img = tile / (tiles_x * tiles_y), trem = tile - img * (tiles_x * tiles_y);
     const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
     const int Y0 = ty * 16, X0 = tx * 16;
@@ -161,6 +140,8 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
         else if constexpr (P == 1) return rs_in_a8;
         else return rs_in_lo;
     };
+    // (two stagers, one per ring form: merged into one with the ring slot and the instruction range as arguments, 16 instantiations - every COUT = 128
+    //  multi-pass form and the fp8 forms - get a different instruction stream)
     auto issue_b = [&](auto pc, int half, int buf, int kt) __attribute__((always_inline)) {  // half-tile `half` (128 weight rows) of K tile kt -> B buffer `buf`
         if constexpr (F8) {
             constexpr int P = decltype(pc)::value, PN = P + 1 < NP ? P + 1 : P;
@@ -275,8 +256,11 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
 #define PC0 (std::integral_constant<int, 0>{})
 #define PC1 (std::integral_constant<int, 1>{})
 #define PCL (std::integral_constant<int, NP - 1>{}) /* the fp16 pass (the only pass of the single-pass forms) */
-#define PIN() __builtin_amdgcn_sched_barrier(0)
-#define BAR() do { PIN(); __builtin_amdgcn_s_barrier(); PIN(); } while (0)
+// the 18 K tiles of a pair of channel blocks, fully unrolled: KT_(U, ...) for U = 0 .. 17 (U is a compile-time constant of every K-tile macro)
+#define CONV_REP18(KT_, ...)                                                                                                                                    \
+    KT_(0, ##__VA_ARGS__); KT_(1, ##__VA_ARGS__); KT_(2, ##__VA_ARGS__); KT_(3, ##__VA_ARGS__); KT_(4, ##__VA_ARGS__); KT_(5, ##__VA_ARGS__);                    \
+    KT_(6, ##__VA_ARGS__); KT_(7, ##__VA_ARGS__); KT_(8, ##__VA_ARGS__); KT_(9, ##__VA_ARGS__); KT_(10, ##__VA_ARGS__); KT_(11, ##__VA_ARGS__);                 \
+    KT_(12, ##__VA_ARGS__); KT_(13, ##__VA_ARGS__); KT_(14, ##__VA_ARGS__); KT_(15, ##__VA_ARGS__); KT_(16, ##__VA_ARGS__); KT_(17, ##__VA_ARGS__)
 #define LOAD_A(QM_, VA_, ROW0_)                                                                                       \
     do {                                                                                                              \
         _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                               \
@@ -333,8 +317,6 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
 #define MQ8A(QM_, QN_, FB_) MFMA_Q8(QM_, QN_, FB_, wsc)
 #define MQ8B(QM_, QN_, FB_) MFMA_Q8(QM_, QN_, FB_, wsc_lo)
 #endif
-#define WAIT_LGKM(N_) asm volatile("s_waitcnt lgkmcnt(" #N_ ")" ::: "memory")
-#define WAIT_VM_IMM(N_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory")
 
     if constexpr (UPIN) {
         // ---- 128 output channels, input = x2 upsample of p.up_in, interpolated per channel block:
@@ -347,6 +329,7 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
         //     this and the previous K tile may stay in flight.
         constexpr int PATCH_OFF = 3 * (BTILE / 2);  // the fourth 16 KB of the weight region
         const float sy = (float)(p.Hs - 1) / (float)(p.H - 1), sx = (float)(p.Ws - 1) / (float)(p.W - 1);
+        // (mdpt_up_patch(.., halo = 1) written out: through the shared function the instruction stream of this form changes)
         const int oy_first = Y0 == 0 ? 0 : Y0 - 1, ox_first = X0 == 0 ? 0 : X0 - 1;
         const int oy_last = min(Y0 + 16, p.H - 1), ox_last = min(X0 + 16, p.W - 1);
         const int py0 = (int)(sy * (float)oy_first), px0 = (int)(sx * (float)ox_first);
@@ -435,8 +418,7 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
         } while (0)
         for (int cbp = 0; cbp < nvcb; cbp += 2) {
             const bool last = cbp + 2 >= nvcb;
-            CONV_KT128U(0); CONV_KT128U(1); CONV_KT128U(2); CONV_KT128U(3); CONV_KT128U(4); CONV_KT128U(5); CONV_KT128U(6); CONV_KT128U(7); CONV_KT128U(8);
-            CONV_KT128U(9); CONV_KT128U(10); CONV_KT128U(11); CONV_KT128U(12); CONV_KT128U(13); CONV_KT128U(14); CONV_KT128U(15); CONV_KT128U(16); CONV_KT128U(17);
+            CONV_REP18(CONV_KT128U);
         }
 #undef CONV_KT128U
     } else
@@ -472,8 +454,7 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
             BAR(); WAIT_LGKM(0); PIN();                                                                               \
             MQ(1, 0, fb0); BAR();                                                                                 \
         } while (0)
-#define CONV_PAIR128(MQ, PC_) CONV_KT128(0, MQ, PC_); CONV_KT128(1, MQ, PC_); CONV_KT128(2, MQ, PC_); CONV_KT128(3, MQ, PC_); CONV_KT128(4, MQ, PC_); CONV_KT128(5, MQ, PC_); CONV_KT128(6, MQ, PC_); CONV_KT128(7, MQ, PC_); CONV_KT128(8, MQ, PC_); \
-            CONV_KT128(9, MQ, PC_); CONV_KT128(10, MQ, PC_); CONV_KT128(11, MQ, PC_); CONV_KT128(12, MQ, PC_); CONV_KT128(13, MQ, PC_); CONV_KT128(14, MQ, PC_); CONV_KT128(15, MQ, PC_); CONV_KT128(16, MQ, PC_); CONV_KT128(17, MQ, PC_)
+#define CONV_PAIR128(MQ, PC_) CONV_REP18(CONV_KT128, MQ, PC_)
         int cbp = 0;
 #if MDPT_HAVE_F8
         if constexpr (F8) {  // the cross-term passes (one loop per pass: the fp16 pass always follows, nothing drains here)
@@ -533,8 +514,7 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
         BAR();                                                                                                        \
         MQ(1, 0, fb0); BAR();                                                                                     \
     } while (0)
-#define CONV_PAIR(MQ, PC_) CONV_KT(0, MQ, PC_); CONV_KT(1, MQ, PC_); CONV_KT(2, MQ, PC_); CONV_KT(3, MQ, PC_); CONV_KT(4, MQ, PC_); CONV_KT(5, MQ, PC_); CONV_KT(6, MQ, PC_); CONV_KT(7, MQ, PC_); CONV_KT(8, MQ, PC_); \
-        CONV_KT(9, MQ, PC_); CONV_KT(10, MQ, PC_); CONV_KT(11, MQ, PC_); CONV_KT(12, MQ, PC_); CONV_KT(13, MQ, PC_); CONV_KT(14, MQ, PC_); CONV_KT(15, MQ, PC_); CONV_KT(16, MQ, PC_); CONV_KT(17, MQ, PC_)
+#define CONV_PAIR(MQ, PC_) CONV_REP18(CONV_KT, MQ, PC_)
     int cbp = 0;
 #if MDPT_HAVE_F8
     if constexpr (F8) {  // the cross-term passes (one loop per pass: the fp16 pass always follows, nothing drains here)
@@ -566,9 +546,9 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
 #endif
     if (p.dbg_times) t_loop = memtime_now();
 
-    // ---- epilogue. Lane (l15, lh) of wave (grp, wc) holds, for tile row y = 8 qm + 4 grp + i, pixel x = l15, the four consecutive channels
+    // ---- epilogue (in the kernel body: moved into a __forceinline__ function template of its own - thread / wave index derived again or passed in -
+    //      every instantiation gets a different instruction stream). Lane (l15, lh) of wave (grp, wc) holds, for tile row y = 8 qm + 4 grp + i, pixel x = l15, the four consecutive channels
     //      n = 128 qn + 32 wc + 16 j + 4 lh .. +3 in acc[qm][qn][i][j].
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
     const size_t plane_px = (size_t)p.H * p.W;
     const __amdgpu_buffer_rsrc_t rs_f = plane_rsrc(F32OUT ? p.out_f32 + (size_t)img * plane_px * COUT : nullptr, F32OUT ? plane_px * COUT * 4 : 0);
     const __amdgpu_buffer_rsrc_t rs_b = plane_rsrc(BFOUT ? p.out_bf + (size_t)img * plane_px * COUT : nullptr, BFOUT ? plane_px * COUT * 2 : 0);
@@ -590,11 +570,9 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
     if constexpr (UP) {
         up_sy = (float)(p.Hu - 1) / (float)(p.H - 1);
         const float sxs = (float)(p.Wu - 1) / (float)(p.W - 1);
-        const int ylast = min(Y0 + 15, p.H - 1), xlast = min(X0 + 15, p.W - 1);
-        up_py0 = (int)(up_sy * (float)Y0);
-        const int px0 = (int)(sxs * (float)X0);
-        const int ph = min((int)(up_sy * (float)ylast) + 1, p.Hu - 1) - up_py0 + 1;
-        up_pw = min((int)(sxs * (float)xlast) + 1, p.Wu - 1) - px0 + 1;  // <= UPW (launcher checks the scale)
+        const mdpt_up_patch_t pt = mdpt_up_patch(up_sy, sxs, Y0, X0, 0, p.H, p.W, p.Hu, p.Wu);  // the tile's own source patch; pw <= UPW (launcher checks the scale)
+        const int px0 = pt.px0, ph = pt.ph;
+        up_py0 = pt.py0; up_pw = pt.pw;
         const int xq = min(X0 + l15, p.W - 1);
         const float sx = sxs * (float)xq;
         const int x0 = (int)sx, x1 = x0 + (x0 < p.Wu - 1);
@@ -719,7 +697,6 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
                 __builtin_amdgcn_raw_buffer_store_b128(u32x4{ph[0], ph[1], ph[2], ph[3]}, rs_b, boff, 0, 0);
 #if MDPT_HAVE_F8
                 if ((X3 || LO_DYN) && lo8) {  // (wave-uniform) fp8 form: 8 e5m2 bytes of the residue (and of the values) per lane, from the same fp32 values / fp16 roundings
-                    typedef __attribute__((ext_vector_type(2))) unsigned u32x2v;
                     unsigned l8[2], a8[2];
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
@@ -729,9 +706,9 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
                     }
                     auto rl8 = __builtin_amdgcn_permlane16_swap(l8[0], l8[1], false, false);
                     const unsigned boff8 = ok ? pix * (unsigned)COUT + (colb >> 1) : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b64(u32x2v{rl8[0], rl8[1]}, rs_l8, boff8, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(u32x2{rl8[0], rl8[1]}, rs_l8, boff8, 0, 0);
                     auto ra8 = __builtin_amdgcn_permlane16_swap(a8[0], a8[1], false, false);
-                    __builtin_amdgcn_raw_buffer_store_b64(u32x2v{ra8[0], ra8[1]}, rs_a8, boff8, 0, 0);  // (zero records without an a8 plane: dropped)
+                    __builtin_amdgcn_raw_buffer_store_b64(u32x2{ra8[0], ra8[1]}, rs_a8, boff8, 0, 0);  // (zero records without an a8 plane: dropped)
                 } else
 #endif
                 // (unconditional where the form can have a lo plane at all: without one the descriptor has zero records and the store is dropped)
@@ -765,35 +742,21 @@ __global__ __launch_bounds__(512, 1) void conv3h_kernel(const Conv3hParams p) {
     }
     if (p.dbg_times && tid == 0) {
         const unsigned long long t_issued = memtime_now();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned long long* d = p.dbg_times + (size_t)blockIdx.x * 6;
-        d[0] = t_start; d[1] = t_first; d[2] = t_loop; d[3] = memtime_now();
-        d[4] = t_issued;
-        d[5] = __builtin_amdgcn_s_getreg(20 << 0 | 0 << 6 | 3 << 11);  // HW_REG_XCC_ID
+        stamp_record(p.dbg_times, t_start, t_first, t_loop, 5, t_issued);
     }
 }
-#undef PIN
-#undef BAR
-#undef WAIT_LGKM
-#undef WAIT_VM_IMM
+#undef CONV_REP18
 #undef PC0
 #undef PC1
 #undef PCL
 
 template <int NQN, int NP, bool SKIP, bool F32OUT, bool RELU, bool UP, bool BFOUT = true, bool UPIN = false, bool F8 = false>
 int launch_variant(const Conv3hParams& p, hipStream_t stream) {
-    auto kern = conv3h_kernel<NQN, NP, SKIP, F32OUT, RELU, UP, BFOUT, UPIN, F8>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    constexpr auto kern = conv3h_kernel<NQN, NP, SKIP, F32OUT, RELU, UP, BFOUT, UPIN, F8>;
+    if (const int e = mdpt_lds_limit<kern>(LDS_BYTES)) return e;
     const int tiles = p.B * ((p.H + 15) / 16) * ((p.W + 15) / 16);
-    static char prof_name[80] = "";
-    if (!prof_name[0])
-        snprintf(prof_name, sizeof(prof_name), "conv3h_kernel<%d, %s, %d, %d, %d, %d>", 128 * NQN, UPIN ? "bf16 up2-in" : (F8 ? (NP == 3 ? "x3f8" : "x2f8") : (NP == 3 ? "x3" : (NP == 2 ? "x2a" : "bf16"))), (int)SKIP, (int)F32OUT, (int)RELU,
-                 (int)UP);
+    const char* prof_name = mdpt_kernel_label<kern>("conv3h_kernel<%d, %s, %d, %d, %d, %d>", 128 * NQN, UPIN ? "bf16 up2-in" : (F8 ? (NP == 3 ? "x3f8" : "x2f8") : (NP == 3 ? "x3" : (NP == 2 ? "x2a" : "bf16"))),
+                                                    (int)SKIP, (int)F32OUT, (int)RELU, (int)UP);
     MdptProfScope prof(prof_name, 2.0 * p.B * p.H * p.W * (128.0 * NQN) * 9.0 * p.Cin, stream);  // algorithmic flops (one pass, whatever the mode)
     hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), LDS_BYTES, stream, p);
     return (int)hipGetLastError();

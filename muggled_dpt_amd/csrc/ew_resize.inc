@@ -154,12 +154,7 @@ int MDPT_FN(mdpt_launch_upsample)(const float* in, op_t* out_hi, op_t* out_lo, f
         const dim3 tiles(B * ((Ho + 7) / 8) * ((Wo + 7) / 8));
         const size_t lds = (size_t)49 * C * 4;
         if (C == 256) {
-            static bool attr_done = false;
-            if (!attr_done) {
-                hipError_t e = hipFuncSetAttribute((const void*)upsample_tiled_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-                if (e != hipSuccess) return (int)e;
-                attr_done = true;
-            }
+            if (const int e = mdpt_lds_limit<upsample_tiled_kernel<32>>(64 * 1024)) return e;
             return ew_launch(upsample_tiled_kernel<32>, tiles, dim3(256), lds, stream, in, out_hi, out_lo, B, Hi, Wi, Ho, Wo, out_f8, out_a8);
         }
         if (C == 128) return ew_launch(upsample_tiled_kernel<16>, tiles, dim3(256), lds, stream, in, out_hi, out_lo, B, Hi, Wi, Ho, Wo, out_f8, out_a8);

@@ -58,12 +58,10 @@
 // bilinear-add epilogue between the 128x128 and 256x256 kernels). Epilogue arithmetic is a negligible cost.
 #pragma clang fp contract(off)
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 namespace {
 
-#include "gemm_common.inc"            // helpers, lockstep operand stager, tile map
+#include "mfma_common.inc"            // vector types, LDS-DMA / clock helpers, schedule macros, XCD tile map, debug stamp record
+#include "gemm_common.inc"            // erf-GELU, plane stores, lockstep operand stager, tile map
 #include "gemm_epilogue_strip.inc"    // LDS-strip epilogues (all epilogue kinds)
 #include "gemm_lockstep.inc"          // gemm_kernel: lockstep main loop, K-split forms of the 64x64 tile
 #include "gemm8_epilogues.inc"        // direct epilogues of the 8-phase kernel
@@ -75,16 +73,10 @@ int launch_pp_mode(const GemmParams& p, hipStream_t stream) {
     if constexpr (MDPT_OP_IS_F16 && !F8 && (EKIND == MDPT_E_GENERIC || EKIND == MDPT_E_D2S) && DMODE != DM_RINIT) {
         if (p.f8) return launch_pp_mode<AMODE, EKIND, DMODE, true>(p, stream);  // fp8 cross terms: their own kernels
     }
-    auto kern = gemm8_kernel<AMODE, EKIND, DMODE, F8>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    constexpr auto kern = gemm8_kernel<AMODE, EKIND, DMODE, F8>;
+    if (const int e = mdpt_lds_limit<kern>(LDS)) return e;
     const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-    static char prof_name[64] = "";
-    if (!prof_name[0]) snprintf(prof_name, sizeof(prof_name), F8 ? "gemm8_kernel<%d, %d, %d, f8>" : "gemm8_kernel<%d, %d, %d>", AMODE, EKIND, DMODE);
+    const char* prof_name = mdpt_kernel_label<kern>(F8 ? "gemm8_kernel<%d, %d, %d, f8>" : "gemm8_kernel<%d, %d, %d>", AMODE, EKIND, DMODE);
     MdptProfScope prof(prof_name, 2.0 * (p.M_alg > 0 ? p.M_alg : p.M) * p.N * p.K, stream);  // algorithmic rows (token pad rows are not work)
     const int ks = (AMODE == MDPT_A_DENSE && EKIND == MDPT_E_GENERIC && DMODE == DM_F32 && p.ksplit > 1) ? p.ksplit : 1;
     hipLaunchKernelGGL(kern, dim3(tiles, ks), dim3(512), LDS, stream, p);
@@ -117,17 +109,10 @@ int launch_cfg(const GemmParams& p, hipStream_t stream) {
     if constexpr (MDPT_OP_IS_F16 && !F8 && BK == 64 && (EKIND == MDPT_E_GENERIC || EKIND == MDPT_E_D2S) && !(BM == 256 && BN == 256)) {
         if (p.f8) return launch_cfg<BM, BN, WM, WN, BK, NST, MINW, AMODE, EKIND, true>(p, stream);  // fp8 cross terms: their own kernels
     }
-    static bool attr_done = false;
-    auto kern = gemm_kernel<BM, BN, WM, WN, BK, NST, MINW, AMODE, EKIND, F8>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    constexpr auto kern = gemm_kernel<BM, BN, WM, WN, BK, NST, MINW, AMODE, EKIND, F8>;
+    if (const int e = mdpt_lds_limit<kern>(LDS)) return e;
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    static char prof_name[112] = "";
-    if (!prof_name[0])
-        snprintf(prof_name, sizeof(prof_name), F8 ? "gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d, f8>" : "gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d>", BM, BN, WM, WN, BK, NST, MINW, AMODE, EKIND);
+    const char* prof_name = mdpt_kernel_label<kern>(F8 ? "gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d, f8>" : "gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d>", BM, BN, WM, WN, BK, NST, MINW, AMODE, EKIND);
     MdptProfScope prof(prof_name, 2.0 * (p.M_alg > 0 ? p.M_alg : p.M) * p.N * p.K, stream);  // algorithmic flops (real rows, one pass whatever npass is)
     const int ks = ((AMODE == MDPT_A_DENSE || AMODE == MDPT_A_CONV3) && EKIND == MDPT_E_GENERIC && BM == 64 && BN == 64 && BK == 64 && p.ksplit > 1) ? p.ksplit : 1;
     hipLaunchKernelGGL(kern, dim3(tiles, ks), dim3(64 * WM * WN), LDS, stream, p);

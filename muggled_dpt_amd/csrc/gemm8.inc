@@ -325,8 +325,6 @@ __device__ __forceinline__ void gemm8_body(const GemmParams& p, char* smem, cons
     }
 
     opx8 fa[4][2], fb0[2][2], fb1[2][2];
-#define PIN() __builtin_amdgcn_sched_barrier(0)
-#define BAR() do { PIN(); __builtin_amdgcn_s_barrier(); PIN(); } while (0)
 #define LOAD_A(QM_, BUF_)                                                                                             \
     do {                                                                                                              \
         _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                               \
@@ -379,8 +377,6 @@ __device__ __forceinline__ void gemm8_body(const GemmParams& p, char* smem, cons
         __builtin_amdgcn_s_setprio(0);                                                                                \
     } while (0)
 #endif
-#define WAIT_LGKM(N_) asm volatile("s_waitcnt lgkmcnt(" #N_ ")" ::: "memory")
-#define WAIT_VM(N_) asm volatile("s_waitcnt vmcnt(" #N_ ")" ::: "memory")
 // RI form: quadrant (QM_, QN_)'s residual loads (inline asm, in-order return) have landed once at most N_ younger vector-memory operations
 // are outstanding; naming the eight accumulators as read-write operands keeps every use of them below this statement
 #define ACC_READY(QM_, QN_, N_)                                                                                                          \
@@ -593,11 +589,7 @@ __device__ __forceinline__ void gemm8_body(const GemmParams& p, char* smem, cons
         }
         if (p.dbg_times && tid == 0) {
             const unsigned long long t_issued = memtime_now();  // all of this wave's stores issued, none waited for
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            unsigned long long* d = p.dbg_times + (size_t)blockIdx.x * 6;
-            d[0] = t_start; d[1] = t_first; d[2] = t_loop; d[3] = memtime_now();
-            d[4] = t_issued;
-            d[5] = __builtin_amdgcn_s_getreg(4 << 0 | 0 << 6 | 31 << 11);
+            stamp_record(p.dbg_times, t_start, t_first, t_loop, STAMP_HW_ID, t_issued);
         }
         return;
     }
@@ -616,11 +608,7 @@ __device__ __forceinline__ void gemm8_body(const GemmParams& p, char* smem, cons
         } else {
             epilogue_direct_vt<false>(p, acc, m0, n0, grp, wc, lane);
         }
-        if (p.dbg_times && tid == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            unsigned long long* d = p.dbg_times + (size_t)blockIdx.x * 6;
-            d[0] = t_start; d[1] = t_first; d[2] = t_loop; d[3] = memtime_now(); d[4] = d[3]; d[5] = 0;
-        }
+        if (p.dbg_times && tid == 0) stamp_record(p.dbg_times, t_start, t_first, t_loop, STAMP_NO_ID);
         return;
     }
     __syncthreads();  // every wave is done reading the ring: reuse it as epilogue staging
@@ -642,18 +630,8 @@ __device__ __forceinline__ void gemm8_body(const GemmParams& p, char* smem, cons
                         for (int r = 0; r < 4; ++r) strip[(ii * 16 + 4 * lh + r) * 32 + j * 16 + l15] = acc[qm][qn][rb * 2 + ii][j][r];
                 epilogue_block<32, EKIND>(p, strip, lane, m0 + qm * 128 + grp * 64 + rb * 32, n0 + qn * 128 + wc * 32);
             }
-    if (p.dbg_times && tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned long long* d = p.dbg_times + (size_t)blockIdx.x * 6;
-        d[0] = t_start; d[1] = t_first; d[2] = t_loop; d[3] = memtime_now();
-        d[4] = __builtin_amdgcn_s_getreg(20 << 0 | 0 << 6 | 3 << 11);
-        d[5] = __builtin_amdgcn_s_getreg(4 << 0 | 0 << 6 | 31 << 11);
-    }
+    if (p.dbg_times && tid == 0) stamp_record(p.dbg_times, t_start, t_first, t_loop, 4);
 }
-#undef PIN
-#undef BAR
-#undef WAIT_LGKM
-#undef WAIT_VM
 
 // Operand order of the MFMAs: swapped -> accumulators hold 4 consecutive COLUMNS per lane and one of the direct epilogues
 // applies; plain order (4 consecutive ROWS per lane) + LDS strip for every other epilogue. For the generic epilogue the choice is

@@ -58,8 +58,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const void* base, si
 // next image's bias vector. One select per value, then the SAME single add as every other form of the epilogue ((acc + bias) ...).
 template <int MODE, bool X3, int ACT, bool IMGB = false>
 __device__ __forceinline__ void epilogue_direct(const GemmParams& p, f32x4 (&acc)[2][2][4][2], int m0, int n0, int grp, int wc, int lane) {
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     constexpr unsigned OOB = 0xFFFFFFF0u;
     const int l15 = lane & 15, lh = lane >> 4;
     const int rows_here = p.M - m0 < 256 ? p.M - m0 : 256;  // valid rows of this tile (tail tile: fewer)
@@ -299,7 +297,6 @@ __device__ __forceinline__ void epilogue_direct(const GemmParams& p, f32x4 (&acc
                 if (X3 && MODE == DM_BF16 && p.out_f8) {
                     // the lo plane in the fp8 form an F8 consumer reads (f8_cross.h): this lane's 8 columns -> 8 e5m2 bytes of the residue (and
                     // of the values), from the SAME fp32 values and fp16 roundings as the 16-bit form; byte offset = element offset = off / 2
-                    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
                     float hv[2][4], vv[2][4];
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
@@ -344,8 +341,6 @@ __device__ __forceinline__ void epilogue_direct(const GemmParams& p, f32x4 (&acc
 template <bool X3, bool IMGB = false>
 __device__ __forceinline__ void epilogue_swin_qk(const GemmParams& p, f32x4 (&acc)[2][2][4][2], int m0, int n0, int grp, int wc, int lane) {
 #pragma clang fp contract(off)
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     constexpr unsigned OOB = 0xFFFFFFF0u;
     const int l15 = lane & 15, lh = lane >> 4;
     const size_t plane = (size_t)(p.M / p.swin_N) * p.swin_img_rows * 64;  // bytes of a Q / K plane (< 4 GiB: checked by the caller)
@@ -470,8 +465,6 @@ __device__ __forceinline__ void epilogue_swin_qk(const GemmParams& p, f32x4 (&ac
 // are zeroed by the caller once per stage.
 template <bool X3, bool IMGB = false>
 __device__ __forceinline__ void epilogue_swin_vt(const GemmParams& p, f32x4 (&acc)[2][2][4][2], int m0, int n0, int grp, int wc, int lane) {
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
     constexpr unsigned OOB = 0xFFFFFFF0u;
     const int l15 = lane & 15, lh = lane >> 4;
     const size_t plane = (size_t)(p.M / p.swin_N) * p.swin_img_velems * 2;  // bytes; < 4 GiB checked by the caller
@@ -543,8 +536,6 @@ __device__ __forceinline__ void epilogue_swin_vt(const GemmParams& p, f32x4 (&ac
 // the tokens 8-15: one 16-byte store per lane and row block, no LDS. Same arithmetic as the strip path (bias add, hi/lo split).
 template <bool X3, bool IMGB = false>
 __device__ __forceinline__ void epilogue_direct_vt(const GemmParams& p, f32x4 (&acc)[2][2][4][2], int m0, int n0, int grp, int wc, int lane) {
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     constexpr unsigned OOB = 0xFFFFFFF0u;
     const int l15 = lane & 15, lh = lane >> 4;
     const size_t plane = (size_t)(p.M / p.npad) * p.F * p.npadv * 2;  // [B, heads, 64, npadv] bf16; < 4 GiB checked by the caller

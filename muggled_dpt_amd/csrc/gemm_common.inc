@@ -1,17 +1,5 @@
-// gemm.hip, part 1 (textually included inside its anonymous namespace): LDS-DMA / timing helpers, the erf-GELU, hi / lo plane stores, the operand
+// gemm.hip, part 1 (textually included inside its anonymous namespace, behind mfma_common.inc): the erf-GELU, hi / lo plane stores, the operand
 // stager of the lockstep kernels and the XCD-aware tile map.
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
-    // 64 lanes x 16 B -> lds_wave_base + lane*16 (destination is wave-uniform base + lane*16)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ unsigned long long memtime_now() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-
 // Exact-GELU 0.5 v (1 + erf(v/sqrt2)) (reference: nn.GELU() default, components/misc_helpers.py:113).
 // erf(|v|/sqrt2) = 1 - 2^(-|v| q(|v|)): -log2 erfc(|v|/sqrt2) = |v| q(|v|) with q a degree-7 polynomial (weighted minimax fit on
 // |v| <= 5.8, where erfc reaches 7e-9; beyond it the positive leading coefficient keeps the exponent growing, an overflowing q gives
@@ -46,7 +34,7 @@ __device__ __forceinline__ float gelu_erf(float v) {
 
 // The same function on PAIRS of values: every multiply / fma becomes one packed instruction (v_pk_mul_f32 / v_pk_fma_f32: two lanes of
 // IEEE fp32, the same bits as the scalar form above), only the exp2 stays scalar.
-typedef __attribute__((ext_vector_type(2))) float gelu_f32x2;
+typedef f32x2 gelu_f32x2;
 __device__ __forceinline__ gelu_f32x2 gelu_erf2(gelu_f32x2 v) {
     const gelu_f32x2 a = {fabsf(v[0]), fabsf(v[1])};
     gelu_f32x2 q = {MDPT_GELU_Q7, MDPT_GELU_Q7};
@@ -254,9 +242,7 @@ struct Stager {
 // XCD-aware tile mapping (bijective for any grid size): the dispatcher places block b on XCD b%8; give every XCD a
 // contiguous run of tiles (same A rows, all N tiles) so operand panels stay in that XCD's L2.
 __device__ __forceinline__ void tile_coords(int tiles_n, int BM, int BN, int& m0, int& n0) {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
+    const int nwg = gridDim.x, swz = xcd_tile();
     if (tiles_n >= 8 && (tiles_n & 3) == 0) {
         // wide outputs (fc1: 16 column tiles, QKV: 12): row-major order makes the 32 concurrent tiles of an XCD cover 2 row
         // blocks x ALL columns, i.e. the whole weight matrix (8 MB for fc1, twice the 4 MB L2) is re-streamed for every pair

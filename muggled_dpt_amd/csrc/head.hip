@@ -32,20 +32,12 @@
 #include <stdlib.h>
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
 namespace {
+
+#include "mfma_common.inc"  // vector types, glds16, memtime_now
 
 constexpr int TS = 16, HS = TS + 2;  // output tile side, halo side
 constexpr int PS = 12;               // max side of the source patch (launcher checks 17 * scale + 2 <= PS)
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
-    // 64 lanes x 16 B -> lds_wave_base + lane*16 (LDS-DMA: the destination is wave-uniform base + lane*16, no register round trip)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 struct TileGeom {
     int b, oy0, ox0, py0, px0, ph, pw;
@@ -64,7 +56,6 @@ __global__ __launch_bounds__(512, 1) void head_tail_kernel(const HeadTailParams 
     constexpr int PIXP = PIXB + 16, ROWB = ((HS * PIXP + 255) / 256) * 256;
     static_assert((PIXP / 16) % 2 == 1 && ROWB % 256 == 0, "halo pitches");
     constexpr int HALO_BYTES = HS * ROWB, PATCH_BYTES = PS * PS * PIXB, XCH_BYTES = 8 * 16 * 64 * 4;
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const sH = smem;
     char* const sP = smem + HALO_BYTES;
@@ -98,19 +89,6 @@ __global__ __launch_bounds__(512, 1) void head_tail_kernel(const HeadTailParams 
     const float head_b = p.head_b[0];
     if (tid < 64) sC[tid] = tid < 32 ? p.bias[tid] : p.head_w[tid - 32];  // published by the first tile's first barrier
 
-    // tile -> image, origin and the source patch its halo interpolates from (halo rows / columns outside the image are zero padding)
-    auto geom = [&](int tile) {
-        TileGeom g;
-        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y;
-        g.b = tile / (tiles_x * tiles_y);
-        g.oy0 = ty * TS; g.ox0 = tx * TS;
-        const int oy_first = g.oy0 == 0 ? 0 : g.oy0 - 1, ox_first = g.ox0 == 0 ? 0 : g.ox0 - 1;
-        const int oy_last = min(g.oy0 + TS, p.Ho - 1), ox_last = min(g.ox0 + TS, p.Wo - 1);
-        g.py0 = (int)(sy * (float)oy_first); g.px0 = (int)(sx * (float)ox_first);
-        g.ph = min((int)(sy * (float)oy_last) + 1, p.Hi - 1) - g.py0 + 1;
-        g.pw = min((int)(sx * (float)ox_last) + 1, p.Wi - 1) - g.px0 + 1;  // <= PS (launcher's scale check)
-        return g;
-    };
     // source patch global -> LDS by LDS-DMA, dense [ph*pw][CIN] image (pixel pitch pw): 1 KiB = PPI pixels per wave instruction
     auto issue_patch = [&](const TileGeom& g) {
         const op_t* src = p.src + (size_t)g.b * p.Hi * p.Wi * CIN;
@@ -125,17 +103,27 @@ __global__ __launch_bounds__(512, 1) void head_tail_kernel(const HeadTailParams 
         }
     };
 
+    // tile -> image, origin and the source patch its halo interpolates from (halo rows / columns outside the image are zero padding)
+    // (written out in both kernels, not through mdpt_up_patch(.., halo = 1) of up_bf16.h: as a shared function the kernels' instruction streams change)
+    auto geom = [&](int tile) {
+        TileGeom g;
+        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y;
+        g.b = tile / (tiles_x * tiles_y);
+        g.oy0 = ty * TS; g.ox0 = tx * TS;
+        const int oy_first = g.oy0 == 0 ? 0 : g.oy0 - 1, ox_first = g.ox0 == 0 ? 0 : g.ox0 - 1;
+        const int oy_last = min(g.oy0 + TS, p.Ho - 1), ox_last = min(g.ox0 + TS, p.Wo - 1);
+        g.py0 = (int)(sy * (float)oy_first); g.px0 = (int)(sx * (float)ox_first);
+        g.ph = min((int)(sy * (float)oy_last) + 1, p.Hi - 1) - g.py0 + 1;
+        g.pw = min((int)(sx * (float)ox_last) + 1, p.Wi - 1) - g.px0 + 1;  // <= PS (launcher's scale check)
+        return g;
+    };
     int tile = blockIdx.x;
     TileGeom g = geom(tile < ntiles ? tile : 0);
     if (tile < ntiles) issue_patch(g);
 
     int tile_no = 0;
-    auto stamp = [&](int slot) {
-        if (p.dbg_times && tile_no == 1 && tid == 0) {
-            unsigned long long t;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-            p.dbg_times[(size_t)blockIdx.x * 8 + slot] = t;
-        }
+    auto stamp = [&](int slot) {  // test hook (MDPT_HEAD_DBG builds): phase stamps of every workgroup's second tile (a lambda per kernel: as a shared function the streams change)
+        if (p.dbg_times && tile_no == 1 && tid == 0) p.dbg_times[(size_t)blockIdx.x * 8 + slot] = memtime_now();
     };
     for (; tile < ntiles; tile += gridDim.x, ++tile_no) {
         stamp(0);
@@ -360,7 +348,6 @@ __global__ __launch_bounds__(512, 1) void head_tail2_kernel(const HeadTailParams
     static_assert((PIXP / 16) % 2 == 1 && ROWB % 256 == 0, "halo pitches");
     constexpr int HALO_BYTES = HS * ROWB, PATCH_PLANE = PS * PS * PIXB;
     static_assert(8 * 16 * 64 * 4 <= 2 * HALO_BYTES, "the block exchange lives in the halo space");
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const sH = smem;                                  // [plane: hi, lo][HS rows][ROWB]
     char* const sP = smem + 2 * HALO_BYTES;                 // [plane: hi, lo][patch pixel][PIXB]
@@ -392,18 +379,6 @@ __global__ __launch_bounds__(512, 1) void head_tail2_kernel(const HeadTailParams
     const float head_b = p.head_b[0];
     if (tid < 64) sC[tid] = tid < 32 ? p.bias[tid] : p.head_w[tid - 32];  // published by the first tile's first barrier
 
-    auto geom = [&](int tile) {
-        TileGeom g;
-        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y;
-        g.b = tile / (tiles_x * tiles_y);
-        g.oy0 = ty * TS; g.ox0 = tx * TS;
-        const int oy_first = g.oy0 == 0 ? 0 : g.oy0 - 1, ox_first = g.ox0 == 0 ? 0 : g.ox0 - 1;
-        const int oy_last = min(g.oy0 + TS, p.Ho - 1), ox_last = min(g.ox0 + TS, p.Wo - 1);
-        g.py0 = (int)(sy * (float)oy_first); g.px0 = (int)(sx * (float)ox_first);
-        g.ph = min((int)(sy * (float)oy_last) + 1, p.Hi - 1) - g.py0 + 1;
-        g.pw = min((int)(sx * (float)ox_last) + 1, p.Wi - 1) - g.px0 + 1;  // <= PS (launcher's scale check)
-        return g;
-    };
     // source patch of stage st (64 channels, hi and lo plane) global -> LDS by LDS-DMA: 1 KiB = 8 pixels per wave instruction
     auto issue_patch = [&](const TileGeom& g, int st) {
         int lane_o = lane;
@@ -419,17 +394,27 @@ __global__ __launch_bounds__(512, 1) void head_tail2_kernel(const HeadTailParams
         }
     };
 
+    // tile -> image, origin and the source patch its halo interpolates from (halo rows / columns outside the image are zero padding)
+    // (written out in both kernels, not through mdpt_up_patch(.., halo = 1) of up_bf16.h: as a shared function the kernels' instruction streams change)
+    auto geom = [&](int tile) {
+        TileGeom g;
+        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y;
+        g.b = tile / (tiles_x * tiles_y);
+        g.oy0 = ty * TS; g.ox0 = tx * TS;
+        const int oy_first = g.oy0 == 0 ? 0 : g.oy0 - 1, ox_first = g.ox0 == 0 ? 0 : g.ox0 - 1;
+        const int oy_last = min(g.oy0 + TS, p.Ho - 1), ox_last = min(g.ox0 + TS, p.Wo - 1);
+        g.py0 = (int)(sy * (float)oy_first); g.px0 = (int)(sx * (float)ox_first);
+        g.ph = min((int)(sy * (float)oy_last) + 1, p.Hi - 1) - g.py0 + 1;
+        g.pw = min((int)(sx * (float)ox_last) + 1, p.Wi - 1) - g.px0 + 1;  // <= PS (launcher's scale check)
+        return g;
+    };
     int tile = blockIdx.x;
     TileGeom g = geom(tile < ntiles ? tile : 0);
     if (tile < ntiles) issue_patch(g, 0);
 
     int tile_no = 0;
-    auto stamp = [&](int slot) {  // test hook (MDPT_HEAD_DBG builds): phase stamps of every workgroup's second tile
-        if (p.dbg_times && tile_no == 1 && tid == 0) {
-            unsigned long long t;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-            p.dbg_times[(size_t)blockIdx.x * 8 + slot] = t;
-        }
+    auto stamp = [&](int slot) {  // test hook (MDPT_HEAD_DBG builds): phase stamps of every workgroup's second tile (a lambda per kernel: as a shared function the streams change)
+        if (p.dbg_times && tile_no == 1 && tid == 0) p.dbg_times[(size_t)blockIdx.x * 8 + slot] = memtime_now();
     };
     for (; tile < ntiles; tile += gridDim.x, ++tile_no) {
         stamp(0);
@@ -540,7 +525,6 @@ __global__ __launch_bounds__(512, 1) void head_tail2_kernel(const HeadTailParams
                     // (in two 8-byte halves: the 144 weight registers + 32 accumulators leave ~70 VGPRs for this phase)
 #pragma unroll
                     for (int hw = 0; hw < 2; ++hw) {
-                        typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
                         u32x2 v[2][4];
 #pragma unroll
                         for (int pl = 0; pl < 2; ++pl) {
@@ -651,87 +635,64 @@ __global__ __launch_bounds__(512, 1) void head_tail2_kernel(const HeadTailParams
     }
 }
 
+#ifdef MDPT_DEBUG_SWITCHES  // A/B builds only (a release build reads no environment variable on the launch path)
+// MDPT_HEAD_DBG hook of both launchers (allocates and synchronises): run the launch with a stamp buffer and print the mean cycles of the NPH
+// phases between the stamps 0 .. NPH of every workgroup's second tile. Returns false when the hook is off.
+template <typename Kern, int NPH>
+bool head_debug_launch(Kern kern, const char* name, int cin, const char* const (&labels)[NPH], int grid, unsigned lds, const HeadTailParams& p, hipStream_t stream, int& err) {
+    static const bool dbg_on = getenv("MDPT_HEAD_DBG") != nullptr;
+    if (!dbg_on) return false;
+    static unsigned long long* dbuf = nullptr;
+    static unsigned long long host[256 * 8];
+    if (!dbuf && hipMalloc((void**)&dbuf, sizeof(host)) != hipSuccess) { err = (int)hipErrorOutOfMemory; return true; }
+    (void)hipMemsetAsync(dbuf, 0, sizeof(host), stream);
+    HeadTailParams q = p;
+    q.dbg_times = dbuf;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, q);
+    (void)hipStreamSynchronize(stream);
+    (void)hipMemcpy(host, dbuf, sizeof(host), hipMemcpyDeviceToHost);
+    double d[NPH] = {};
+    int n = 0;
+    for (int w = 0; w < grid; ++w)
+        if (host[w * 8 + NPH] > host[w * 8]) { for (int k = 0; k < NPH; ++k) d[k] += (double)(host[w * 8 + k + 1] - host[w * 8 + k]); ++n; }
+    if (n) {
+        fprintf(stderr, "%s<%d> phases (cycles, mean of %d workgroups' 2nd tile):", name, cin, n);
+        for (int k = 0; k < NPH; ++k) fprintf(stderr, "%s %s %.0f", k ? " |" : "", labels[k], d[k] / n);
+        fprintf(stderr, "\n");
+    }
+    err = (int)hipGetLastError();
+    return true;
+}
+#endif
+
+// one launch of either kernel: persistent workgroups (the weights are loaded into registers once per workgroup)
+template <auto Kern, int NPH>
+int launch_tail(const char* name, int cin, unsigned lds, const char* const (&phases)[NPH], const HeadTailParams& p, hipStream_t stream) {
+    if (const int e = mdpt_lds_limit<Kern>(lds)) return e;
+    const int ntiles = p.B * ((p.Ho + TS - 1) / TS) * ((p.Wo + TS - 1) / TS);
+    const int grid = ntiles < 256 ? ntiles : 256;
+    MdptProfScope prof(mdpt_kernel_label<Kern>("%s_kernel<%d>", name, cin), 2.0 * p.B * p.Ho * p.Wo * 32.0 * 9.0 * cin, stream);  // algorithmic flops (one pass)
+#ifdef MDPT_DEBUG_SWITCHES
+    int err = 0;
+    if (head_debug_launch(Kern, name, cin, phases, grid, lds, p, stream, err)) return err;
+#endif
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(512), lds, stream, p);
+    return (int)hipGetLastError();
+}
+
 template <int CIN>
 int launch_cin2(const HeadTailParams& p, hipStream_t stream) {
     constexpr unsigned ROWB2 = ((HS * (64 * 2 + 16) + 255) / 256) * 256;
     constexpr unsigned LDS = 2 * HS * ROWB2 + 2 * PS * PS * 128 + 2 * HS * 16 + 256;  // halo planes, patch planes, tables, epilogue constants
-    auto kern = head_tail2_kernel<CIN>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    const int ntiles = p.B * ((p.Ho + TS - 1) / TS) * ((p.Wo + TS - 1) / TS);
-    const int grid = ntiles < 256 ? ntiles : 256;
-    static char prof_name[48] = "";
-    if (!prof_name[0]) snprintf(prof_name, sizeof(prof_name), "head_tail2_kernel<%d>", CIN);
-    MdptProfScope prof(prof_name, 2.0 * p.B * p.Ho * p.Wo * 32.0 * 9.0 * CIN, stream);  // algorithmic flops (one pass)
-#ifdef MDPT_DEBUG_SWITCHES  // A/B builds only
-    static const bool dbg_on = getenv("MDPT_HEAD_DBG") != nullptr;
-    if (dbg_on) {  // debug hook only (allocates and synchronises): phase stamps of every workgroup's second tile
-        static unsigned long long* dbuf = nullptr;
-        if (!dbuf && hipMalloc((void**)&dbuf, 256 * 8 * sizeof(unsigned long long)) != hipSuccess) return (int)hipErrorOutOfMemory;
-        (void)hipMemsetAsync(dbuf, 0, 256 * 8 * sizeof(unsigned long long), stream);
-        HeadTailParams q = p;
-        q.dbg_times = dbuf;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, stream, q);
-        (void)hipStreamSynchronize(stream);
-        static unsigned long long host[256 * 8];
-        (void)hipMemcpy(host, dbuf, sizeof(host), hipMemcpyDeviceToHost);
-        double d[7] = {0, 0, 0, 0, 0, 0, 0};
-        int n = 0;
-        for (int w = 0; w < grid; ++w)
-            if (host[w * 8 + 7] > host[w * 8]) { for (int k = 0; k < 7; ++k) d[k] += (double)(host[w * 8 + k + 1] - host[w * 8 + k]); ++n; }
-        if (n) fprintf(stderr, "head_tail2<%d> phases (cycles, mean of %d workgroups' 2nd tile): tables+patch wait %.0f | halo 0 %.0f | mfma 0 %.0f | patch wait 1 %.0f | halo 1 %.0f | mfma 1 %.0f | exchange + epilogue %.0f\n",
-                       CIN, n, d[0] / n, d[1] / n, d[2] / n, d[3] / n, d[4] / n, d[5] / n, d[6] / n);
-        return (int)hipGetLastError();
-    }
-#endif
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, stream, p);
-    return (int)hipGetLastError();
+    static const char* const phases[7] = {"tables+patch wait", "halo 0", "mfma 0", "patch wait 1", "halo 1", "mfma 1", "exchange + epilogue"};
+    return launch_tail<head_tail2_kernel<CIN>>("head_tail2", CIN, LDS, phases, p, stream);
 }
 
 template <int CIN>
 int launch_cin(const HeadTailParams& p, hipStream_t stream) {
     constexpr unsigned LDS = HS * (((HS * (CIN * 2 + 16) + 255) / 256) * 256) + PS * PS * CIN * 2 + 8 * 16 * 64 * 4 + 2 * HS * 16 + 256;  // halo, patch, exchange, tables, epilogue constants
-    auto kern = head_tail_kernel<CIN>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    const int ntiles = p.B * ((p.Ho + TS - 1) / TS) * ((p.Wo + TS - 1) / TS);
-    const int grid = ntiles < 256 ? ntiles : 256;  // persistent: the weights are loaded into registers once per workgroup
-    static char prof_name[48] = "";
-    if (!prof_name[0]) snprintf(prof_name, sizeof(prof_name), "head_tail_kernel<%d>", CIN);
-    MdptProfScope prof(prof_name, 2.0 * p.B * p.Ho * p.Wo * 32.0 * 9.0 * CIN, stream);
-#ifdef MDPT_DEBUG_SWITCHES  // A/B builds only
-    static const bool dbg_on = getenv("MDPT_HEAD_DBG") != nullptr;
-#else
-    constexpr bool dbg_on = false;
-#endif
-    if (dbg_on) {  // debug hook only (allocates and synchronises): phase stamps of every workgroup's second tile
-        static unsigned long long* dbuf = nullptr;
-        if (!dbuf) hipMalloc((void**)&dbuf, 256 * 8 * sizeof(unsigned long long));
-        hipMemsetAsync(dbuf, 0, 256 * 8 * sizeof(unsigned long long), stream);
-        HeadTailParams q = p;
-        q.dbg_times = dbuf;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, stream, q);
-        hipStreamSynchronize(stream);
-        static unsigned long long host[256 * 8];
-        hipMemcpy(host, dbuf, sizeof(host), hipMemcpyDeviceToHost);
-        double d[5] = {0, 0, 0, 0, 0};
-        int n = 0;
-        for (int w = 0; w < grid; ++w)
-            if (host[w * 8 + 5] > host[w * 8]) { for (int k = 0; k < 5; ++k) d[k] += (double)(host[w * 8 + k + 1] - host[w * 8 + k]); ++n; }
-        if (n) fprintf(stderr, "head_tail<%d> phases (cycles, mean of %d workgroups' 2nd tile): tables+patch wait %.0f | halo %.0f | mfma %.0f | exchange wait %.0f | epilogue %.0f\n",
-                       CIN, n, d[0] / n, d[1] / n, d[2] / n, d[3] / n, d[4] / n);
-        return (int)hipGetLastError();
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, stream, p);
-    return (int)hipGetLastError();
+    static const char* const phases[5] = {"tables+patch wait", "halo", "mfma", "exchange wait", "epilogue"};
+    return launch_tail<head_tail_kernel<CIN>>("head_tail", CIN, LDS, phases, p, stream);
 }
 
 }  // namespace

@@ -85,6 +85,9 @@ struct GemmParams {
     int ks_all;  // 1: EVERY range (z = 0 too) stores its bare partial sums, plane z at ks_part + z * M * ldc, and nothing else is written: a finishing
                  // kernel (mdpt_launch_ksplit_finish) adds the planes in the order z = 0, 1, ... and applies bias / ReLU / the output planes.
                  // Dense rows or 3x3-conv rows, 64x64 tile. Latency mode: the long-K convs of the 18^2 / 36^2 levels at batch 1.
+    // test hook: six 64-bit slots per workgroup, written by stamp_record (mfma_common.inc): clock stamps [start, first barrier, loop done, stores
+    // acknowledged], then by epilogue  LDS strip (both kernels): [XCC id, HW_REG_HW_ID];  direct: [stores issued, HW_REG_HW_ID];
+    // transposed V: [stores acknowledged again, 0]
     unsigned long long* dbg_times;
 };
 
@@ -115,7 +118,7 @@ struct Conv3hParams {
     int f8; size_t a8_off;
     const unsigned char* w8; const unsigned char* w8_lo; const unsigned char* s8; const unsigned char* s8_lo;
     size_t out_f8; int out_a8;
-    unsigned long long* dbg_times;  // test hook: per-workgroup s_memtime stamps [start, first barrier, loop done, stores acknowledged, stores issued, XCC id]
+    unsigned long long* dbg_times;  // test hook: the six-slot record of GemmParams::dbg_times in the layout [start, first barrier, loop done, stores acknowledged, stores issued, XCC id]
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -325,12 +325,7 @@ int MDPT_FN(mdpt_launch_swin_qkv_prep)(const float* qkv, const int* rowmap, cons
     MdptProfScope prof("swin_v_prep", 0.0, stream);  // by hand: the scope opens before the argument check, as it always has
     const size_t v_lds = (size_t)(vt_lo ? 2 : 1) * 32 * (npadv + 8) * 2;
     if (v_lds > 160 * 1024 || (npadv & 63)) return (int)hipErrorInvalidValue;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)swin_v_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    if (const int e = mdpt_lds_limit<swin_v_prep_kernel>(160 * 1024)) return e;
     return ew_launch(swin_v_prep_kernel, dim3((unsigned)((size_t)B * nw * heads)), dim3(256), v_lds, stream, qkv, rowmap, vt_hi, vt_lo, B, N, nw, wa, npadv, heads);
 }
 

@@ -25,3 +25,19 @@ __device__ __forceinline__ mdpt_u32x4 mdpt_up_bf16x8(mdpt_u32x4 v00, mdpt_u32x4 
     }
     return out;
 }
+
+// Source patch of a 16x16 output tile at (oy0, ox0) of an align_corners upsample (scales sy, sx = (source - 1) / (output - 1)): the source
+// pixels that the tile's output rows oy0 - halo .. oy0 + 15 + halo (clipped to the map; columns alike) interpolate from - first row /
+// column and extent. halo = 1: the tile with the one-pixel border a 3x3 conv reads; halo = 0: the tile itself.
+struct mdpt_up_patch_t {
+    int py0, px0, ph, pw;
+};
+__device__ __forceinline__ mdpt_up_patch_t mdpt_up_patch(float sy, float sx, int oy0, int ox0, int halo, int Ho, int Wo, int Hs, int Ws) {
+    mdpt_up_patch_t g;
+    const int oy_first = oy0 == 0 ? 0 : oy0 - halo, ox_first = ox0 == 0 ? 0 : ox0 - halo;
+    const int oy_last = min(oy0 + 15 + halo, Ho - 1), ox_last = min(ox0 + 15 + halo, Wo - 1);
+    g.py0 = (int)(sy * (float)oy_first); g.px0 = (int)(sx * (float)ox_first);
+    g.ph = min((int)(sy * (float)oy_last) + 1, Hs - 1) - g.py0 + 1;
+    g.pw = min((int)(sx * (float)ox_last) + 1, Ws - 1) - g.px0 + 1;
+    return g;
+}

@@ -31,14 +31,30 @@ def _kernel_stats(src, tmp_path, extra=()):
     return stats
 
 
+# The instantiations that spill, by mangled template arguments <NQN, NP, SKIP, F32OUT, RELU, UP, BFOUT, UPIN, F8>, with the scratch bytes per lane
+# read from the ISA of the commit that added conv3h.hip to this guard (an open item of DESIGN.md, not a budget: none may grow, no other may spill).
+# Both are three-pass 256-channel forms with the skip add: conv3h_kernel<2, 3, true, true, true, true, true> and <2, 3, true, false, false, false, true>.
+KNOWN_SPILLS = {
+    ("conv3h.hip", "bf16"): {"conv3h_kernelILi2ELi3ELb1ELb1ELb1ELb1ELb1ELb0ELb0EE": 16, "conv3h_kernelILi2ELi3ELb1ELb0ELb0ELb0ELb1ELb0ELb0EE": 8},
+    ("conv3h.hip", "fp16"): {"conv3h_kernelILi2ELi3ELb1ELb1ELb1ELb1ELb1ELb0ELb0EE": 16, "conv3h_kernelILi2ELi3ELb1ELb0ELb0ELb0ELb1ELb0ELb0EE": 16},
+}
+
+
 @pytest.mark.parametrize("operands", ["bf16", "fp16"])  # every kernel file exists once per MFMA operand format (csrc/op_types.h)
 @pytest.mark.parametrize("src,pattern,at_least", [("gemm.hip", "gemm8_kernel", 6), ("attention.hip", "attn_kernel", 6),
-                                                  ("head.hip", "head_tail_kernel", 2)])
+                                                  ("head.hip", "head_tail_kernel", 2), ("conv3h.hip", "conv3h_kernel", 19)])
 def test_hot_kernels_do_not_spill(tmp_path, src, pattern, at_least, operands):
     extra = ("-DMDPT_OP_F16",) if operands == "fp16" else ()
     stats = {k: v for k, v in _kernel_stats(src, tmp_path, extra).items() if pattern in k}
     assert len(stats) >= at_least, sorted(stats)
+    known = KNOWN_SPILLS.get((src, operands), {})
+    assert all(any(k in name for name in stats) for k in known), "a named exception no longer exists: remove it"
     for name, s in stats.items():
+        allowed = max([b for k, b in known.items() if k in name], default=0)
+        if allowed:
+            assert s["ScratchSize"] <= allowed, f"{name} spills {s['ScratchSize']} bytes of scratch per lane, {allowed} when it was recorded"
+            assert s["NumVgprs"] <= 256
+            continue
         # (incl. the fp8 cross-term forms gemm8_kernel<..., true>, MDPT_PASSES_2F8 / _3F8: with four weight pointers instead of one they reloaded spilled
         #  pointer pairs inside the fp16 loop - a vmcnt(0) each, 370 us against 310 us for three fp16 passes on the 36x36 fusion convs)
         assert s["ScratchSize"] == 0, f"{name} spills {s['ScratchSize']} bytes of scratch per lane ({s['NumVgprs']} VGPRs)"
