@@ -725,6 +725,48 @@ int mdpt_post_video_display(const void* stable_f32, int32_t T, int32_t h, int32_
                             int32_t out_h, int32_t out_w, int32_t reverse, const void* cmap_bgr, double range_rate, void* out_bgr, void* ranges_f32,
                             void* range_out_f32, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Synthetic depth of field on the device (additive to ABI v6; not in the reference): a photo refocused by its depth map ("portrait mode"). A focal
+ * plane is put where the caller says; every photo pixel gets a blur radius from its signed defocus; the blur varies per pixel and is occlusion-aware
+ * (a sharp foreground is not smeared by the blurred background behind it, a blurred foreground spreads over what is behind it). n pairs of any sizes
+ * in one call, four launches whatever n is, nothing read back, nothing synchronises, no atomics, bit-deterministic, every pair independent of the
+ * others. A pair is an mdpt_refocus_pair record: the h x w map (dtype), the uint8 BGR photo of H x W pixels (any size relative to the map) whose rows
+ * start `pitch` bytes apart (pitch >= 3 W; no alignment is asked: the photo is read byte by byte, in place), the packed uint8 H x W x 3 output (NULL
+ * in EVERY record: the preparation alone, for radius_out / defocus_out), scratch_off, the byte offset of the pair's own scratch inside `scratch` (a
+ * multiple of 8; the pair needs mdpt_post_refocus_scratch_bytes of its record alone from there: 1024 bytes and 8 per photo pixel; regions must not
+ * overlap), and tile_off = the sum over the pairs before it of ceil(H / 32) ceil(W / 32) (MDPT_REFOCUS_TILE = 32). The table is passed twice:
+ * records_dev in DEVICE memory (8-byte aligned), records_host the same records on the host, read during the call for the argument checks only.
+ * All arithmetic is fp64, nothing contracted:
+ *   map ........... s(Y, X) = the map at the centre of photo pixel (Y, X): bilinear at u = (X + 0.5) w / W - 0.5 clamped to the grid, fp64 weights, rows
+ *                   first (the resampler of mdpt_post_align_* and mdpt_post_guided_upsample); a map of the photo's size is read directly.
+ *   defocus ....... space MDPT_ALIGN_INVERSE (relative models: the map is affine in 1 / depth): lo, hi = the fp32 min / max of the map's finite values
+ *                   (a zero of either sign counts as +0), e = (s - lo) / (hi - lo) - focus, focus in [0, 1]. MDPT_ALIGN_DEPTH (metric maps):
+ *                   u = 1 / s for s > 0, u = 0 for a finite s <= 0 (infinitely far), e = u - 1 / focus, focus a depth > 0. e > 0: nearer than the
+ *                   focal plane. focus_xy != NULL ((x, y) in [0, 1]^2, host memory): focus is replaced by the value at photo pixel
+ *                   (min(H - 1, floor(y H)), min(W - 1, floor(x W))) - (s - lo) / (hi - lo) there, or s there - read on the device, so e = 0 at it.
+ *                   e = 0 where s is not finite (NaN or +-inf, in either space); e = 0 for every pixel of a pair whose map is flat or has no finite
+ *                   value (inverse space), or whose pointed s is not finite or, in depth space, not > 0: that photo comes back byte for byte.
+ *                   e32 = e rounded once to fp32.
+ *   radius ........ r = min(max_radius, aperture max(0, |e| - focus_range / 2)) from the fp64 e; aperture = photo pixels per unit of e; quantised
+ *                   to quarter pixels, rq = floor(4 r), 0 <= rq <= 4 max_radius <= 128. The footprint of a pixel is the lattice disc
+ *                   {d : dx^2 + dy^2 <= k}, k = (rq rq) >> 4, its weight 1 / N(k), N(k) = the lattice points of that disc (1, 5, 9, 9, 13, ...).
+ *   gather ........ for output pixel p over the taps q = p + (dy, dx) inside the photo, dy outer, dx inner, both ascending:
+ *                   k_eff = k(q) if e32(q) > e32(p), else min(k(q), k(p)); where dx^2 + dy^2 <= k_eff the tap adds w B, w G, w R, w with
+ *                   w = 1.0 / N(k_eff) to four fp64 sums, product then add; any other tap adds nothing. out_c = (uint8) floor(sum_c / sum_w + 0.5).
+ * radius_out (or NULL): every pair's rq plane, uint8 [H, W], end to end in pair order; defocus_out (or NULL, 4-byte aligned): the e32 planes alike.
+ * Checks (MDPT_E_INVALID, nothing launched, the message names the argument): null pointers, n outside 1 .. 65535, max_radius outside 0 ..
+ * MDPT_REFOCUS_MAX_RADIUS, aperture or focus_range negative or not finite, focus outside its domain (without focus_xy) or focus_xy outside
+ * [0, 1]^2, sizes <= 0, H W or h w >= 2^31, pitch < 3 W, a wrong tile_off, misaligned map / table / scratch, a scratch region outside scratch_bytes
+ * or overlapping another, outputs in some records only. mdpt_post_refocus_scratch_bytes reads only H and W: the bytes of n regions laid end to end.
+ * Known limits: what a blurred foreground edge uncovers is not inpainted; the disc is hard-edged (no bokeh shapes, no highlight boost); the average
+ * is taken on the gamma-encoded bytes. */
+#define MDPT_REFOCUS_MAX_RADIUS 32
+#define MDPT_REFOCUS_TILE 32
+typedef struct mdpt_refocus_pair { const void* map; int32_t h, w; const void* photo; int64_t pitch; int32_t H, W; void* out; int64_t scratch_off, tile_off; } mdpt_refocus_pair;
+int mdpt_post_refocus_scratch_bytes(const mdpt_refocus_pair* records_host, int32_t n, int32_t max_radius, size_t* bytes);
+int mdpt_post_refocus(const mdpt_refocus_pair* records_host, const void* records_dev, int32_t n, int32_t dtype, int32_t space, double focus,
+                      const double* focus_xy, double aperture, double focus_range, int32_t max_radius, void* scratch, size_t scratch_bytes, void* radius_out,
+                      void* defocus_out, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

@@ -424,6 +424,32 @@ int mdpt_launch_post_video_display(const float* stable, int T, int h, int w, int
                                    double rho, int reverse, const unsigned char* cmap, float* scaled, unsigned* parts, unsigned* rparts, unsigned char* u8,
                                    unsigned char* out, float* ranges, float* range_out, hipStream_t stream);
 
+// synthetic depth of field (post_refocus.inc; a pair = mdpt_refocus_pair of include/mdpt.h): the h x w map (the table's dtype), the uint8 BGR photo of
+// H x W pixels whose rows lie `pitch` bytes apart (any alignment), the packed uint8 H x W x 3 output (null in every record: the preparation alone),
+// where the pair's scratch starts (bytes from the call's scratch pointer, a multiple of 8) and the number of 32 x 32 output tiles of the pairs before
+// it. Device table, indexed by pair. A pair's scratch: REFOCUS_HEADER_BYTES ({min, max} partials of the map as ordered keys, then RefocusState),
+// then 8 bytes per photo pixel: B | G << 8 | R << 16 | rq << 24 and the fp32 bits of the signed defocus.
+struct RefocusPair { const void* map; int h, w; const unsigned char* photo; long long pitch; int H, W; unsigned char* out; long long scratch_off, tile_off; };
+#define REFOCUS_MAX_RADIUS 32
+#define REFOCUS_TILE 32    // output pixels of one gather workgroup along each axis (one thread each)
+#define REFOCUS_PARTS 64   // workgroups that share the min / max of one map
+#define REFOCUS_HEADER_BYTES 1024
+inline size_t refocus_pair_scratch_bytes(size_t H, size_t W) { return REFOCUS_HEADER_BYTES + H * W * 8; }
+inline size_t refocus_pair_tiles(size_t H, size_t W) { return ((H + REFOCUS_TILE - 1) / REFOCUS_TILE) * ((W + REFOCUS_TILE - 1) / REFOCUS_TILE); }
+// one call: `focus` is the focal value (inverse space: 0 .. 1 of the map's own range; depth space: 1 / the focal depth) unless pointed, when it is read
+// at the photo pixel under (fx, fy) on the device; half_range = focus_range / 2. radius_out / defocus_out (null: not wanted): every pair's rq and e32
+// planes end to end in pair order. gather == 0: the preparation alone. Three launches and the gather whatever P is. Bit-deterministic, no atomics.
+struct RefocusJob {
+    const RefocusPair* pairs;
+    int P, dt, depth_space, pointed, max_radius, gather;
+    double focus, fx, fy, aperture, half_range;
+    char* scratch;
+    unsigned char* radius_out;
+    float* defocus_out;
+    size_t max_pixels, total_tiles;
+};
+int mdpt_launch_post_refocus(const RefocusJob& job, hipStream_t stream);
+
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);
 

@@ -777,4 +777,90 @@ int mdpt_post_video_display(const void* stable_f32, int32_t T, int32_t h, int32_
     return 0;
 }
 
+// ---- synthetic depth of field (per-pixel defocus, occlusion-aware gather; not in the reference)
+static_assert(sizeof(mdpt_refocus_pair) == sizeof(RefocusPair) && sizeof(mdpt_refocus_pair) == 64, "mdpt_refocus_pair of include/mdpt.h is RefocusPair of mdpt_kernels.h");
+static_assert(offsetof(mdpt_refocus_pair, photo) == offsetof(RefocusPair, photo) && offsetof(mdpt_refocus_pair, pitch) == offsetof(RefocusPair, pitch) &&
+              offsetof(mdpt_refocus_pair, H) == offsetof(RefocusPair, H) && offsetof(mdpt_refocus_pair, out) == offsetof(RefocusPair, out) &&
+              offsetof(mdpt_refocus_pair, scratch_off) == offsetof(RefocusPair, scratch_off) && offsetof(mdpt_refocus_pair, tile_off) == 56 &&
+              offsetof(RefocusPair, tile_off) == 56, "mdpt_refocus_pair of include/mdpt.h is RefocusPair of mdpt_kernels.h, field by field");
+static_assert(MDPT_REFOCUS_MAX_RADIUS == REFOCUS_MAX_RADIUS && MDPT_REFOCUS_TILE == REFOCUS_TILE, "the refocus limits of include/mdpt.h are those of mdpt_kernels.h");
+
+// the host table's photo sizes: positive, H W < 2^31; *bytes = the scratch of the P regions laid end to end
+static int check_refocus_sizes(const mdpt_refocus_pair* pairs, int32_t P, int32_t max_radius, size_t* bytes) {
+    if (!pairs) return fail(MDPT_E_INVALID, "null argument (records)");
+    if (P <= 0 || P > 65535) return fail(MDPT_E_INVALID, "bad pair count n = %d (1 .. 65535 per call)", P);
+    if (max_radius < 0 || max_radius > REFOCUS_MAX_RADIUS) return fail(MDPT_E_INVALID, "max_radius %d: the blur radius limit must be 0 .. %d pixels", max_radius, REFOCUS_MAX_RADIUS);
+    size_t total = 0;
+    for (int p = 0; p < P; ++p) {
+        const mdpt_refocus_pair& q = pairs[p];
+        if (q.H <= 0 || q.W <= 0) return fail(MDPT_E_INVALID, "bad photo size %dx%d (pair %d)", q.H, q.W, p);
+        if ((size_t)q.H * q.W >= ((size_t)1 << 31)) return fail(MDPT_E_INVALID, "a photo of %dx%d is too large (H W < 2^31 pixels, pair %d)", q.H, q.W, p);
+        total += refocus_pair_scratch_bytes((size_t)q.H, (size_t)q.W);
+    }
+    *bytes = total;
+    return 0;
+}
+
+int mdpt_post_refocus_scratch_bytes(const mdpt_refocus_pair* records_host, int32_t n, int32_t max_radius, size_t* bytes) {
+    if (!bytes) return fail(MDPT_E_INVALID, "null argument (bytes)");
+    return check_refocus_sizes(records_host, n, max_radius, bytes);
+}
+
+int mdpt_post_refocus(const mdpt_refocus_pair* records_host, const void* records_dev, int32_t n, int32_t dtype, int32_t space, double focus,
+                      const double* focus_xy, double aperture, double focus_range, int32_t max_radius, void* scratch, size_t scratch_bytes, void* radius_out,
+                      void* defocus_out, void* stream) {
+    if (!records_host || !records_dev || !scratch) return fail(MDPT_E_INVALID, "null argument (records_host, records_dev or scratch)");
+    if (!tensor_dtype_ok(dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dtype);
+    if (space != MDPT_ALIGN_INVERSE && space != MDPT_ALIGN_DEPTH) return fail(MDPT_E_INVALID, "unknown refocus space %d", space);
+    size_t packed;
+    CHK(check_refocus_sizes(records_host, n, max_radius, &packed));
+    if (!(aperture >= 0.0) || aperture > 1e300) return fail(MDPT_E_INVALID, "aperture must be finite and >= 0 (pixels per unit of defocus), got %g", aperture);
+    if (!(focus_range >= 0.0) || focus_range > 1e300) return fail(MDPT_E_INVALID, "focus_range must be finite and >= 0, got %g", focus_range);
+    if (focus_xy) {
+        if (!(focus_xy[0] >= 0.0 && focus_xy[0] <= 1.0 && focus_xy[1] >= 0.0 && focus_xy[1] <= 1.0))
+            return fail(MDPT_E_INVALID, "focus_xy must lie in [0, 1]^2, got (%g, %g)", focus_xy[0], focus_xy[1]);
+    } else if (space == MDPT_ALIGN_INVERSE ? !(focus >= 0.0 && focus <= 1.0) : (!(focus > 0.0) || focus > 1e300)) {
+        return fail(MDPT_E_INVALID, "focus %g is outside its domain (inverse space: 0 .. 1 of the map's range; depth space: a finite depth > 0)", focus);
+    }
+    if ((((uintptr_t)records_dev | (uintptr_t)scratch) & 7) != 0 || ((uintptr_t)defocus_out & 3) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table and the scratch need 8 bytes, defocus_out 4)");
+    size_t max_pixels = 0, tiles = 0;
+    int with_out = 0;
+    std::vector<std::pair<size_t, size_t>> regions;
+    for (int p = 0; p < n; ++p) {
+        const mdpt_refocus_pair& q = records_host[p];
+        if (!q.map || !q.photo) return fail(MDPT_E_INVALID, "null map or photo (pair %d)", p);
+        if (((uintptr_t)q.map & (dtype_bytes(dtype) - 1)) != 0) return fail(MDPT_E_INVALID, "misaligned map (pair %d: it needs its element)", p);
+        if (q.h <= 0 || q.w <= 0 || (size_t)q.h * q.w >= ((size_t)1 << 31)) return fail(MDPT_E_INVALID, "bad map size %dx%d (pair %d; h w < 2^31)", q.h, q.w, p);
+        if (q.pitch < 3 * (int64_t)q.W) return fail(MDPT_E_INVALID, "a row pitch of %lld bytes is less than the %d pixels of a row (pair %d)", (long long)q.pitch, q.W, p);
+        const size_t px = (size_t)q.H * q.W, need = refocus_pair_scratch_bytes((size_t)q.H, (size_t)q.W);
+        if (q.scratch_off < 0 || (q.scratch_off & 7) != 0 || (size_t)q.scratch_off > scratch_bytes || scratch_bytes - (size_t)q.scratch_off < need)
+            return fail(MDPT_E_INVALID, "the scratch region of pair %d (offset %lld, %zu bytes) is misaligned or outside the %zu bytes of scratch given "
+                        "(mdpt_post_refocus_scratch_bytes)", p, (long long)q.scratch_off, need, scratch_bytes);
+        if (q.tile_off != (int64_t)tiles)
+            return fail(MDPT_E_INVALID, "tile_off %lld of pair %d is not the %zu tiles of %dx%d pixels of the pairs before it", (long long)q.tile_off, p, tiles,
+                        REFOCUS_TILE, REFOCUS_TILE);
+        regions.emplace_back((size_t)q.scratch_off, (size_t)q.scratch_off + need);
+        tiles += refocus_pair_tiles((size_t)q.H, (size_t)q.W);
+        max_pixels = px > max_pixels ? px : max_pixels;
+        with_out += q.out != nullptr;
+    }
+    if (with_out != 0 && with_out != n) return fail(MDPT_E_INVALID, "out is null in %d of %d records: every pair has an output, or none (the preparation alone)", n - with_out, n);
+    if (!with_out && !radius_out && !defocus_out) return fail(MDPT_E_INVALID, "null argument: no record has an output and neither radius_out nor defocus_out is given");
+    if (tiles >= ((size_t)1 << 31)) return fail(MDPT_E_INVALID, "%zu tiles: a call takes fewer than 2^31", tiles);
+    std::sort(regions.begin(), regions.end());
+    for (size_t k = 1; k < regions.size(); ++k)
+        if (regions[k].first < regions[k - 1].second) return fail(MDPT_E_INVALID, "the scratch regions of two pairs overlap (at byte %zu)", regions[k].first);
+    RefocusJob j{};
+    j.pairs = (const RefocusPair*)records_dev;
+    j.P = n, j.dt = dtype, j.depth_space = space == MDPT_ALIGN_DEPTH, j.pointed = focus_xy != nullptr, j.max_radius = max_radius, j.gather = with_out != 0;
+    j.focus = focus_xy ? 0.0 : (j.depth_space ? 1.0 / focus : focus);
+    j.fx = focus_xy ? focus_xy[0] : 0.0, j.fy = focus_xy ? focus_xy[1] : 0.0;
+    j.aperture = aperture, j.half_range = focus_range / 2.0;
+    j.scratch = (char*)scratch, j.radius_out = (unsigned char*)radius_out, j.defocus_out = (float*)defocus_out;
+    j.max_pixels = max_pixels, j.total_tiles = tiles;
+    CHK(mdpt_launch_post_refocus(j, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

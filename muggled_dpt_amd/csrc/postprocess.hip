@@ -16,3 +16,4 @@
 #include "post_render.inc"   // rendering of depth meshes
 #include "post_fill.inc"     // hole filling of rendered views
 #include "post_video.inc"    // temporally stable video depth: frame-to-frame fit, temporal filter, carried display range
+#include "post_refocus.inc"  // synthetic depth of field: per-pixel defocus, occlusion-aware LDS-tiled gather

@@ -1093,6 +1093,23 @@ class DPTModel(nn.Module):
         preds = self.inference_images(images_bgr, max_side_length, use_square_sizing, batch_size)
         return guided_upsample_images(preds, list(images_bgr), radius, eps)
 
+    def inference_refocus(self, images_bgr, focus: float = 0.5, focus_xy=None, aperture: float | None = None, max_radius: int = 16, focus_range: float = 0.0,
+                          space: str | None = None, guided=None, max_side_length: int | None = None, use_square_sizing: bool = True,
+                          batch_size: int = 32) -> list[Tensor]:
+        """Every photo refocused by its own predicted depth ("portrait mode") -> a list of uint8 [H_i,W_i,3] BGR device tensors in input order (not in
+        the reference): one inference_images call, with guided = (radius, eps) one postprocess.guided_upsample_images call that puts the depth
+        edges where the photo has them, then one refocus.refocus_images call; nothing is read back. images_bgr as inference_images takes them.
+        focus / focus_xy / aperture / max_radius / focus_range are refocus_images' (aperture None: its default); space None: "depth" for a metric
+        model (config is_metric), "inverse" for every other."""
+        from .postprocess import guided_upsample_images
+        from .refocus import REFOCUS_APERTURE, refocus_images
+        if space is None:
+            space = "depth" if self.config.get("is_metric", False) else "inverse"
+        preds = self.inference_images(images_bgr, max_side_length, use_square_sizing, batch_size)
+        if guided is not None:
+            preds = guided_upsample_images(preds, list(images_bgr), int(guided[0]), float(guided[1]))
+        return refocus_images(preds, list(images_bgr), focus, focus_xy, REFOCUS_APERTURE if aperture is None else aperture, max_radius, focus_range, space)
+
     def render_views(self, image_bgr: np.ndarray, view_proj=None, out_wh=(1280, 720), max_side_length: int | None = None,
                      use_square_sizing: bool = True, fov_deg: float | None = None, min_depth: float | None = None, max_depth: float | None = None,
                      edge_threshold: float | None = None, target_num_faces=None, mode: str = "triangles", cull: str = "back", point_size: float = 2.0,

@@ -21,6 +21,10 @@ neighbours have in common): <name>_tiled.npy, fp32 [H, W], in the current direct
 For one image or several, --guided RADIUS EPS saves the depth at the PHOTO's resolution with the photo as the guide of the enlargement
 (postprocess.guided_upsample_images, one call for the whole list; RADIUS in cells of the model's map, EPS the variance below which the photo's texture
 is ignored, e.g. 8 1e-4; no photo may be smaller than the model's map of it): <name>_guided.npy, fp32 [H, W], in the current directory.
+For one image or several, --refocus FOCUS APERTURE saves every photo refocused by its depth ("portrait mode": refocus.refocus_images, one call for
+the whole list; FOCUS = the focal plane, 0 .. 1 of the map's range or, for a metric model, a depth; APERTURE = photo pixels of blur radius per unit of
+defocus, e.g. 0.8 32): <name>_refocus.png in the current directory. --refocus_at X Y focuses on the point (X, Y) of the photo, normalised, instead of
+FOCUS; --refocus_radius R is the largest blur radius (0 .. 32, default 16); --refocus_guided RADIUS EPS enlarges the depth with the photo as the guide first.
 --stable [ALPHA] takes the images, in order, as the frames of ONE clip (they share a size): DPTModel.inference_video aligns every frame's map to the
 frame before it and filters the clip over time (muggled_dpt_amd.video; ALPHA = the filter's weight, default 0.3), video_display shows it with a
 carried range: <name>_stable.npy (fp32, the model's map size) and <name>_stable.png (the photo's size) into --output (a directory; default: the
@@ -78,6 +82,11 @@ def main():
     ap.add_argument("--tile_overlap", type=float, default=0.25, metavar="F", help="tiles: the share of a tile side that neighbouring tiles have in common")
     ap.add_argument("--guided", nargs=2, default=None, metavar=("RADIUS", "EPS"), help="save every image's depth at its own resolution, enlarged with "
                     "the photo as the guide (fast guided filter): window radius in map cells and regularisation, e.g. 8 1e-4")
+    ap.add_argument("--refocus", type=float, nargs=2, default=None, metavar=("FOCUS", "APERTURE"), help="save every photo refocused by its depth: the focal "
+                    "plane (0 .. 1 of the map's range; a depth for a metric model) and the blur radius in photo pixels per unit of defocus, e.g. 0.8 32")
+    ap.add_argument("--refocus_at", type=float, nargs=2, default=None, metavar=("X", "Y"), help="refocus: focus on this point of the photo (normalised) instead of FOCUS")
+    ap.add_argument("--refocus_radius", type=int, default=16, metavar="R", help="refocus: the largest blur radius in photo pixels, 0 .. 32")
+    ap.add_argument("--refocus_guided", nargs=2, default=None, metavar=("RADIUS", "EPS"), help="refocus: enlarge the depth with the photo as the guide first")
     ap.add_argument("--truth", default=None, metavar="DIR", help="measured depth per image, DIR/<name>.npy (fp32, any size; zero or NaN: no measurement): "
                     "fit the prediction to it, save <name>_true.npy (true depth at the truth's size) and <name>_metrics.json")
     ap.add_argument("--truth_method", default="lstsq", choices=("lstsq", "median"), help="truth: least squares, or median and mean absolute deviation")
@@ -144,6 +153,7 @@ def main():
     save_tiled(model, args, args.image_path or ["synthetic.npy"], [img])
     save_true_depth(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [depth])
     save_guided(args, args.image_path or ["synthetic.npy"], [img], [depth])
+    save_refocus(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
 
 
 def crop_argument(args):
@@ -275,6 +285,24 @@ def save_guided(args, paths, images, depths):
         print("saved", out, f"({m.shape[2]}x{m.shape[1]}, radius {int(args.guided[0])}, eps {float(args.guided[1]):g})")
 
 
+def save_refocus(args, is_metric, paths, images, depths):
+    """--refocus: one refocus.refocus_images call over all images (after one guided_upsample_images call with --refocus_guided), a PNG per photo"""
+    if not args.refocus:
+        return
+    from muggled_dpt_amd import mesh_io
+    from muggled_dpt_amd.refocus import refocus_images
+    if args.refocus_guided:
+        from muggled_dpt_amd.postprocess import guided_upsample_images
+        depths = guided_upsample_images(depths, images, int(args.refocus_guided[0]), float(args.refocus_guided[1]))
+    shown = refocus_images(depths, images, args.refocus[0], args.refocus_at, args.refocus[1], args.refocus_radius, 0.0, "depth" if is_metric else "inverse")
+    for path, bgr in zip(paths, shown):
+        out = os.path.splitext(os.path.basename(path))[0] + "_refocus.png"
+        with open(out, "wb") as fh:
+            fh.write(mesh_io.encode_png(np.ascontiguousarray(bgr.cpu().numpy()[:, :, ::-1])))
+        where = f"at ({args.refocus_at[0]:g}, {args.refocus_at[1]:g})" if args.refocus_at else f"focus {args.refocus[0]:g}"
+        print("saved", out, f"({bgr.shape[1]}x{bgr.shape[0]}, {where}, aperture {args.refocus[1]:g}, radius <= {args.refocus_radius})")
+
+
 def save_block_norms(model, args, paths, images):
     """--block_norms: one DPTModel.block_norms call per group of images that share a model tensor size"""
     if not args.block_norms:
@@ -332,6 +360,7 @@ def run_images(model, args, t0, is_metric=False):
     save_tiled(model, args, args.image_path, images)
     save_true_depth(args, is_metric, args.image_path, depths)
     save_guided(args, args.image_path, images, depths)
+    save_refocus(args, is_metric, args.image_path, images, depths)
 
 
 def run_clip(model, args):
