@@ -767,6 +767,54 @@ int mdpt_post_refocus(const mdpt_refocus_pair* records_host, const void* records
                       const double* focus_xy, double aperture, double focus_range, int32_t max_radius, void* scratch, size_t scratch_bytes, void* radius_out,
                       void* defocus_out, void* stream);
 
+/* Surface normals and relighting on the device (additive to ABI v6; not in the reference): the surface normal of every photo pixel from its depth map,
+ * under the camera of mdpt_post_mesh (x right, y up, the camera looks along -z), so the normals are those of the mesh this library exports and renders;
+ * as fp32 unit vectors, as an encoded uint8 normal map and / or as num_lights relit copies of the photo. n pairs of any sizes in one call, at most three
+ * launches whatever n and num_lights are (inverse space: min / max, per-pair state, the tile kernel; depth space: the tile kernel alone), nothing read
+ * back, nothing synchronises, no atomics, bit-deterministic, every pair independent of the others. A pair is an mdpt_normals_pair record: the h x w map
+ * (dtype); the uint8 BGR photo of H x W pixels (any size relative to the map) whose rows start `pitch` bytes apart (pitch >= 3 W; read byte by byte, in
+ * place; NULL in EVERY record: every photo byte is 255, a white-clay hillshade of H x W pixels); the outputs, each NULL in every record or in none -
+ * normals fp32 [H,W,3] = (x, y, z), encoded uint8 [H,W,3], relit uint8 [num_lights,H,W,3] - which decide what is written; scratch_off, the byte offset of
+ * the pair's own scratch inside `scratch` (a multiple of 8; 1024 bytes a pair; regions must not overlap); tile_off = the sum over the pairs before it of
+ * ceil(H / 32) ceil(W / 32) (MDPT_NORMALS_TILE = 32); kx = x_scale tan(fov / 2), ky = y_scale tan(fov / 2) with (x_scale, y_scale) = (1, H / W) for
+ * W > H, else (W / H, 1) (the aspect rule of mdpt_post_mesh); step = the difference step t in photo pixels, 1 .. MDPT_NORMALS_MAX_STEP. The table is
+ * passed twice: records_dev in DEVICE memory (8-byte aligned), records_host the same records on the host, read during the call for the argument checks
+ * only. lights_dev: fp64 [num_lights,3] UNIT directions towards the light in DEVICE memory (8-byte aligned; the caller normalises them).
+ * All arithmetic is fp64, nothing contracted, every result rounded once. Per photo pixel (Y, X):
+ *   sample ........ s = the map at the pixel's centre: bilinear at u = (X + 0.5) w / W - 0.5 clamped to the grid, fp64 weights, rows first (the resampler
+ *                   of mdpt_post_refocus); a map of the photo's size is read directly.
+ *   depth ......... space MDPT_ALIGN_INVERSE: lo, hi = the fp32 min / max of the map's finite values (a zero of either sign counts as +0),
+ *                   v = hi > lo ? (s - lo) / (hi - lo) : 0, z = 1 / (a + b v), a = 1 / max_depth, b = 1 / min_depth - 1 / max_depth (mdpt_post_mesh's
+ *                   non-metric depth); the pixel is valid iff s is finite. MDPT_ALIGN_DEPTH: z = s, valid iff s is finite and s > 0 (min_depth and
+ *                   max_depth are not read).
+ *   position ...... x = 2 (X + 0.5) / W - 1, y = 1 - 2 (Y + 0.5) / H, P = ((z x) kx, (z y) ky, -z).
+ *   tangents ...... per axis, A = the neighbour at +t (x axis: X + t; y axis: Y - t, up), B the one at -t; a neighbour is usable if it lies inside the
+ *                   photo and is valid. Both usable, with da = |z_A - z_0|, db = |z_0 - z_B|: da <= edge_ratio db and db <= edge_ratio da (edge_ratio =
+ *                   inf: always, the products are not formed) -> T = P_A - P_B; else T = P_A - P_0 if da < db, else P_0 - P_B. One usable: that
+ *                   side. None usable on either axis, or the centre invalid: the pixel is invalid. A normal is never taken across a depth edge.
+ *   normal ........ n = Tx x Ty = (Tx.y Ty.z - Tx.z Ty.y, Tx.z Ty.x - Tx.x Ty.z, Tx.x Ty.y - Tx.y Ty.x), len2 = (nx nx + ny ny) + nz nz; invalid unless
+ *                   len2 is finite and > 0; n_c / sqrt(len2). No flip: a height field seen from the origin faces the camera. An invalid pixel gets
+ *                   (0, 0, 0). normals = fp32(n). encoded byte = floor((c + 1) / 2 * 255 + 0.5) of the fp64 component, stored B, G, R = z, y, x
+ *                   (invalid: 128, 128, 128).
+ *   shading ....... per light l: d = n.l = (nx lx + ny ly) + nz lz, shade = ambient + diffuse (d > 0 ? d : 0). specular > 0: view_c = -P_c / |P|,
+ *                   |P| = sqrt((Px Px + Py Py) + Pz Pz), h_c = (l_c + view_c) / |l + view| alike, sp = n.h (> 0, else 0; the sum formed as for d),
+ *                   squared shininess_log2 times (repeated squaring, no pow), spec = 255 (specular sp); else spec = 0.
+ *                   relit_c = min(255, floor((photo_c shade + spec) + 0.5)). An invalid pixel returns the photo's bytes. The mix is on the
+ *                   gamma-encoded bytes of a photo that carries its own lighting; no cast shadows, no ambient occlusion.
+ * Checks (MDPT_E_INVALID, nothing launched, the message names the argument): null pointers, n outside 1 .. 65535, num_lights outside 0 ..
+ * MDPT_NORMALS_MAX_LIGHTS, relit outputs without lights, min_depth / max_depth outside 0 < min < max < inf (inverse space), edge_ratio < 1 or NaN,
+ * ambient / diffuse / specular negative or not finite, shininess_log2 outside 0 .. 10, sizes <= 0, H W or h w >= 2^31, pitch < 3 W, step outside its
+ * range, kx / ky not finite or <= 0, a wrong tile_off, misaligned map / table / lights / scratch / normals, a scratch region outside scratch_bytes or
+ * overlapping another, an output or the photo in some records only, no output at all. mdpt_post_normals_scratch_bytes reads only H and W. */
+#define MDPT_NORMALS_MAX_STEP 16
+#define MDPT_NORMALS_TILE 32
+#define MDPT_NORMALS_MAX_LIGHTS 64
+typedef struct mdpt_normals_pair { const void* map; int32_t h, w; const void* photo; int64_t pitch; int32_t H, W; void* normals; void* encoded; void* relit; int64_t scratch_off, tile_off; double kx, ky; int32_t step, pad; } mdpt_normals_pair;
+int mdpt_post_normals_scratch_bytes(const mdpt_normals_pair* records_host, int32_t n, size_t* bytes);
+int mdpt_post_normals(const mdpt_normals_pair* records_host, const void* records_dev, int32_t n, int32_t dtype, int32_t space, double min_depth,
+                      double max_depth, double edge_ratio, const void* lights_dev, int32_t num_lights, double ambient, double diffuse, double specular,
+                      int32_t shininess_log2, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

@@ -450,6 +450,33 @@ struct RefocusJob {
 };
 int mdpt_launch_post_refocus(const RefocusJob& job, hipStream_t stream);
 
+// surface normals and relighting (post_normals.inc; a pair = mdpt_normals_pair of include/mdpt.h): the h x w map (the table's dtype), the uint8 BGR photo
+// of H x W pixels whose rows lie `pitch` bytes apart (null: every byte 255, a white-clay hillshade), the outputs (each null in every record or in none):
+// fp32 [H,W,3] unit normals (x, y, z), uint8 [H,W,3] encoded normals (B, G, R = z, y, x) and uint8 [V,H,W,3] relit frames, where the pair's scratch
+// starts (NORMALS_HEADER_BYTES: the {min, max} partials of the map as ordered keys, then NormalsState), the 32 x 32 output tiles of the pairs before it,
+// the camera's kx = x_scale tan(fov / 2), ky = y_scale tan(fov / 2) and the difference step in photo pixels. Device table, indexed by pair.
+struct NormalsPair {
+    const void* map; int h, w; const unsigned char* photo; long long pitch; int H, W; float* normals; unsigned char* encoded; unsigned char* relit;
+    long long scratch_off, tile_off; double kx, ky; int step, pad;
+};
+#define NORMALS_MAX_STEP 16
+#define NORMALS_TILE 32      // output pixels of one workgroup along each axis (one thread each)
+#define NORMALS_MAX_LIGHTS 64
+#define NORMALS_PARTS 64     // workgroups that share the min / max of one map
+#define NORMALS_HEADER_BYTES 1024
+inline size_t normals_pair_tiles(size_t H, size_t W) { return ((H + NORMALS_TILE - 1) / NORMALS_TILE) * ((W + NORMALS_TILE - 1) / NORMALS_TILE); }
+// one call: z = 1 / (depth_a + depth_b v) with v = the map in its own range (inverse space), or z = the map (depth space: no min / max launches).
+// lights: V unit directions, fp64 [V,3], device memory (null: no frames). central_only: edge_ratio = inf. At most three launches whatever P and V.
+struct NormalsJob {
+    const NormalsPair* pairs;
+    int P, dt, depth_space, central_only, V, shininess_log2;
+    double depth_a, depth_b, edge_ratio, ambient, diffuse, specular;
+    const double* lights;
+    char* scratch;
+    size_t total_tiles;
+};
+int mdpt_launch_post_normals(const NormalsJob& job, hipStream_t stream);
+
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);
 

@@ -216,6 +216,49 @@ __device__ __forceinline__ double bilinear_f64_at(const void* g, int gdt, int gh
     return bilinear_f64_mix(t, g00, g01, g10, g11);
 }
 
+// What the per-photo features over a pair table (refocus, normals) share. The map at the centre of photo pixel (Y, X) of an H x W photo: a map of the
+// photo's size is read directly, so that it comes through unchanged whatever its neighbours hold
+__device__ __forceinline__ double map_at_pixel_centre(const void* map, int dt, int h, int w, int H, int W, int Y, int X) {
+    if (h == H && w == W) return (double)ld_dt(map, (size_t)Y * w + X, dt);
+    return bilinear_f64_at(map, dt, h, w, (double)X + 0.5, (double)Y + 0.5, H, W);
+}
+
+// share `share` of `shares` (workgroups of 256 threads) of the fp32 min / max of the FINITE values of a map of n elements -> part[0..1] as ordered
+// keys (a share without a finite value stores the neutral {~0, 0})
+__device__ __forceinline__ void finite_minmax_part(const void* map, size_t n, int dt, unsigned share, unsigned shares, unsigned* part) {
+    float lo = INFINITY, hi = -INFINITY;
+    bool any = false;
+    for (size_t i = (size_t)share * 256 + threadIdx.x; i < n; i += (size_t)shares * 256) {
+        const float v = ld_dt(map, i, dt);
+        if (isfinite(v)) {
+            lo = fminf(lo, v), hi = fmaxf(hi, v);
+            any = true;
+        }
+    }
+    block_minmax_part(lo, hi, false, any, part);
+}
+
+// the reduced ordered keys of those partials -> lo, hi as fp64 (a zero takes the sign +; a map without a finite value: 0, 0) and whether hi > lo
+__device__ __forceinline__ bool finite_range(unsigned lo_o, unsigned hi_o, double& lo, double& hi) {
+#pragma clang fp contract(off)
+    const bool any = lo_o <= hi_o;  // (a map without a finite value leaves the neutral partials {~0, 0})
+    lo = any ? (double)ord2f(lo_o) + 0.0 : 0.0;
+    hi = any ? (double)ord2f(hi_o) + 0.0 : 0.0;
+    return any && hi > lo;
+}
+
+// the pair that owns tile `tile` of a call: the last record whose tile_off (the tiles of the pairs before it) is not beyond it
+template <typename Pair>
+__device__ __forceinline__ int pair_of_tile(const Pair* __restrict__ pairs, int P, long long tile) {
+    int a = 0, b = P - 1;
+    while (a < b) {
+        const int mid = (a + b + 1) >> 1;
+        if (pairs[mid].tile_off <= tile) a = mid;
+        else b = mid - 1;
+    }
+    return a;
+}
+
 inline int grid_for(size_t total) {
     size_t g = (total + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));

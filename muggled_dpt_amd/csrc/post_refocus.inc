@@ -52,24 +52,13 @@ __device__ __forceinline__ uint2* refocus_plane(const RefocusPair& p, char* scra
 
 // the map at the centre of photo pixel (Y, X)
 __device__ __forceinline__ double refocus_map_at(const RefocusPair& p, int dt, int Y, int X) {
-    if (p.h == p.H && p.w == p.W) return (double)ld_dt(p.map, (size_t)Y * p.w + X, dt);
-    return bilinear_f64_at(p.map, dt, p.h, p.w, (double)X + 0.5, (double)Y + 0.5, p.H, p.W);
+    return map_at_pixel_centre(p.map, dt, p.h, p.w, p.H, p.W, Y, X);
 }
 
 // (1) blockIdx.y = pair, blockIdx.x = one of the 64 shares of the map (elements share + 64 k blocks of 256)
 __global__ __launch_bounds__(256) void refocus_minmax_kernel(const RefocusPair* __restrict__ pairs, int dt, char* __restrict__ scratch) {
     const RefocusPair p = pairs[blockIdx.y];
-    const size_t n = (size_t)p.h * p.w;
-    float lo = INFINITY, hi = -INFINITY;
-    bool any = false;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)REFOCUS_PARTS * 256) {
-        const float v = ld_dt(p.map, i, dt);
-        if (isfinite(v)) {
-            lo = fminf(lo, v), hi = fmaxf(hi, v);
-            any = true;
-        }
-    }
-    block_minmax_part(lo, hi, false, any, refocus_parts(p, scratch) + 2 * blockIdx.x);
+    finite_minmax_part(p.map, (size_t)p.h * p.w, dt, blockIdx.x, REFOCUS_PARTS, refocus_parts(p, scratch) + 2 * blockIdx.x);
 }
 
 // (2) blockIdx.x = pair, one wave
@@ -88,12 +77,9 @@ __global__ __launch_bounds__(64) void refocus_state_kernel(RefocusJob j) {
         before += __shfl_xor(before, o);
     }
     if (threadIdx.x != 0) return;
-    const bool any = lo_o <= hi_o;  // (a map without a finite value leaves the neutral partials {~0, 0})
     RefocusState st{};
-    st.lo = any ? (double)ord2f(lo_o) + 0.0 : 0.0;
-    st.hi = any ? (double)ord2f(hi_o) + 0.0 : 0.0;
+    const bool ranged = finite_range(lo_o, hi_o, st.lo, st.hi);
     st.before = before;
-    const bool ranged = any && st.hi > st.lo;
     st.live = j.depth_space || ranged;
     st.focus = j.focus;
     if (j.pointed) {
@@ -153,15 +139,7 @@ __global__ __launch_bounds__(REFOCUS_TILE* REFOCUS_TILE) void refocus_gather_ker
     __shared__ int wave_k[THREADS / 64];
     __shared__ int which;
     const int tid = (int)threadIdx.x;
-    if (tid == 0) {
-        int a = 0, b = P - 1;
-        while (a < b) {
-            const int mid = (a + b + 1) >> 1;
-            if (pairs[mid].tile_off <= (long long)blockIdx.x) a = mid;
-            else b = mid - 1;
-        }
-        which = a;
-    }
+    if (tid == 0) which = pair_of_tile(pairs, P, (long long)blockIdx.x);
     __syncthreads();
     const RefocusPair p = pairs[which];
     const int tile = (int)((long long)blockIdx.x - p.tile_off), tiles_x = (p.W + T - 1) / T;

@@ -1110,6 +1110,39 @@ class DPTModel(nn.Module):
             preds = guided_upsample_images(preds, list(images_bgr), int(guided[0]), float(guided[1]))
         return refocus_images(preds, list(images_bgr), focus, focus_xy, REFOCUS_APERTURE if aperture is None else aperture, max_radius, focus_range, space)
 
+    def _maps_for_photos(self, images_bgr, guided, max_side_length, use_square_sizing, batch_size):
+        """inference_images and, with guided = (radius, eps), guided_upsample_images: what inference_normals and inference_relight start from"""
+        preds = self.inference_images(images_bgr, max_side_length, use_square_sizing, batch_size)
+        if guided is not None:
+            from .postprocess import guided_upsample_images
+            preds = guided_upsample_images(preds, list(images_bgr), int(guided[0]), float(guided[1]))
+        return preds
+
+    def inference_normals(self, images_bgr, space: str | None = None, guided=None, encode: bool = False, max_side_length: int | None = None,
+                          use_square_sizing: bool = True, batch_size: int = 32, **camera):
+        """The surface normals of every photo from its own predicted depth -> a list of fp32 [H_i,W_i,3] device tensors in input order (not in the
+        reference; encode=True: -> (normals, uint8 BGR normal maps)): one inference_images call, with guided = (radius, eps) one
+        postprocess.guided_upsample_images call, then one relight.depth_normals call at the photos' sizes; nothing is read back. camera: depth_normals'
+        fov_deg / min_depth / max_depth / step / edge_ratio. space None: "depth" for a metric model (config is_metric), "inverse" for every other."""
+        from .relight import depth_normals
+        if space is None:
+            space = "depth" if self.config.get("is_metric", False) else "inverse"
+        preds = self._maps_for_photos(images_bgr, guided, max_side_length, use_square_sizing, batch_size)
+        return depth_normals(preds, None, list(images_bgr), space=space, encode=encode, **camera)
+
+    def inference_relight(self, images_bgr, light_dirs, ambient: float = 0.35, diffuse: float = 0.9, specular: float = 0.0, shininess_log2: int = 4,
+                          space: str | None = None, guided=None, max_side_length: int | None = None, use_square_sizing: bool = True, batch_size: int = 32,
+                          **camera) -> list[Tensor]:
+        """Every photo relit by its own predicted depth ("portrait lighting") -> a list of uint8 [V,H_i,W_i,3] BGR device tensors in input order, one frame
+        per row of light_dirs (not in the reference): one inference_images call, with guided = (radius, eps) one postprocess.guided_upsample_images
+        call, then one relight.relight_images call; nothing is read back. light_dirs / ambient / diffuse / specular / shininess_log2 and camera (fov_deg /
+        min_depth / max_depth / step / edge_ratio) are relight_images'. space None: "depth" for a metric model (config is_metric), else "inverse"."""
+        from .relight import relight_images
+        if space is None:
+            space = "depth" if self.config.get("is_metric", False) else "inverse"
+        preds = self._maps_for_photos(images_bgr, guided, max_side_length, use_square_sizing, batch_size)
+        return relight_images(preds, list(images_bgr), light_dirs, ambient, diffuse, specular, shininess_log2, space=space, **camera)
+
     def render_views(self, image_bgr: np.ndarray, view_proj=None, out_wh=(1280, 720), max_side_length: int | None = None,
                      use_square_sizing: bool = True, fov_deg: float | None = None, min_depth: float | None = None, max_depth: float | None = None,
                      edge_threshold: float | None = None, target_num_faces=None, mode: str = "triangles", cull: str = "back", point_size: float = 2.0,

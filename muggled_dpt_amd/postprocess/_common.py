@@ -200,6 +200,20 @@ def _photo_list(images_bgr, n: int, what: str) -> tuple[list, bool]:
     return [f.detach().contiguous() if on_device else f for f in images_bgr], on_device
 
 
+def _photo_pointers(images_bgr, photos, on_device: bool, dev, what: str):
+    """_photo_list's photos for kernels that read a photo byte by byte through its row pitch -> (what must stay alive until the launch, the device address and
+    the pitch in bytes of each). A CUDA view whose pixels are packed and whose rows are at least a row apart is read in place; anything else as its packed
+    copy; host photos go through one pinned upload."""
+    if on_device:
+        if photos[0].device != dev:
+            raise RuntimeError(f"{what}: the predictions are on {dev} but the images are on {photos[0].device}")
+        in_place = [f.stride(2) == 1 and f.stride(1) == 3 and f.stride(0) >= 3 * f.shape[1] for f in images_bgr]
+        keep = [f.detach() if ok else c for f, c, ok in zip(images_bgr, photos, in_place)]
+        return keep, [f.data_ptr() for f in keep], [int(f.stride(0)) for f in keep]
+    keep, img_ptrs = upload(photos, dev, 16)
+    return keep, img_ptrs, [3 * f.shape[1] for f in photos]
+
+
 def _cmap_tensor(lut, device) -> Tensor | None:
     if lut is None:
         return None

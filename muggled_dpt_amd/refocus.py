@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 from . import native
-from .postprocess._common import (_launch, _photo_list, _prediction_list, _upload_records, _views, packed_offsets, prediction_count, ptr, record_table,
-                                  scratch_bytes, upload)
+from .postprocess._common import (_launch, _photo_list, _photo_pointers, _prediction_list, _upload_records, _views, packed_offsets, prediction_count, ptr,
+                                  record_table, scratch_bytes)
 
 __all__ = ["REFOCUS_SPACES", "REFOCUS_APERTURE", "refocus_images", "defocus_planes"]
 
@@ -66,16 +66,7 @@ def _run(predictions, images_bgr, checked, space, what: str, gather: bool, plane
     photos, on_device = _photo_list(images_bgr, n, what) if n >= 0 else (None, False)
     maps = _prediction_list(predictions, what)
     dev = maps[0].device
-    if on_device:
-        if photos[0].device != dev:
-            raise RuntimeError(f"{what}: the predictions are on {dev} but the images are on {photos[0].device}")
-        # a view whose pixels are packed and whose rows are at least a row apart is read in place through its pitch; anything else as its packed copy
-        in_place = [f.stride(2) == 1 and f.stride(1) == 3 and f.stride(0) >= 3 * f.shape[1] for f in images_bgr]
-        keep = [f.detach() if ok else c for f, c, ok in zip(images_bgr, photos, in_place)]
-        img_ptrs, pitches = [f.data_ptr() for f in keep], [int(f.stride(0)) for f in keep]
-    else:
-        keep, img_ptrs = upload(photos, dev, 16)
-        pitches = [3 * f.shape[1] for f in photos]
+    keep, img_ptrs, pitches = _photo_pointers(images_bgr, photos, on_device, dev, what)
     hws = [(int(f.shape[0]), int(f.shape[1])) for f in photos]
     if any(h * w >= 2 ** 31 for h, w in hws):
         raise ValueError(f"{what}: a photo of 2^31 pixels or more is not supported")

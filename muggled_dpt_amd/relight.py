@@ -1,0 +1,203 @@
+"""Surface normals and relighting from depth maps (not in the reference): the surface normal of every photo pixel under the camera of the mesh export
+(postprocess.depth_frames_to_mesh: x right, y up, the camera looks along -z), so the normals are by construction those of the mesh this project exports and
+renders. depth_normals returns them as fp32 unit vectors and, asked, as encoded uint8 normal maps; relight_images shades the photo once per light ("portrait
+lighting", the sibling of refocus's "portrait mode"), or a white surface where no photo is given (a hillshade, which shows the facets, ringing and seams of a
+depth map that a colormap hides); DPTModel.inference_normals / inference_relight start from the photos. The differences are edge-aware: across a depth
+discontinuity the one-sided difference is taken, never the central one, which would smear every depth edge into a band of grazing normals.
+Kernels: csrc/post_normals.inc (mdpt_post_normals); the arithmetic is written out in include/mdpt.h.
+
+Known limits: the normals of a relative-depth model depend on the assumed fov_deg, min_depth and max_depth, which are the viewer's controls, not measurements.
+Shading multiplies a photo that already carries its own lighting and is done on the gamma-encoded bytes, not in linear light. There are no cast shadows and no
+ambient occlusion (both would be a gather over a halo, like refocus's). Output quality on real photographs is unverified - no checkpoint can be loaded where
+this was written; the tests hold the arithmetic and synthetic scenes only."""
+
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from . import native
+from .postprocess._common import (_launch, _photo_list, _photo_pointers, _prediction_list, _upload_records, _views, packed_offsets, prediction_count,
+                                  record_table, scratch_bytes)
+from .postprocess.mesh import MESH_FOV_DEG, MESH_MAX_DEPTH, MESH_MIN_DEPTH
+
+__all__ = ["NORMALS_SPACES", "depth_normals", "relight_images", "light_sweep", "default_step"]
+
+NORMALS_SPACES = {"inverse": native.ALIGN_INVERSE, "depth": native.ALIGN_DEPTH}
+# mdpt_normals_pair of include/mdpt.h (csrc/mdpt_post.cpp static_asserts the layout)
+NORMALS_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("normals", "<u8"),
+                           ("encoded", "<u8"), ("relit", "<u8"), ("scratch_off", "<i8"), ("tile_off", "<i8"), ("kx", "<f8"), ("ky", "<f8"), ("step", "<i4"),
+                           ("pad", "<i4")])
+
+
+def light_sweep(n: int, elevation_deg: float = 35.0) -> np.ndarray:
+    """A closed ring of n unit light directions around the camera axis -> float64 [n,3]: direction k points towards the light at azimuth 2 pi k / n in the
+    image plane (0: from the right, counter-clockwise seen from the camera) and elevation_deg above it, towards the camera (90: straight from the camera).
+    The lights of relight_images for a sweep around a portrait, as orbit_camera.swing_views is the cameras' of a swing. Plain host math."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"light_sweep: n must be an int >= 1, got {n!r}")
+    el = float(elevation_deg)
+    if not -90.0 <= el <= 90.0:
+        raise ValueError(f"light_sweep: elevation_deg must be in [-90, 90], got {elevation_deg}")
+    az = np.arange(int(n), dtype=np.float64) * (2.0 * math.pi / int(n))
+    d = np.stack([math.cos(math.radians(el)) * np.cos(az), math.cos(math.radians(el)) * np.sin(az), np.full(int(n), math.sin(math.radians(el)))], axis=1)
+    return d / np.sqrt((d * d).sum(axis=1, keepdims=True))
+
+
+def default_step(W: int, w: int) -> int:
+    """the difference step for a map w wide shown on a photo W wide: about one map cell, min(16, max(1, floor(W / w + 0.5))) photo pixels"""
+    return min(native.NORMALS_MAX_STEP, max(1, int(math.floor(W / w + 0.5))))
+
+
+def _unit_lights(light_dirs, what: str) -> np.ndarray:
+    """a single (x, y, z) or [V,3] directions towards the lights -> float64 [V,3], each normalised in fp64"""
+    d = np.asarray(light_dirs.detach().cpu().numpy() if isinstance(light_dirs, torch.Tensor) else light_dirs, dtype=np.float64)
+    if d.ndim == 1:
+        d = d[None]
+    if d.ndim != 2 or d.shape[1] != 3 or not 1 <= d.shape[0] <= native.NORMALS_MAX_LIGHTS:
+        raise ValueError(f"{what}: light_dirs must be (x, y, z) or [V,3] with 1 <= V <= {native.NORMALS_MAX_LIGHTS}, got shape {d.shape}")
+    with np.errstate(all="ignore"):
+        length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    if not (np.isfinite(d).all() and np.isfinite(length).all() and (length > 0.0).all()):
+        raise ValueError(f"{what}: every light direction must be finite and not zero, got {d.tolist()}")
+    return np.ascontiguousarray(d / length[:, None])
+
+
+def _normals_checked(predictions, target_hws, images_bgr, space, fov_deg, min_depth, max_depth, step, edge_ratio, what: str):
+    """everything the calls can refuse from shapes and values alone, before any tensor has to be on the device -> the checked scalars"""
+    if space not in NORMALS_SPACES:
+        raise ValueError(f"{what}: space must be one of {sorted(NORMALS_SPACES)}, got {space!r}")
+    fov_deg, min_depth, max_depth, edge_ratio = float(fov_deg), float(min_depth), float(max_depth), float(edge_ratio)
+    if not 0.0 < fov_deg < 180.0:
+        raise ValueError(f"{what}: fov_deg must be in (0, 180), got {fov_deg}")
+    if space == "inverse" and not (0.0 < min_depth < max_depth < float("inf")):
+        raise ValueError(f"{what}: need 0 < min_depth < max_depth, finite, got {min_depth}, {max_depth}")
+    if step is not None and (isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 1 <= int(step) <= native.NORMALS_MAX_STEP):
+        raise ValueError(f"{what}: step must be None (about one map cell) or an int in 1 .. {native.NORMALS_MAX_STEP} (photo pixels), got {step!r}")
+    if not edge_ratio >= 1.0:
+        raise ValueError(f"{what}: edge_ratio must be >= 1 (inf: always the central difference), got {edge_ratio}")
+    n = prediction_count(predictions)
+    if n >= 0 and isinstance(images_bgr, (list, tuple)):
+        if len(images_bgr) != n:
+            raise ValueError(f"{what}: {n} predictions but {len(images_bgr)} images")
+        for k, f in enumerate(images_bgr):
+            if isinstance(f, (np.ndarray, torch.Tensor)) and (f.dtype != (torch.uint8 if isinstance(f, torch.Tensor) else np.uint8) or f.ndim != 3 or f.shape[2] != 3):
+                raise ValueError(f"{what}: image {k} is not a uint8 HxWx3 BGR photo (shape {tuple(f.shape)}, dtype {f.dtype})")
+    if target_hws is not None:
+        if images_bgr is not None:
+            raise ValueError(f"{what}: give target_hws or images_bgr, not both (the output has the photo's size)")
+        target_hws = [(int(hw[0]), int(hw[1])) for hw in target_hws]
+        if n >= 0 and len(target_hws) != n:
+            raise ValueError(f"{what}: {n} predictions but {len(target_hws)} target sizes")
+        if any(h <= 0 or w <= 0 or h * w >= 2 ** 31 for h, w in target_hws):
+            raise ValueError(f"{what}: target sizes must be positive (H, W) of fewer than 2^31 pixels, got {target_hws}")
+    return target_hws, fov_deg, min_depth, max_depth, None if step is None else int(step), edge_ratio
+
+
+def _shading_checked(ambient, diffuse, specular, shininess_log2, what: str):
+    ambient, diffuse, specular = float(ambient), float(diffuse), float(specular)
+    for name, v in (("ambient", ambient), ("diffuse", diffuse), ("specular", specular)):
+        if not 0.0 <= v < float("inf"):
+            raise ValueError(f"{what}: {name} must be finite and >= 0, got {v}")
+    if isinstance(shininess_log2, bool) or not isinstance(shininess_log2, (int, np.integer)) or not 0 <= int(shininess_log2) <= 10:
+        raise ValueError(f"{what}: shininess_log2 must be an int in 0 .. 10 (the exponent is 2^shininess_log2), got {shininess_log2!r}")
+    return ambient, diffuse, specular, int(shininess_log2)
+
+
+def _run(predictions, images_bgr, checked, space, what: str, lights, shading, want_normals: bool, want_encoded: bool):
+    target_hws, fov_deg, min_depth, max_depth, step, edge_ratio = checked
+    n = prediction_count(predictions)
+    photos = None
+    if images_bgr is not None:
+        photos, on_device = _photo_list(images_bgr, n, what) if n >= 0 else (None, False)
+    maps = _prediction_list(predictions, what)
+    dev = maps[0].device
+    if photos is not None:
+        keep, img_ptrs, pitches = _photo_pointers(images_bgr, photos, on_device, dev, what)
+        hws = [(int(f.shape[0]), int(f.shape[1])) for f in photos]
+    else:
+        keep, img_ptrs, pitches = None, [0] * len(maps), [0] * len(maps)
+        hws = target_hws if target_hws is not None else [(int(m.shape[0]), int(m.shape[1])) for m in maps]
+        if len(hws) != len(maps):
+            raise ValueError(f"{what}: {len(maps)} predictions but {len(hws)} target sizes")
+    if any(h * w >= 2 ** 31 for h, w in hws):
+        raise ValueError(f"{what}: a photo of 2^31 pixels or more is not supported")
+    tan_half = math.tan(fov_deg * 0.5 * (math.pi / 180.0))
+    scales = [(1.0, h / w) if w > h else (w / h, 1.0) for h, w in hws]  # (x_scale, y_scale): depth_frames_to_mesh's aspect rule
+    records = record_table(NORMALS_RECORD, maps, photo=img_ptrs, pitch=pitches, H=[h for h, _ in hws], W=[w for _, w in hws],
+                           kx=[sx * tan_half for sx, _ in scales], ky=[sy * tan_half for _, sy in scales],
+                           step=[default_step(w, int(m.shape[1])) if step is None else step for (_, w), m in zip(hws, maps)])
+    tile = native.NORMALS_TILE
+    records["tile_off"], _ = packed_offsets([((h + tile - 1) // tile) * ((w + tile - 1) // tile) for h, w in hws])
+    records["scratch_off"], at = packed_offsets([scratch_bytes("mdpt_post_normals_scratch_bytes", records[k:k + 1].ctypes.data, 1) for k in range(len(maps))])
+    offs, total = packed_offsets([h * w for h, w in hws])
+    normals = encoded = relit = table_l = None
+    V = 0 if lights is None else int(lights.shape[0])
+    if want_normals:
+        normals = torch.empty(3 * total, device=dev, dtype=torch.float32)
+        records["normals"] = [normals.data_ptr() + 12 * o for o in offs]
+    if want_encoded:
+        encoded = torch.empty(3 * total, device=dev, dtype=torch.uint8)
+        records["encoded"] = [encoded.data_ptr() + 3 * o for o in offs]
+    if V:
+        relit = torch.empty(3 * V * total, device=dev, dtype=torch.uint8)
+        records["relit"] = [relit.data_ptr() + 3 * V * o for o in offs]
+        table_l = _upload_records(lights, dev)
+    scratch = torch.empty(at // 8, device=dev, dtype=torch.float64)
+    table = _upload_records(records, dev)
+    ambient, diffuse, specular, shininess_log2 = shading
+    _launch(dev, "mdpt_post_normals", records.ctypes.data, table.data_ptr(), len(maps), native.dtype_code(maps[0].dtype), NORMALS_SPACES[space], min_depth,
+            max_depth, edge_ratio, None if table_l is None else table_l.data_ptr(), V, ambient, diffuse, specular, shininess_log2, scratch.data_ptr(), at)
+    del table, table_l, keep, scratch  # (the caching allocator reuses them in stream order only)
+    frames = [relit[3 * V * o:3 * V * (o + h * w)].view(V, h, w, 3) for o, (h, w) in zip(offs, hws)] if V else None
+    return ([v[0] for v in _views(normals, hws, (3,))] if want_normals else None, [v[0] for v in _views(encoded, hws, (3,))] if want_encoded else None, frames)
+
+
+def depth_normals(predictions, target_hws=None, images_bgr=None, *, space: str = "inverse", fov_deg: float = MESH_FOV_DEG, min_depth: float = MESH_MIN_DEPTH,
+                  max_depth: float = MESH_MAX_DEPTH, step=None, edge_ratio: float = 2.0, encode: bool = False):
+    """Depth maps -> one fp32 [H_i,W_i,3] unit surface normal (x, y, z) per map, in order, on the device (views into one allocation), in the camera frame of
+    depth_frames_to_mesh: x right, y up, the camera looks along -z, so a surface that faces the camera has n = (0, 0, 1). The output size is the photo's if
+    images_bgr is given (only its size is used), else target_hws[i] = (H, W), else the map's own. encode=True: -> (normals, uint8 [H_i,W_i,3] BGR normal maps,
+    byte = floor((c + 1) / 2 * 255 + 0.5), B, G, R = z, y, x, the usual bluish tangent-space look).
+    Per output pixel: s = the map at the pixel's centre (bilinear; a map of the output's size is read directly); space="inverse" (relative models):
+    z = 1 / (a + b v) with v = the map in its own range of finite values, a = 1 / max_depth, b = 1 / min_depth - 1 / max_depth - the viewer's depth, as
+    depth_frames_to_mesh(is_metric=False); space="depth" (metric maps): z = s, valid where s > 0. The pixel is unprojected with fov_deg and the aspect rule of
+    the mesh; per axis the tangent is the difference of the neighbours `step` pixels away: central where the depth differences to both are within edge_ratio
+    of each other, else one-sided towards the nearer one in depth (so no normal is taken across a depth edge; edge_ratio=inf: always central), one-sided next
+    to an invalid (NaN, inf; depth space: <= 0) neighbour or the border. n = Tx x Ty, normalised; a pixel without a usable neighbour on an axis is (0, 0, 0)
+    and encodes to 128, 128, 128. step: an int in 1 .. 16 photo pixels; None: about one map cell, min(16, max(1, floor(W / w + 0.5))), because a
+    bilinearly enlarged map is piecewise bilinear and a 1-pixel difference shows its cell grid as facets; for a guided-upsampled map of the photo's own size
+    step=1 is right. The defaults (step, edge_ratio 2, the viewer's fov 50 and depths 50 .. 100) are user-facing choices, not measured optima.
+    predictions / images_bgr as refocus_images takes them - a [B,h,w] tensor or a list of [1,h,w] / [h,w] CUDA maps of one dtype (fp32 / bf16 / fp16) whose
+    sizes may differ. fp64 arithmetic, bit-deterministic, every pair independent of the others, at most three launches for the whole call, nothing read back,
+    no synchronisation. Limits: see this module's docstring."""
+    what = "depth_normals"
+    checked = _normals_checked(predictions, target_hws, images_bgr, space, fov_deg, min_depth, max_depth, step, edge_ratio, what)
+    if images_bgr is not None:  # only the sizes are used: no photo is uploaded or read
+        checked = ([(int(f.shape[0]), int(f.shape[1])) for f in _photo_list(images_bgr, prediction_count(predictions), what)[0]],) + checked[1:]
+    normals, encoded, _ = _run(predictions, None, checked, space, what, None, (0.0, 0.0, 0.0, 0), True, bool(encode))
+    return (normals, encoded) if encode else normals
+
+
+def relight_images(predictions, images_bgr, light_dirs, ambient: float = 0.35, diffuse: float = 0.9, specular: float = 0.0, shininess_log2: int = 4, *,
+                   target_hws=None, space: str = "inverse", fov_deg: float = MESH_FOV_DEG, min_depth: float = MESH_MIN_DEPTH, max_depth: float = MESH_MAX_DEPTH,
+                   step=None, edge_ratio: float = 2.0, return_normals: bool = False):
+    """Depth maps and the photos they came from -> one uint8 [V,H_i,W_i,3] BGR tensor per pair, in order, on the device (views into one allocation): the photo
+    shaded by its surface normals, one frame per row of light_dirs [V,3] (a single (x, y, z): V = 1; at most 64; directions TOWARDS the light in the camera frame
+    of depth_normals, normalised here in fp64; light_sweep gives a ring of them). The normals are depth_normals' (same space / fov_deg / min_depth / max_depth /
+    step / edge_ratio), formed once per pixel for all V lights. Per light: shade = ambient + diffuse max(0, n.l); with specular > 0 a Blinn-Phong highlight
+    255 specular max(0, n.h)^(2^shininess_log2), h the half vector of the light and the view direction, the power by repeated squaring (no pow, whose last bit
+    differs between libraries); out = min(255, floor(photo shade + highlight + 0.5)) per byte. A pixel without a normal keeps the photo's bytes.
+    images_bgr=None with target_hws: a white-clay hillshade (every photo byte is 255). return_normals: -> (frames, fp32 [H_i,W_i,3] normals). The defaults
+    (ambient 0.35, diffuse 0.9, no highlight) are user-facing choices, not measured optima. predictions / images_bgr as refocus_images takes them: host photos
+    go through pinned staging, CUDA photos and pitched slices are read in place byte by byte, a photo may have any size relative to its map. fp64 arithmetic,
+    bit-deterministic, at most three launches whatever the number of pairs and lights, nothing read back. Limits (gamma-space mix of a photo that carries its
+    own lighting, no cast shadows, no ambient occlusion): see this module's docstring."""
+    what = "relight_images"
+    checked = _normals_checked(predictions, target_hws, images_bgr, space, fov_deg, min_depth, max_depth, step, edge_ratio, what)
+    shading = _shading_checked(ambient, diffuse, specular, shininess_log2, what)
+    lights = _unit_lights(light_dirs, what)
+    normals, _, frames = _run(predictions, images_bgr, checked, space, what, lights, shading, bool(return_normals), False)
+    return (frames, normals) if return_normals else frames

@@ -25,6 +25,11 @@ For one image or several, --refocus FOCUS APERTURE saves every photo refocused b
 the whole list; FOCUS = the focal plane, 0 .. 1 of the map's range or, for a metric model, a depth; APERTURE = photo pixels of blur radius per unit of
 defocus, e.g. 0.8 32): <name>_refocus.png in the current directory. --refocus_at X Y focuses on the point (X, Y) of the photo, normalised, instead of
 FOCUS; --refocus_radius R is the largest blur radius (0 .. 32, default 16); --refocus_guided RADIUS EPS enlarges the depth with the photo as the guide first.
+For one image or several, --normals saves every photo's encoded surface normal map (relight.depth_normals at the photo's size; B, G, R = z, y, x):
+<name>_normals.png in the current directory. --relight X Y Z saves every photo shaded by its normals with a light towards (X, Y, Z) in the camera frame
+(x right, y up, z towards the camera; relight.relight_images, one call for the whole list): <name>_relit000.png; --relight_sweep N instead writes N frames
+<name>_relit###.png for a ring of N lights at the elevation of (X, Y, Z), starting at its azimuth; --relight_guided RADIUS EPS enlarges the depth with the
+photo as the guide first (and takes the normals over one photo pixel).
 --stable [ALPHA] takes the images, in order, as the frames of ONE clip (they share a size): DPTModel.inference_video aligns every frame's map to the
 frame before it and filters the clip over time (muggled_dpt_amd.video; ALPHA = the filter's weight, default 0.3), video_display shows it with a
 carried range: <name>_stable.npy (fp32, the model's map size) and <name>_stable.png (the photo's size) into --output (a directory; default: the
@@ -87,6 +92,11 @@ def main():
     ap.add_argument("--refocus_at", type=float, nargs=2, default=None, metavar=("X", "Y"), help="refocus: focus on this point of the photo (normalised) instead of FOCUS")
     ap.add_argument("--refocus_radius", type=int, default=16, metavar="R", help="refocus: the largest blur radius in photo pixels, 0 .. 32")
     ap.add_argument("--refocus_guided", nargs=2, default=None, metavar=("RADIUS", "EPS"), help="refocus: enlarge the depth with the photo as the guide first")
+    ap.add_argument("--normals", action="store_true", help="save every photo's encoded surface normal map, <name>_normals.png")
+    ap.add_argument("--relight", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="save every photo relit from the direction (X, Y, Z) "
+                    "(x right, y up, z towards the camera), e.g. -1 1 1")
+    ap.add_argument("--relight_sweep", type=int, default=None, metavar="N", help="relight: N frames for a ring of lights at the elevation of (X, Y, Z)")
+    ap.add_argument("--relight_guided", nargs=2, default=None, metavar=("RADIUS", "EPS"), help="normals / relight: enlarge the depth with the photo as the guide first")
     ap.add_argument("--truth", default=None, metavar="DIR", help="measured depth per image, DIR/<name>.npy (fp32, any size; zero or NaN: no measurement): "
                     "fit the prediction to it, save <name>_true.npy (true depth at the truth's size) and <name>_metrics.json")
     ap.add_argument("--truth_method", default="lstsq", choices=("lstsq", "median"), help="truth: least squares, or median and mean absolute deviation")
@@ -154,6 +164,7 @@ def main():
     save_true_depth(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [depth])
     save_guided(args, args.image_path or ["synthetic.npy"], [img], [depth])
     save_refocus(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
+    save_relight(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
 
 
 def crop_argument(args):
@@ -303,6 +314,40 @@ def save_refocus(args, is_metric, paths, images, depths):
         print("saved", out, f"({bgr.shape[1]}x{bgr.shape[0]}, {where}, aperture {args.refocus[1]:g}, radius <= {args.refocus_radius})")
 
 
+def save_relight(args, is_metric, paths, images, depths):
+    """--normals / --relight: one relight.depth_normals and / or one relight.relight_images call over all images (after one guided_upsample_images call with
+    --relight_guided), PNGs per photo"""
+    if not (args.normals or args.relight):
+        return
+    import math
+    from muggled_dpt_amd import mesh_io
+    from muggled_dpt_amd.relight import depth_normals, light_sweep, relight_images
+    step = None
+    if args.relight_guided:
+        from muggled_dpt_amd.postprocess import guided_upsample_images
+        depths, step = guided_upsample_images(depths, images, int(args.relight_guided[0]), float(args.relight_guided[1])), 1
+    space = "depth" if is_metric else "inverse"
+
+    def save(out, bgr, note):
+        with open(out, "wb") as fh:
+            fh.write(mesh_io.encode_png(np.ascontiguousarray(bgr.cpu().numpy()[:, :, ::-1])))
+        print("saved", out, f"({bgr.shape[1]}x{bgr.shape[0]}, {note})")
+
+    if args.normals:
+        for path, bgr in zip(paths, depth_normals(depths, None, images, space=space, step=step, encode=True)[1]):
+            save(os.path.splitext(os.path.basename(path))[0] + "_normals.png", bgr, "normal map")
+    if args.relight:
+        x, y, z = args.relight
+        lights = [args.relight]
+        if args.relight_sweep:
+            ring = light_sweep(args.relight_sweep, math.degrees(math.atan2(z, math.hypot(x, y))))
+            turn = math.atan2(y, x)  # the ring starts at the given light's azimuth
+            lights = [(math.cos(turn) * lx - math.sin(turn) * ly, math.sin(turn) * lx + math.cos(turn) * ly, lz) for lx, ly, lz in ring.tolist()]
+        for path, frames in zip(paths, relight_images(depths, images, lights, space=space, step=step)):
+            for k, bgr in enumerate(frames):
+                save(os.path.splitext(os.path.basename(path))[0] + f"_relit{k:03d}.png", bgr, f"light {tuple(round(v, 3) for v in lights[k])}")
+
+
 def save_block_norms(model, args, paths, images):
     """--block_norms: one DPTModel.block_norms call per group of images that share a model tensor size"""
     if not args.block_norms:
@@ -361,6 +406,7 @@ def run_images(model, args, t0, is_metric=False):
     save_true_depth(args, is_metric, args.image_path, depths)
     save_guided(args, args.image_path, images, depths)
     save_refocus(args, is_metric, args.image_path, images, depths)
+    save_relight(args, is_metric, args.image_path, images, depths)
 
 
 def run_clip(model, args):
