@@ -815,6 +815,52 @@ int mdpt_post_normals(const mdpt_normals_pair* records_host, const void* records
                       double max_depth, double edge_ratio, const void* lights_dev, int32_t num_lights, double ambient, double diffuse, double specular,
                       int32_t shininess_log2, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Cast shadows and ambient occlusion for the relighting, on the device (additive to ABI v6; not in the reference): screen-space shadow marches and
+ * horizon occlusion on a small working grid of gh x gw nodes per pair, resized to the photo and folded into the shading of mdpt_post_normals. n pairs of
+ * any sizes in one call, at most four launches whatever n and num_lights are (inverse space: min / max, per-pair state; the grid kernel; the shade
+ * kernel), nothing read back, nothing synchronises, no atomics, bit-deterministic, every pair independent of the others. A pair is an mdpt_shadows_pair
+ * record: map, h, w, photo, pitch, H, W, scratch_off (1024 bytes a pair), tile_off, kx, ky (the PHOTO's) and step as in mdpt_normals_pair; gh, gw = the
+ * working grid (any positive size, gh gw < 2^31; node (i, j) is pixel (i, j) of a gh x gw image over the photo's field of view); gtile_off = the sum over
+ * the pairs before it of ceil(gh / 32) ceil(gw / 32); and three outputs, each NULL in every record or in none: ao fp32 [gh,gw], vis fp32
+ * [num_lights,gh,gw] (4-byte aligned), relit uint8 [num_lights,H,W,3]. With relit the planes are the call's working memory as well: vis is required
+ * where shadow_reach > 0, ao where ao_reach > 0 and ao_strength > 0; without relit the call computes the planes alone. lights_dev as for
+ * mdpt_post_normals. All arithmetic is fp64, nothing contracted, only + - * / sqrt floor and comparisons, every stored value rounded once.
+ * Per grid node (i, j):
+ *   depth ......... s = the map at the node's centre (the sample rule of mdpt_post_normals with H, W := gh, gw; a map of the grid's size is read
+ *                   directly), z by its depth rule (lo, hi are the map's), x0 = 2 (j + 0.5) / gw - 1, y0 = 1 - 2 (i + 0.5) / gh,
+ *                   P = ((z x0) kx, (z y0) ky, -z). n = the normal of mdpt_post_normals on the grid at a step of one node with edge_ratio. A node
+ *                   without z or without n has ao = 1 and vis = 1 for every light.
+ *   occlusion ..... the eight directions (di, dj) = (0,1) (-1,1) (-1,0) (-1,-1) (0,-1) (1,-1) (1,0) (1,1) in this order; for k = 1 .. ao_reach:
+ *                   q = (i + k di, j + k dj); off the grid ends the direction, an invalid q is skipped; D = P_q - P_0, l2 = (Dx Dx + Dy Dy) + Dz Dz,
+ *                   hgt = ((Dx nx + Dy ny) + Dz nz) / sqrt(l2), fall = 1 - l2 / (rad rad) with rad = ao_radius z_0, rise = hgt - ao_bias,
+ *                   term = (rise > 0 ? rise : 0) (fall > 0 ? fall : 0); occ_d = the largest term (a term that is not > the running maximum, which
+ *                   starts at 0, is dropped). sum = (((0 + occ_0) + occ_1) + ...) + occ_7, open = 1 - (ao_strength sum) / 8,
+ *                   ao = fp32(open > 0 ? open : 0).
+ *   shadow ........ per light L: gx = (Lx / kx + x0 Lz) gw, gy = -((Ly / ky + y0 Lz) gh), the projected direction of the ray P_0 + t L. Both zero, or
+ *                   either not finite: lit. Else the major axis c is x if |gx| >= |gy|, else y; m = |g_c|, sx = gx / m, sy = gy / m. For
+ *                   k = 1 .. shadow_reach: q = (i + floor(k sy + 0.5), j + floor(k sx + 0.5)); off the grid: lit, the march ends. cq = x or y of q
+ *                   (formed as x0 / y0 are), t = ((z_0 k_c) (cq - c_0)) / (L_c + (Lz k_c) cq), zr = z_0 - t Lz; t not > 0 or zr not > 0: lit, ends.
+ *                   q occludes iff z_q is valid and z_q < zr (1 - shadow_bias) and (shadow_thickness = inf or zr - z_q <= shadow_thickness zr); the
+ *                   first occluder sets vis = 0 and ends the march. vis is 0 or 1.
+ * Per photo pixel (Y, X): the normal, d, sp, the photo bytes and the invalid pixels of mdpt_post_normals, with a = the ao plane and s_v = light v's vis
+ * plane at the pixel's centre (the sample rule again, fp32 planes of gh x gw under an H x W photo; the constant 1 where the factor is off, no plane
+ * read): shade = ambient a + (diffuse (d > 0 ? d : 0)) s_v, spec = 255 ((specular sp) s_v), relit_c = min(255, floor((photo_c shade + spec) + 0.5)).
+ * With shadow_reach = 0 and ao_strength = 0 (or ao_reach = 0) every byte equals mdpt_post_normals'.
+ * Checks (MDPT_E_INVALID, nothing launched): those of mdpt_post_normals on the shared arguments, and shadow_reach / ao_reach outside 0 ..
+ * MDPT_SHADOWS_MAX_REACH, shadow_bias outside [0, 1), shadow_thickness negative or NaN, ao_radius not finite or <= 0, ao_bias or ao_strength negative
+ * or not finite, a bad grid size, a wrong gtile_off, misaligned planes, a plane in some records only, a plane the shading needs missing, vis or relit
+ * without lights, no output at all. Known limits: screen space only - what lies outside the frame or behind the first surface casts nothing; the
+ * thickness of an occluder is assumed; a march reaches at most 32 grid nodes; the bilinear resize of the planes is the only penumbra; the mix is on
+ * the gamma-encoded bytes. */
+#define MDPT_SHADOWS_MAX_REACH 32
+#define MDPT_SHADOWS_AO_DIRECTIONS 8
+typedef struct mdpt_shadows_pair { const void* map; int32_t h, w; const void* photo; int64_t pitch; int32_t H, W, gh, gw; void* ao; void* vis; void* relit; int64_t scratch_off, tile_off, gtile_off; double kx, ky; int32_t step, pad; } mdpt_shadows_pair;
+int mdpt_post_shadows_scratch_bytes(const mdpt_shadows_pair* records_host, int32_t n, size_t* bytes);
+int mdpt_post_shadows(const mdpt_shadows_pair* records_host, const void* records_dev, int32_t n, int32_t dtype, int32_t space, double min_depth,
+                      double max_depth, double edge_ratio, const void* lights_dev, int32_t num_lights, double ambient, double diffuse, double specular,
+                      int32_t shininess_log2, int32_t shadow_reach, double shadow_bias, double shadow_thickness, int32_t ao_reach, double ao_radius,
+                      double ao_bias, double ao_strength, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

@@ -477,6 +477,29 @@ struct NormalsJob {
 };
 int mdpt_launch_post_normals(const NormalsJob& job, hipStream_t stream);
 
+// cast shadows and ambient occlusion for the relighting (post_shadows.inc; a pair = mdpt_shadows_pair of include/mdpt.h): a NormalsPair's map, photo, relit
+// frames, scratch header, photo tiles, camera and step, and the pair's working grid of gh x gw nodes with its planes - ao fp32 [gh,gw] and vis fp32
+// [V,gh,gw], each null in every record or in none - and gtile_off, the 32 x 32 grid tiles of the pairs before it. Device table, indexed by pair.
+struct ShadowsPair {
+    const void* map; int h, w; const unsigned char* photo; long long pitch; int H, W, gh, gw; float* ao; float* vis; unsigned char* relit;
+    long long scratch_off, tile_off, gtile_off; double kx, ky; int step, pad;
+};
+#define SHADOWS_MAX_REACH 32     // grid nodes a shadow march or an occlusion direction walks at most: the halo of the grid kernel's LDS image
+#define SHADOWS_AO_DIRECTIONS 8
+// one call: the fields of a NormalsJob under their names (the shade kernel is normals_tile_kernel's body), the marches' controls and which planes the
+// shade kernel reads (use_vis: shadow_reach > 0; use_ao: ao_reach > 0 and ao_strength > 0; else the factor is the constant 1). At most four launches.
+struct ShadowsJob {
+    const ShadowsPair* pairs;
+    int P, dt, depth_space, central_only, V, shininess_log2;
+    double depth_a, depth_b, edge_ratio, ambient, diffuse, specular;
+    const double* lights;
+    char* scratch;
+    size_t total_tiles, total_gtiles;
+    int shadow_reach, ao_reach, thick_inf, use_vis, use_ao, planes, shade, pad;
+    double shadow_bias, shadow_thickness, ao_radius, ao_bias, ao_strength;
+};
+int mdpt_launch_post_shadows(const ShadowsJob& job, hipStream_t stream);
+
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);
 

@@ -952,4 +952,115 @@ int mdpt_post_normals(const mdpt_normals_pair* records_host, const void* records
     return 0;
 }
 
+// ---- cast shadows and ambient occlusion for the relighting (marches on a working grid, folded into the shading; not in the reference)
+static_assert(sizeof(mdpt_shadows_pair) == sizeof(ShadowsPair) && sizeof(mdpt_shadows_pair) == 120, "mdpt_shadows_pair of include/mdpt.h is ShadowsPair of mdpt_kernels.h");
+static_assert(offsetof(mdpt_shadows_pair, photo) == offsetof(ShadowsPair, photo) && offsetof(mdpt_shadows_pair, pitch) == offsetof(ShadowsPair, pitch) &&
+              offsetof(mdpt_shadows_pair, H) == offsetof(ShadowsPair, H) && offsetof(mdpt_shadows_pair, gh) == offsetof(ShadowsPair, gh) &&
+              offsetof(mdpt_shadows_pair, gw) == offsetof(ShadowsPair, gw) && offsetof(mdpt_shadows_pair, ao) == offsetof(ShadowsPair, ao) &&
+              offsetof(mdpt_shadows_pair, vis) == offsetof(ShadowsPair, vis) && offsetof(mdpt_shadows_pair, relit) == offsetof(ShadowsPair, relit) &&
+              offsetof(mdpt_shadows_pair, scratch_off) == offsetof(ShadowsPair, scratch_off) && offsetof(mdpt_shadows_pair, tile_off) == offsetof(ShadowsPair, tile_off) &&
+              offsetof(mdpt_shadows_pair, gtile_off) == offsetof(ShadowsPair, gtile_off) && offsetof(mdpt_shadows_pair, kx) == offsetof(ShadowsPair, kx) &&
+              offsetof(mdpt_shadows_pair, ky) == offsetof(ShadowsPair, ky) && offsetof(mdpt_shadows_pair, step) == 112 && offsetof(ShadowsPair, step) == 112,
+              "mdpt_shadows_pair of include/mdpt.h is ShadowsPair of mdpt_kernels.h, field by field");
+static_assert(MDPT_SHADOWS_MAX_REACH == SHADOWS_MAX_REACH && MDPT_SHADOWS_AO_DIRECTIONS == SHADOWS_AO_DIRECTIONS, "the shadow limits of include/mdpt.h are those of mdpt_kernels.h");
+
+// the host table's photo and grid sizes: positive, fewer than 2^31 pixels / nodes; *bytes = the scratch of the P regions laid end to end
+static int check_shadows_sizes(const mdpt_shadows_pair* pairs, int32_t P, size_t* bytes) {
+    if (!pairs) return fail(MDPT_E_INVALID, "null argument (records)");
+    if (P <= 0 || P > 65535) return fail(MDPT_E_INVALID, "bad pair count n = %d (1 .. 65535 per call)", P);
+    for (int p = 0; p < P; ++p) {
+        const mdpt_shadows_pair& q = pairs[p];
+        if (q.H <= 0 || q.W <= 0) return fail(MDPT_E_INVALID, "bad photo size %dx%d (pair %d)", q.H, q.W, p);
+        if ((size_t)q.H * q.W >= ((size_t)1 << 31)) return fail(MDPT_E_INVALID, "a photo of %dx%d is too large (H W < 2^31 pixels, pair %d)", q.H, q.W, p);
+        if (q.gh <= 0 || q.gw <= 0 || (size_t)q.gh * q.gw >= ((size_t)1 << 31))
+            return fail(MDPT_E_INVALID, "bad working grid %dx%d (pair %d; positive, gh gw < 2^31 nodes)", q.gh, q.gw, p);
+    }
+    *bytes = (size_t)P * NORMALS_HEADER_BYTES;
+    return 0;
+}
+
+int mdpt_post_shadows_scratch_bytes(const mdpt_shadows_pair* records_host, int32_t n, size_t* bytes) {
+    if (!bytes) return fail(MDPT_E_INVALID, "null argument (bytes)");
+    return check_shadows_sizes(records_host, n, bytes);
+}
+
+int mdpt_post_shadows(const mdpt_shadows_pair* records_host, const void* records_dev, int32_t n, int32_t dtype, int32_t space, double min_depth,
+                      double max_depth, double edge_ratio, const void* lights_dev, int32_t num_lights, double ambient, double diffuse, double specular,
+                      int32_t shininess_log2, int32_t shadow_reach, double shadow_bias, double shadow_thickness, int32_t ao_reach, double ao_radius,
+                      double ao_bias, double ao_strength, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!records_host || !records_dev || !scratch) return fail(MDPT_E_INVALID, "null argument (records_host, records_dev or scratch)");
+    if (!tensor_dtype_ok(dtype)) return fail(MDPT_E_INVALID, "bad tensor dtype %d", dtype);
+    if (space != MDPT_ALIGN_INVERSE && space != MDPT_ALIGN_DEPTH) return fail(MDPT_E_INVALID, "unknown shadows space %d", space);
+    size_t packed;
+    CHK(check_shadows_sizes(records_host, n, &packed));
+    if (space == MDPT_ALIGN_INVERSE && !(min_depth > 0.0 && min_depth < max_depth && max_depth <= 1e300))
+        return fail(MDPT_E_INVALID, "need 0 < min_depth < max_depth, finite, in inverse space, got %g, %g", min_depth, max_depth);
+    if (!(edge_ratio >= 1.0)) return fail(MDPT_E_INVALID, "edge_ratio must be >= 1 (inf: always the central difference), got %g", edge_ratio);
+    if (num_lights < 0 || num_lights > NORMALS_MAX_LIGHTS) return fail(MDPT_E_INVALID, "bad light count num_lights = %d (0 .. %d per call)", num_lights, NORMALS_MAX_LIGHTS);
+    if (!(ambient >= 0.0 && ambient <= 1e300 && diffuse >= 0.0 && diffuse <= 1e300 && specular >= 0.0 && specular <= 1e300))
+        return fail(MDPT_E_INVALID, "ambient, diffuse and specular must be finite and >= 0, got %g, %g, %g", ambient, diffuse, specular);
+    if (shininess_log2 < 0 || shininess_log2 > 10) return fail(MDPT_E_INVALID, "shininess_log2 %d: the number of squarings must be 0 .. 10", shininess_log2);
+    if (shadow_reach < 0 || shadow_reach > SHADOWS_MAX_REACH) return fail(MDPT_E_INVALID, "shadow_reach %d: a shadow march takes 0 .. %d grid nodes", shadow_reach, SHADOWS_MAX_REACH);
+    if (ao_reach < 0 || ao_reach > SHADOWS_MAX_REACH) return fail(MDPT_E_INVALID, "ao_reach %d: an occlusion direction takes 0 .. %d grid nodes", ao_reach, SHADOWS_MAX_REACH);
+    if (!(shadow_bias >= 0.0 && shadow_bias < 1.0)) return fail(MDPT_E_INVALID, "shadow_bias must be in [0, 1), got %g", shadow_bias);
+    if (!(shadow_thickness >= 0.0)) return fail(MDPT_E_INVALID, "shadow_thickness must be >= 0 (inf: an occluder of any thickness), got %g", shadow_thickness);
+    if (!(ao_radius > 0.0 && ao_radius <= 1e300)) return fail(MDPT_E_INVALID, "ao_radius must be finite and > 0, got %g", ao_radius);
+    if (!(ao_bias >= 0.0 && ao_bias <= 1e300 && ao_strength >= 0.0 && ao_strength <= 1e300))
+        return fail(MDPT_E_INVALID, "ao_bias and ao_strength must be finite and >= 0, got %g, %g", ao_bias, ao_strength);
+    if ((((uintptr_t)records_dev | (uintptr_t)scratch | (uintptr_t)lights_dev) & 7) != 0)
+        return fail(MDPT_E_INVALID, "misaligned pointer (the table, the lights and the scratch need 8 bytes)");
+    size_t tiles = 0, gtiles = 0;
+    int with_ao = 0, with_vis = 0, with_relit = 0, with_photo = 0;
+    std::vector<std::pair<size_t, size_t>> regions;
+    for (int p = 0; p < n; ++p) {
+        const mdpt_shadows_pair& q = records_host[p];
+        if (!q.map) return fail(MDPT_E_INVALID, "null map (pair %d)", p);
+        if (((uintptr_t)q.map & (dtype_bytes(dtype) - 1)) != 0) return fail(MDPT_E_INVALID, "misaligned map (pair %d: it needs its element)", p);
+        if (q.h <= 0 || q.w <= 0 || (size_t)q.h * q.w >= ((size_t)1 << 31)) return fail(MDPT_E_INVALID, "bad map size %dx%d (pair %d; h w < 2^31)", q.h, q.w, p);
+        if (q.photo && q.pitch < 3 * (int64_t)q.W)
+            return fail(MDPT_E_INVALID, "a row pitch of %lld bytes is less than the %d pixels of a row (pair %d)", (long long)q.pitch, q.W, p);
+        if (q.step < 1 || q.step > NORMALS_MAX_STEP) return fail(MDPT_E_INVALID, "step %d of pair %d: the difference step must be 1 .. %d photo pixels", q.step, p, NORMALS_MAX_STEP);
+        if (!(q.kx > 0.0 && q.kx <= 1e300 && q.ky > 0.0 && q.ky <= 1e300)) return fail(MDPT_E_INVALID, "the camera scales kx, ky of pair %d must be finite and > 0, got %g, %g", p, q.kx, q.ky);
+        if ((((uintptr_t)q.ao | (uintptr_t)q.vis) & 3) != 0) return fail(MDPT_E_INVALID, "misaligned ao or vis plane (pair %d: fp32)", p);
+        if (q.scratch_off < 0 || (q.scratch_off & 7) != 0 || (size_t)q.scratch_off > scratch_bytes || scratch_bytes - (size_t)q.scratch_off < NORMALS_HEADER_BYTES)
+            return fail(MDPT_E_INVALID, "the scratch region of pair %d (offset %lld, %d bytes) is misaligned or outside the %zu bytes of scratch given "
+                        "(mdpt_post_shadows_scratch_bytes)", p, (long long)q.scratch_off, NORMALS_HEADER_BYTES, scratch_bytes);
+        if (q.tile_off != (int64_t)tiles)
+            return fail(MDPT_E_INVALID, "tile_off %lld of pair %d is not the %zu tiles of %dx%d pixels of the pairs before it", (long long)q.tile_off, p, tiles,
+                        NORMALS_TILE, NORMALS_TILE);
+        if (q.gtile_off != (int64_t)gtiles)
+            return fail(MDPT_E_INVALID, "gtile_off %lld of pair %d is not the %zu tiles of %dx%d grid nodes of the pairs before it", (long long)q.gtile_off, p,
+                        gtiles, NORMALS_TILE, NORMALS_TILE);
+        regions.emplace_back((size_t)q.scratch_off, (size_t)q.scratch_off + NORMALS_HEADER_BYTES);
+        tiles += normals_pair_tiles((size_t)q.H, (size_t)q.W);
+        gtiles += normals_pair_tiles((size_t)q.gh, (size_t)q.gw);
+        with_ao += q.ao != nullptr, with_vis += q.vis != nullptr, with_relit += q.relit != nullptr, with_photo += q.photo != nullptr;
+    }
+    for (int got : {with_ao, with_vis, with_relit})
+        if (got != 0 && got != n) return fail(MDPT_E_INVALID, "an output is null in %d of %d records: every pair has it, or none", n - got, n);
+    if (!with_ao && !with_vis && !with_relit) return fail(MDPT_E_INVALID, "null argument: no record has an output (ao, vis or relit)");
+    if ((with_relit || with_vis) && (num_lights < 1 || !lights_dev))
+        return fail(MDPT_E_INVALID, "vis planes or relit frames are asked for without lights (lights_dev null or num_lights = %d)", num_lights);
+    const bool use_vis = shadow_reach > 0, use_ao = ao_reach > 0 && ao_strength > 0.0;
+    if (with_relit && ((use_vis && !with_vis) || (use_ao && !with_ao)))
+        return fail(MDPT_E_INVALID, "the shading needs a plane that no record has (vis with shadow_reach > 0, ao with ao_reach > 0 and ao_strength > 0)");
+    if (with_photo != 0 && with_photo != n) return fail(MDPT_E_INVALID, "photo is null in %d of %d records: every pair has a photo, or none (white clay)", n - with_photo, n);
+    if (tiles >= ((size_t)1 << 31) || gtiles >= ((size_t)1 << 31)) return fail(MDPT_E_INVALID, "%zu photo tiles, %zu grid tiles: a call takes fewer than 2^31 of each", tiles, gtiles);
+    std::sort(regions.begin(), regions.end());
+    for (size_t k = 1; k < regions.size(); ++k)
+        if (regions[k].first < regions[k - 1].second) return fail(MDPT_E_INVALID, "the scratch regions of two pairs overlap (at byte %zu)", regions[k].first);
+    ShadowsJob j{};
+    j.pairs = (const ShadowsPair*)records_dev;
+    j.P = n, j.dt = dtype, j.depth_space = space == MDPT_ALIGN_DEPTH, j.central_only = edge_ratio > 1e300, j.V = (with_relit || with_vis) ? num_lights : 0;
+    j.shininess_log2 = shininess_log2;
+    if (!j.depth_space) j.depth_a = 1.0 / max_depth, j.depth_b = 1.0 / min_depth - 1.0 / max_depth;
+    j.edge_ratio = edge_ratio, j.ambient = ambient, j.diffuse = diffuse, j.specular = specular;
+    j.lights = (const double*)lights_dev, j.scratch = (char*)scratch, j.total_tiles = tiles, j.total_gtiles = gtiles;
+    j.shadow_reach = shadow_reach, j.ao_reach = ao_reach, j.thick_inf = shadow_thickness > 1e300, j.use_vis = use_vis, j.use_ao = use_ao;
+    j.planes = with_ao || with_vis, j.shade = with_relit != 0;
+    j.shadow_bias = shadow_bias, j.shadow_thickness = shadow_thickness, j.ao_radius = ao_radius, j.ao_bias = ao_bias, j.ao_strength = ao_strength;
+    CHK(mdpt_launch_post_shadows(j, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

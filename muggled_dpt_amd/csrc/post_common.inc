@@ -247,13 +247,14 @@ __device__ __forceinline__ bool finite_range(unsigned lo_o, unsigned hi_o, doubl
     return any && hi > lo;
 }
 
-// the pair that owns tile `tile` of a call: the last record whose tile_off (the tiles of the pairs before it) is not beyond it
+// the pair that owns tile `tile` of a call: the last record whose tile_off (the tiles of the pairs before it) is not beyond it; `off`: the field that
+// counts them, for a record with more than one tiling
 template <typename Pair>
-__device__ __forceinline__ int pair_of_tile(const Pair* __restrict__ pairs, int P, long long tile) {
+__device__ __forceinline__ int pair_of_tile(const Pair* __restrict__ pairs, int P, long long tile, long long Pair::*off = &Pair::tile_off) {
     int a = 0, b = P - 1;
     while (a < b) {
         const int mid = (a + b + 1) >> 1;
-        if (pairs[mid].tile_off <= tile) a = mid;
+        if (pairs[mid].*off <= tile) a = mid;
         else b = mid - 1;
     }
     return a;

@@ -27,8 +27,11 @@ static_assert(NORMALS_PARTS * 2 * sizeof(unsigned) + sizeof(NormalsState) <= NOR
 static_assert(NORMALS_PARTS == 64, "normals_state_kernel reduces the partials with one wave");
 static_assert(NORMALS_TILE + 2 * NORMALS_MAX_STEP == 64, "the LDS image of normals_tile_kernel");
 
-__device__ __forceinline__ unsigned* normals_parts(const NormalsPair& p, char* scratch) { return (unsigned*)(scratch + p.scratch_off); }
-__device__ __forceinline__ NormalsState* normals_state(const NormalsPair& p, char* scratch) {
+// (Pair: NormalsPair, or the ShadowsPair of post_shadows.inc, whose header is laid out alike)
+template <typename Pair>
+__device__ __forceinline__ unsigned* normals_parts(const Pair& p, char* scratch) { return (unsigned*)(scratch + p.scratch_off); }
+template <typename Pair>
+__device__ __forceinline__ NormalsState* normals_state(const Pair& p, char* scratch) {
     return (NormalsState*)(scratch + p.scratch_off + NORMALS_PARTS * 2 * sizeof(unsigned));
 }
 
@@ -38,9 +41,9 @@ __global__ __launch_bounds__(256) void normals_minmax_kernel(const NormalsPair* 
     finite_minmax_part(p.map, (size_t)p.h * p.w, dt, blockIdx.x, NORMALS_PARTS, normals_parts(p, scratch) + 2 * blockIdx.x);
 }
 
-// (2) blockIdx.x = pair, one wave
-__global__ __launch_bounds__(64) void normals_state_kernel(const NormalsPair* __restrict__ pairs, char* __restrict__ scratch) {
-    const NormalsPair p = pairs[blockIdx.x];
+// the body of launch (2): one wave reduces the partials of pair p and lane 0 stores its state
+template <typename Pair>
+__device__ __forceinline__ void normals_state_of(const Pair& p, char* __restrict__ scratch) {
     const unsigned* parts = normals_parts(p, scratch);
     unsigned lo_o = parts[2 * threadIdx.x], hi_o = parts[2 * threadIdx.x + 1];
 #pragma unroll
@@ -54,10 +57,17 @@ __global__ __launch_bounds__(64) void normals_state_kernel(const NormalsPair* __
     *normals_state(p, scratch) = st;
 }
 
+// (2) blockIdx.x = pair, one wave
+__global__ __launch_bounds__(64) void normals_state_kernel(const NormalsPair* __restrict__ pairs, char* __restrict__ scratch) {
+    normals_state_of(pairs[blockIdx.x], scratch);
+}
+
 struct NormalsVec { double x, y, z; };
 
-// the camera-space point of photo pixel (Y, X) at depth z
-__device__ __forceinline__ NormalsVec normals_point(const NormalsPair& p, double z, int Y, int X) {
+// the camera-space point of pixel (Y, X) of an H x W image at depth z (Cam: anything with H, W, kx, ky - a pair, or the working grid of post_shadows.inc)
+struct NormalsCam { int H, W; double kx, ky; };
+template <typename Cam>
+__device__ __forceinline__ NormalsVec normals_point(const Cam& p, double z, int Y, int X) {
 #pragma clang fp contract(off)
     const double x = 2.0 * ((double)X + 0.5) / (double)p.W - 1.0, y = 1.0 - 2.0 * ((double)Y + 0.5) / (double)p.H;
     return NormalsVec{(z * x) * p.kx, (z * y) * p.ky, -z};
@@ -71,7 +81,8 @@ __device__ __forceinline__ NormalsVec normals_sub(const NormalsVec& a, const Nor
 // The tangent along one axis: A = the neighbour at +step (x axis: X + step; y axis: Y - step, up), B the one at -step, a NaN depth = not usable.
 // Both usable: central where the two depth differences are within edge_ratio of each other, else the side with the smaller one; one usable: that side.
 // -> false where neither is.
-__device__ __forceinline__ bool normals_tangent(const NormalsJob& j, const NormalsPair& p, double z0, const NormalsVec& P0, double zA, int YA, int XA,
+template <typename Job, typename Cam>
+__device__ __forceinline__ bool normals_tangent(const Job& j, const Cam& p, double z0, const NormalsVec& P0, double zA, int YA, int XA,
                                                 double zB, int YB, int XB, NormalsVec& T) {
 #pragma clang fp contract(off)
     const bool useA = zA == zA, useB = zB == zB;
@@ -89,48 +100,42 @@ __device__ __forceinline__ bool normals_tangent(const NormalsJob& j, const Norma
     return true;
 }
 
-// (3) blockIdx.x = a tile of the call (pair_of_tile); thread = (ty, tx) of the tile, tx fastest
-__global__ __launch_bounds__(NORMALS_TILE* NORMALS_TILE) void normals_tile_kernel(NormalsJob j) {
+// the pair's depth range as the staging loops use it (inverse space: what launch (2) left; depth space: not read)
+struct NormalsRange { double lo, range; bool ranged; };
+template <typename Job, typename Pair>
+__device__ __forceinline__ NormalsRange normals_range(const Job& j, const Pair& p) {
 #pragma clang fp contract(off)
-    constexpr int T = NORMALS_TILE, S = T + 2 * NORMALS_MAX_STEP, THREADS = T * T;
-    __shared__ double zt[S * S];
-    __shared__ int which;
-    const int tid = (int)threadIdx.x;
-    if (tid == 0) which = pair_of_tile(j.pairs, j.P, (long long)blockIdx.x);
-    __syncthreads();
-    const NormalsPair p = j.pairs[which];
-    const int tile = (int)((long long)blockIdx.x - p.tile_off), tiles_x = (p.W + T - 1) / T;
-    const int X0 = (tile % tiles_x) * T, Y0 = (tile / tiles_x) * T;
-    const int t = p.step, side = T + 2 * t;  // (1 <= t <= NORMALS_MAX_STEP, checked on the host: side <= S)
-    double lo = 0.0, range = 0.0;
-    bool ranged = false;
+    NormalsRange r{0.0, 0.0, false};
     if (!j.depth_space) {
         const NormalsState st = *normals_state(p, j.scratch);
-        lo = st.lo, range = st.hi - st.lo, ranged = st.ranged != 0;
+        r.lo = st.lo, r.range = st.hi - st.lo, r.ranged = st.ranged != 0;
     }
-    for (int idx = tid; idx < side * side; idx += THREADS) {
-        const int ly = idx / side, lx = idx - ly * side;
-        if ((ly < t || ly >= t + T) && (lx < t || lx >= t + T)) continue;  // a corner of the halo: no tap reads it
-        const int Y = Y0 - t + ly, X = X0 - t + lx;
-        double z = NAN;  // outside the photo, or invalid
-        if (Y >= 0 && Y < p.H && X >= 0 && X < p.W) {
-            const double s = map_at_pixel_centre(p.map, j.dt, p.h, p.w, p.H, p.W, Y, X);
-            if (j.depth_space) {
-                if (isfinite(s) && s > 0.0) z = s;
-            } else if (isfinite(s)) {
-                const double v = ranged ? (s - lo) / range : 0.0;
-                z = 1.0 / (j.depth_a + j.depth_b * v);
-            }
-        }
-        zt[ly * S + lx] = z;
-    }
-    __syncthreads();
+    return r;
+}
 
-    const int tx = tid % T, ty = tid / T, X = X0 + tx, Y = Y0 + ty;
-    if (X >= p.W || Y >= p.H) return;
-    const double* centre = zt + (ty + t) * S + tx + t;
+// z of pixel (Y, X) of an H x W image over the pair's map, NaN where it lies outside the image or is invalid
+template <typename Job, typename Pair>
+__device__ __forceinline__ double normals_depth(const Job& j, const Pair& p, const NormalsRange& r, int H, int W, int Y, int X) {
+#pragma clang fp contract(off)
+    double z = NAN;
+    if (Y >= 0 && Y < H && X >= 0 && X < W) {
+        const double s = map_at_pixel_centre(p.map, j.dt, p.h, p.w, H, W, Y, X);
+        if (j.depth_space) {
+            if (isfinite(s) && s > 0.0) z = s;
+        } else if (isfinite(s)) {
+            const double v = r.ranged ? (s - r.lo) / r.range : 0.0;
+            z = 1.0 / (j.depth_a + j.depth_b * v);
+        }
+    }
+    return z;
+}
+
+// The normal of pixel (Y, X) from the staged depths: centre = its texel in an LDS image of row pitch S, the neighbours t texels away. -> whether it has
+// one; P0 is set where the centre is valid, n where the normal is.
+template <typename Job, typename Cam>
+__device__ __forceinline__ bool normals_at(const Job& j, const Cam& p, const double* centre, int S, int t, int Y, int X, NormalsVec& P0, NormalsVec& n) {
+#pragma clang fp contract(off)
     const double z0 = *centre;
-    NormalsVec P0{0.0, 0.0, 0.0}, n{0.0, 0.0, 0.0};
     bool valid = z0 == z0;
     if (valid) {
         P0 = normals_point(p, z0, Y, X);
@@ -147,16 +152,49 @@ __global__ __launch_bounds__(NORMALS_TILE* NORMALS_TILE) void normals_tile_kerne
             }
         }
     }
-    const size_t i = (size_t)Y * p.W + X;
-    if (p.normals) {
-        float* o = p.normals + 3 * i;
-        o[0] = (float)n.x, o[1] = (float)n.y, o[2] = (float)n.z;
+    return valid;
+}
+
+// The body of launch (3), blockIdx.x = a tile of the call (pair_of_tile); thread = (ty, tx) of the tile, tx fastest. OCC = false: normals_tile_kernel
+// (Job = NormalsJob). OCC = true: the shade kernel of post_shadows.inc (Job = ShadowsJob), the same pixel with the two factors of its planes in the mix -
+// shade = ambient a + (diffuse d) s_v, spec = 255 ((specular sp) s_v) - and no normals / encoded outputs.
+template <bool OCC, typename Job>
+__device__ __forceinline__ void normals_tile_body(const Job& j) {
+#pragma clang fp contract(off)
+    constexpr int T = NORMALS_TILE, S = T + 2 * NORMALS_MAX_STEP, THREADS = T * T;
+    __shared__ double zt[S * S];
+    __shared__ int which;
+    const int tid = (int)threadIdx.x;
+    if (tid == 0) which = pair_of_tile(j.pairs, j.P, (long long)blockIdx.x);
+    __syncthreads();
+    const auto p = j.pairs[which];  // (a NormalsPair, or a ShadowsPair)
+    const int tile = (int)((long long)blockIdx.x - p.tile_off), tiles_x = (p.W + T - 1) / T;
+    const int X0 = (tile % tiles_x) * T, Y0 = (tile / tiles_x) * T;
+    const int t = p.step, side = T + 2 * t;  // (1 <= t <= NORMALS_MAX_STEP, checked on the host: side <= S)
+    const NormalsRange range = normals_range(j, p);
+    for (int idx = tid; idx < side * side; idx += THREADS) {
+        const int ly = idx / side, lx = idx - ly * side;
+        if ((ly < t || ly >= t + T) && (lx < t || lx >= t + T)) continue;  // a corner of the halo: no tap reads it
+        zt[ly * S + lx] = normals_depth(j, p, range, p.H, p.W, Y0 - t + ly, X0 - t + lx);  // (NaN: outside the photo, or invalid)
     }
-    if (p.encoded) {
-        unsigned char* o = p.encoded + 3 * i;
-        o[0] = (unsigned char)floor((n.z + 1.0) / 2.0 * 255.0 + 0.5);
-        o[1] = (unsigned char)floor((n.y + 1.0) / 2.0 * 255.0 + 0.5);
-        o[2] = (unsigned char)floor((n.x + 1.0) / 2.0 * 255.0 + 0.5);
+    __syncthreads();
+
+    const int tx = tid % T, ty = tid / T, X = X0 + tx, Y = Y0 + ty;
+    if (X >= p.W || Y >= p.H) return;
+    NormalsVec P0{0.0, 0.0, 0.0}, n{0.0, 0.0, 0.0};
+    const bool valid = normals_at(j, p, zt + (ty + t) * S + tx + t, S, t, Y, X, P0, n);
+    const size_t i = (size_t)Y * p.W + X;
+    if constexpr (!OCC) {
+        if (p.normals) {
+            float* o = p.normals + 3 * i;
+            o[0] = (float)n.x, o[1] = (float)n.y, o[2] = (float)n.z;
+        }
+        if (p.encoded) {
+            unsigned char* o = p.encoded + 3 * i;
+            o[0] = (unsigned char)floor((n.z + 1.0) / 2.0 * 255.0 + 0.5);
+            o[1] = (unsigned char)floor((n.y + 1.0) / 2.0 * 255.0 + 0.5);
+            o[2] = (unsigned char)floor((n.x + 1.0) / 2.0 * 255.0 + 0.5);
+        }
     }
     if (!p.relit) return;
     unsigned c0 = 255u, c1 = 255u, c2 = 255u;
@@ -171,6 +209,24 @@ __global__ __launch_bounds__(NORMALS_TILE* NORMALS_TILE) void normals_tile_kerne
     }
     const size_t frame = (size_t)p.H * p.W * 3;
     unsigned char* o = p.relit + 3 * i;
+    // OCC: the pair's planes at the pixel's centre, by map_at_pixel_centre's rule with the taps formed once for the 1 + V planes
+    [[maybe_unused]] BilinearTaps taps{};
+    [[maybe_unused]] bool direct = false;
+    [[maybe_unused]] double amb = j.ambient;
+    [[maybe_unused]] auto plane_at = [&](const float* g) -> double {
+        if constexpr (OCC) {
+            if (direct) return (double)g[(size_t)Y * p.gw + X];
+            return bilinear_f64_mix(taps, (double)g[(size_t)taps.y0 * p.gw + taps.x0], (double)g[(size_t)taps.y0 * p.gw + taps.x1],
+                                    (double)g[(size_t)taps.y1 * p.gw + taps.x0], (double)g[(size_t)taps.y1 * p.gw + taps.x1]);
+        } else {
+            return 1.0;
+        }
+    };
+    if constexpr (OCC) {
+        direct = p.gh == p.H && p.gw == p.W;
+        if (valid && !direct && (j.use_ao || j.use_vis)) taps = bilinear_f64_taps(p.gh, p.gw, (double)X + 0.5, (double)Y + 0.5, p.H, p.W);
+        if (valid && j.use_ao) amb = j.ambient * plane_at(p.ao);
+    }
     for (int v = 0; v < j.V; ++v, o += frame) {
         if (!valid) {
             o[0] = (unsigned char)c0, o[1] = (unsigned char)c1, o[2] = (unsigned char)c2;
@@ -178,7 +234,13 @@ __global__ __launch_bounds__(NORMALS_TILE* NORMALS_TILE) void normals_tile_kerne
         }
         const double lx = j.lights[3 * v], ly = j.lights[3 * v + 1], lz = j.lights[3 * v + 2];
         const double dot = (n.x * lx + n.y * ly) + n.z * lz;
-        const double shade = j.ambient + j.diffuse * (dot > 0.0 ? dot : 0.0);
+        double shade, sv = 1.0;
+        if constexpr (OCC) {
+            if (j.use_vis) sv = plane_at(p.vis + (size_t)v * p.gh * p.gw);
+            shade = amb + (j.diffuse * (dot > 0.0 ? dot : 0.0)) * sv;
+        } else {
+            shade = j.ambient + j.diffuse * (dot > 0.0 ? dot : 0.0);
+        }
         double spec = 0.0;
         if (j.specular > 0.0) {
             const double hx = lx + view.x, hy = ly + view.y, hz = lz + view.z;
@@ -186,13 +248,16 @@ __global__ __launch_bounds__(NORMALS_TILE* NORMALS_TILE) void normals_tile_kerne
             const double nh = (n.x * (hx / hlen) + n.y * (hy / hlen)) + n.z * (hz / hlen);
             double sp = nh > 0.0 ? nh : 0.0;  // (a NaN - the light straight behind the view - is 0)
             for (int k = 0; k < j.shininess_log2; ++k) sp = sp * sp;
-            spec = 255.0 * (j.specular * sp);
+            spec = OCC ? 255.0 * ((j.specular * sp) * sv) : 255.0 * (j.specular * sp);
         }
         o[0] = (unsigned char)fmin(255.0, floor(((double)c0 * shade + spec) + 0.5));
         o[1] = (unsigned char)fmin(255.0, floor(((double)c1 * shade + spec) + 0.5));
         o[2] = (unsigned char)fmin(255.0, floor(((double)c2 * shade + spec) + 0.5));
     }
 }
+
+// (3)
+__global__ __launch_bounds__(NORMALS_TILE* NORMALS_TILE) void normals_tile_kernel(NormalsJob j) { normals_tile_body<false>(j); }
 
 }  // namespace
 

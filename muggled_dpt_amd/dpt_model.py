@@ -1143,6 +1143,20 @@ class DPTModel(nn.Module):
         preds = self._maps_for_photos(images_bgr, guided, max_side_length, use_square_sizing, batch_size)
         return relight_images(preds, list(images_bgr), light_dirs, ambient, diffuse, specular, shininess_log2, space=space, **camera)
 
+    def inference_shade(self, images_bgr, light_dirs, ambient: float = 0.35, diffuse: float = 0.9, specular: float = 0.0, shininess_log2: int = 4,
+                        space: str | None = None, guided=None, max_side_length: int | None = None, use_square_sizing: bool = True, batch_size: int = 32,
+                        **controls) -> list[Tensor]:
+        """inference_relight with cast shadows and ambient occlusion -> a list of uint8 [V,H_i,W_i,3] BGR device tensors in input order (not in the
+        reference): one inference_images call, with guided = (radius, eps) one postprocess.guided_upsample_images call, then one relight.shade_images
+        call; nothing is read back. controls: shade_images' keywords (shadow_reach / shadow_bias / shadow_thickness / ao_reach / ao_radius / ao_bias /
+        ao_strength / grid_hw and the camera's fov_deg / min_depth / max_depth / step / edge_ratio). space None: "depth" for a metric model (config
+        is_metric), else "inverse". Limits (screen space only, an assumed thickness, a reach of 32 grid nodes): see relight's docstring."""
+        from .relight import shade_images
+        if space is None:
+            space = "depth" if self.config.get("is_metric", False) else "inverse"
+        preds = self._maps_for_photos(images_bgr, guided, max_side_length, use_square_sizing, batch_size)
+        return shade_images(preds, list(images_bgr), light_dirs, ambient, diffuse, specular, shininess_log2, space=space, **controls)
+
     def render_views(self, image_bgr: np.ndarray, view_proj=None, out_wh=(1280, 720), max_side_length: int | None = None,
                      use_square_sizing: bool = True, fov_deg: float | None = None, min_depth: float | None = None, max_depth: float | None = None,
                      edge_threshold: float | None = None, target_num_faces=None, mode: str = "triangles", cull: str = "back", point_size: float = 2.0,

@@ -57,6 +57,7 @@ GUIDED_MAX_RADIUS = 64  # the largest window radius of mdpt_post_guided_upsample
 REFOCUS_MAX_RADIUS, REFOCUS_TILE = 32, 32  # MDPT_REFOCUS_*: the largest blur radius of mdpt_post_refocus, the side of its output tiles
 REFOCUS_INVERSE, REFOCUS_DEPTH = ALIGN_INVERSE, ALIGN_DEPTH  # its spaces are the MDPT_ALIGN_* ones
 NORMALS_MAX_STEP, NORMALS_TILE, NORMALS_MAX_LIGHTS = 16, 32, 64  # MDPT_NORMALS_*: the largest difference step of mdpt_post_normals, its tile side, the lights a call takes
+SHADOWS_MAX_REACH, SHADOWS_AO_DIRECTIONS = 32, 8  # MDPT_SHADOWS_*: the grid nodes a shadow march / an occlusion direction of mdpt_post_shadows walks at most, its directions
 
 
 def _hipcc() -> str:
@@ -265,6 +266,8 @@ SYMBOLS = {
     "mdpt_post_refocus": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _D, ctypes.POINTER(_D), _D, _D, _I, _VP, _SZ, _VP, _VP, _VP]),
     "mdpt_post_normals_scratch_bytes": (ctypes.c_int, [_VP, _I, ctypes.POINTER(_SZ)]),
     "mdpt_post_normals": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _D, _D, _D, _VP, _I, _D, _D, _D, _I, _VP, _SZ, _VP]),
+    "mdpt_post_shadows_scratch_bytes": (ctypes.c_int, [_VP, _I, ctypes.POINTER(_SZ)]),
+    "mdpt_post_shadows": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _D, _D, _D, _VP, _I, _D, _D, _D, _I, _I, _D, _D, _I, _D, _D, _D, _VP, _SZ, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

@@ -29,7 +29,9 @@ For one image or several, --normals saves every photo's encoded surface normal m
 <name>_normals.png in the current directory. --relight X Y Z saves every photo shaded by its normals with a light towards (X, Y, Z) in the camera frame
 (x right, y up, z towards the camera; relight.relight_images, one call for the whole list): <name>_relit000.png; --relight_sweep N instead writes N frames
 <name>_relit###.png for a ring of N lights at the elevation of (X, Y, Z), starting at its azimuth; --relight_guided RADIUS EPS enlarges the depth with the
-photo as the guide first (and takes the normals over one photo pixel).
+photo as the guide first (and takes the normals over one photo pixel). --shade X Y Z [--shade_sweep N] does the same with cast shadows and ambient
+occlusion (relight.shade_images; --shade_reach K: the grid nodes a shadow march walks, 0 .. 32, 0 = no shadows; --shade_ao STRENGTH: the occlusion's
+strength, 0 = none): <name>_shaded###.png.
 --stable [ALPHA] takes the images, in order, as the frames of ONE clip (they share a size): DPTModel.inference_video aligns every frame's map to the
 frame before it and filters the clip over time (muggled_dpt_amd.video; ALPHA = the filter's weight, default 0.3), video_display shows it with a
 carried range: <name>_stable.npy (fp32, the model's map size) and <name>_stable.png (the photo's size) into --output (a directory; default: the
@@ -96,7 +98,12 @@ def main():
     ap.add_argument("--relight", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="save every photo relit from the direction (X, Y, Z) "
                     "(x right, y up, z towards the camera), e.g. -1 1 1")
     ap.add_argument("--relight_sweep", type=int, default=None, metavar="N", help="relight: N frames for a ring of lights at the elevation of (X, Y, Z)")
-    ap.add_argument("--relight_guided", nargs=2, default=None, metavar=("RADIUS", "EPS"), help="normals / relight: enlarge the depth with the photo as the guide first")
+    ap.add_argument("--relight_guided", nargs=2, default=None, metavar=("RADIUS", "EPS"), help="normals / relight / shade: enlarge the depth with the photo as the guide first")
+    ap.add_argument("--shade", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="save every photo relit from (X, Y, Z) with cast shadows "
+                    "and ambient occlusion, <name>_shaded000.png")
+    ap.add_argument("--shade_sweep", type=int, default=None, metavar="N", help="shade: N frames for a ring of lights at the elevation of (X, Y, Z)")
+    ap.add_argument("--shade_reach", type=int, default=32, metavar="K", help="shade: grid nodes a shadow march walks (0 .. 32; 0: no shadows)")
+    ap.add_argument("--shade_ao", type=float, default=1.0, metavar="STRENGTH", help="shade: strength of the ambient occlusion (0: none)")
     ap.add_argument("--truth", default=None, metavar="DIR", help="measured depth per image, DIR/<name>.npy (fp32, any size; zero or NaN: no measurement): "
                     "fit the prediction to it, save <name>_true.npy (true depth at the truth's size) and <name>_metrics.json")
     ap.add_argument("--truth_method", default="lstsq", choices=("lstsq", "median"), help="truth: least squares, or median and mean absolute deviation")
@@ -317,7 +324,7 @@ def save_refocus(args, is_metric, paths, images, depths):
 def save_relight(args, is_metric, paths, images, depths):
     """--normals / --relight: one relight.depth_normals and / or one relight.relight_images call over all images (after one guided_upsample_images call with
     --relight_guided), PNGs per photo"""
-    if not (args.normals or args.relight):
+    if not (args.normals or args.relight or args.shade):
         return
     import math
     from muggled_dpt_amd import mesh_io
@@ -336,16 +343,27 @@ def save_relight(args, is_metric, paths, images, depths):
     if args.normals:
         for path, bgr in zip(paths, depth_normals(depths, None, images, space=space, step=step, encode=True)[1]):
             save(os.path.splitext(os.path.basename(path))[0] + "_normals.png", bgr, "normal map")
+    def ring_of(light, sweep):
+        """the light alone, or with a sweep a ring of lights at its elevation that starts at its azimuth"""
+        if not sweep:
+            return [light]
+        x, y, z = light
+        ring = light_sweep(sweep, math.degrees(math.atan2(z, math.hypot(x, y))))
+        turn = math.atan2(y, x)
+        return [(math.cos(turn) * lx - math.sin(turn) * ly, math.sin(turn) * lx + math.cos(turn) * ly, lz) for lx, ly, lz in ring.tolist()]
+
     if args.relight:
-        x, y, z = args.relight
-        lights = [args.relight]
-        if args.relight_sweep:
-            ring = light_sweep(args.relight_sweep, math.degrees(math.atan2(z, math.hypot(x, y))))
-            turn = math.atan2(y, x)  # the ring starts at the given light's azimuth
-            lights = [(math.cos(turn) * lx - math.sin(turn) * ly, math.sin(turn) * lx + math.cos(turn) * ly, lz) for lx, ly, lz in ring.tolist()]
+        lights = ring_of(args.relight, args.relight_sweep)
         for path, frames in zip(paths, relight_images(depths, images, lights, space=space, step=step)):
             for k, bgr in enumerate(frames):
                 save(os.path.splitext(os.path.basename(path))[0] + f"_relit{k:03d}.png", bgr, f"light {tuple(round(v, 3) for v in lights[k])}")
+    if args.shade:
+        from muggled_dpt_amd.relight import shade_images
+        lights = ring_of(args.shade, args.shade_sweep)
+        for path, frames in zip(paths, shade_images(depths, images, lights, space=space, step=step, shadow_reach=args.shade_reach, ao_strength=args.shade_ao)):
+            for k, bgr in enumerate(frames):
+                save(os.path.splitext(os.path.basename(path))[0] + f"_shaded{k:03d}.png", bgr,
+                     f"light {tuple(round(v, 3) for v in lights[k])}, shadows over {args.shade_reach} nodes, occlusion {args.shade_ao:g}")
 
 
 def save_block_norms(model, args, paths, images):
