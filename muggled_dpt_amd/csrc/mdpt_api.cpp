@@ -1,5 +1,5 @@
 // libmdpt: the model half of the C ABI of include/mdpt.h (entry points only; inventory / plan: mdpt_inventory.cpp, stage drivers: mdpt_stages.cpp,
-// test hooks: mdpt_debug.cpp, depth post-processing: mdpt_post.cpp).
+// test hooks: mdpt_debug.cpp, depth post-processing: mdpt_post.cpp and the mdpt_post_*.cpp beside it).
 #include "mdpt_internal.h"
 
 // =====================================================================================================================

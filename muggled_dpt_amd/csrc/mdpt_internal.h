@@ -2,7 +2,9 @@
 //   mdpt_inventory.cpp  parameter inventory (reference key names), packed-weight layout, activation workspace plan
 //   mdpt_stages.cpp     launch sequences of the five stages (patch embed, encoder, reassemble, fusion, head) for all families
 //   mdpt_api.cpp        the C entry points of the model: handle lifecycle, forward, stage entry points, probes
-//   mdpt_post.cpp       the depth post-processing entry points (mdpt_post_*: no handle, no plan, no workspace)
+//   mdpt_post.cpp       the depth post-processing entry points (mdpt_post_*: no handle, no plan, no workspace): display, still image, masks, block norms;
+//   mdpt_post_geometry.cpp  ... mesh, render, hole filling; mdpt_post_fit.cpp  ... tiles, true-depth alignment, guided upsampling, video;
+//   mdpt_post_photo.cpp     ... refocus, normals, shadows; mdpt_post_checks.h  the argument checks and layout asserts these four share, each once
 //   mdpt_debug.cpp      test / measurement hooks and the RCCL wrapper
 //
 // libmdpt: C ABI (include/mdpt.h) + host-side orchestration of the DPT forward path on one MI355X.

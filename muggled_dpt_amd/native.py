@@ -20,7 +20,8 @@ LIB_PATH = os.path.join(CSRC, "libmdpt.so")
 # kernel files that touch MFMA operand planes are compiled twice, once per operand format (csrc/op_types.h): bf16 and, with
 # -DMDPT_OP_F16, fp16; the launcher symbols carry the format as a suffix and the host side (mdpt_internal.h: OPL) picks per handle
 OPERAND_SOURCES = ("gemm.hip", "conv3h.hip", "attention.hip", "elementwise.hip", "swin.hip", "head.hip")
-PLAIN_SOURCES = ("postprocess.hip", "stream_probe.hip", "mdpt_api.cpp", "mdpt_post.cpp", "mdpt_inventory.cpp", "mdpt_stages.cpp", "mdpt_debug.cpp", "mdpt_prof.cpp")
+PLAIN_SOURCES = ("postprocess.hip", "stream_probe.hip", "mdpt_api.cpp", "mdpt_post.cpp", "mdpt_post_geometry.cpp", "mdpt_post_fit.cpp", "mdpt_post_photo.cpp",
+                 "mdpt_inventory.cpp", "mdpt_stages.cpp", "mdpt_debug.cpp", "mdpt_prof.cpp")
 SOURCES = OPERAND_SOURCES + PLAIN_SOURCES
 # everything a source may #include: every header and .inc of csrc/ (read from the directory, so that a new one cannot be forgotten; sorted:
 # source_hash() covers the names) and the public header. _stale() and source_hash() go over SOURCES + HEADERS

@@ -11,12 +11,21 @@ from torch import Tensor
 
 from .. import native
 
-# the host tables of the per-item entry points, one numpy record per struct of include/mdpt.h (csrc/mdpt_post.cpp static_asserts the layouts)
+# the host tables of the per-item entry points, one numpy record per struct of include/mdpt.h (csrc/mdpt_post_*.cpp static_assert the layouts, field by field:
+# MDPT_SAME_RECORD of csrc/mdpt_post_checks.h)
 TILE_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4")])  # mdpt_tile
 PAIR_RECORD = np.dtype([("pred", "<u8"), ("ph", "<i4"), ("pw", "<i4"), ("truth", "<u8"), ("valid", "<u8"), ("H", "<i4"), ("W", "<i4")])  # mdpt_depth_pair
 GUIDED_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("out", "<u8"),
                           ("scratch_off", "<i8")])  # mdpt_guided_pair
 TEXTURE_RECORD = np.dtype([("bgr", "<u8"), ("h", "<i4"), ("w", "<i4")])  # mdpt_texture
+REFOCUS_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("out", "<u8"),
+                           ("scratch_off", "<i8"), ("tile_off", "<i8")])  # mdpt_refocus_pair
+NORMALS_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("normals", "<u8"),
+                           ("encoded", "<u8"), ("relit", "<u8"), ("scratch_off", "<i8"), ("tile_off", "<i8"), ("kx", "<f8"), ("ky", "<f8"), ("step", "<i4"),
+                           ("pad", "<i4")])  # mdpt_normals_pair
+SHADOWS_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("gh", "<i4"), ("gw", "<i4"),
+                           ("ao", "<u8"), ("vis", "<u8"), ("relit", "<u8"), ("scratch_off", "<i8"), ("tile_off", "<i8"), ("gtile_off", "<i8"), ("kx", "<f8"),
+                           ("ky", "<f8"), ("step", "<i4"), ("pad", "<i4")])  # mdpt_shadows_pair
 
 
 def _need_cuda(tensors, what: str, expected: str = "expected a CUDA tensor") -> None:

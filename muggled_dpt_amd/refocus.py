@@ -16,16 +16,15 @@ import numpy as np
 import torch
 
 from . import native
-from .postprocess._common import (_launch, _photo_list, _photo_pointers, _prediction_list, _upload_records, _views, packed_offsets, prediction_count, ptr,
-                                  record_table, scratch_bytes)
+from .postprocess._common import (REFOCUS_RECORD, _launch, _photo_list, _photo_pointers, _prediction_list, _upload_records, _views, packed_offsets,
+                                  prediction_count, ptr, record_table, scratch_bytes)
 
 __all__ = ["REFOCUS_SPACES", "REFOCUS_APERTURE", "refocus_images", "defocus_planes"]
 
 REFOCUS_SPACES = {"inverse": native.REFOCUS_INVERSE, "depth": native.REFOCUS_DEPTH}
 REFOCUS_APERTURE = 32.0  # photo pixels of blur radius per unit of defocus: half the map's range away from the focal plane reaches the default max_radius
-# mdpt_refocus_pair of include/mdpt.h (csrc/mdpt_post.cpp static_asserts the layout)
-REFOCUS_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("out", "<u8"),
-                           ("scratch_off", "<i8"), ("tile_off", "<i8")])
+# (REFOCUS_RECORD, mdpt_refocus_pair of include/mdpt.h, stands with the other record tables in postprocess/_common.py; csrc/mdpt_post_photo.cpp
+# static_asserts the layout)
 
 
 def _refocus_checked(predictions, images_bgr, focus, focus_xy, aperture, max_radius, focus_range, space, what: str):

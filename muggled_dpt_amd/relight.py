@@ -23,21 +23,15 @@ import numpy as np
 import torch
 
 from . import native
-from .postprocess._common import (_launch, _photo_list, _photo_pointers, _prediction_list, _upload_records, _views, packed_offsets, prediction_count,
-                                  record_table, scratch_bytes)
+from .postprocess._common import (NORMALS_RECORD, SHADOWS_RECORD, _launch, _photo_list, _photo_pointers, _prediction_list, _upload_records, _views,
+                                  packed_offsets, prediction_count, record_table, scratch_bytes)
 from .postprocess.mesh import MESH_FOV_DEG, MESH_MAX_DEPTH, MESH_MIN_DEPTH
 
 __all__ = ["NORMALS_SPACES", "depth_normals", "relight_images", "light_sweep", "default_step", "light_occlusion", "shade_images"]
 
 NORMALS_SPACES = {"inverse": native.ALIGN_INVERSE, "depth": native.ALIGN_DEPTH}
-# mdpt_normals_pair of include/mdpt.h (csrc/mdpt_post.cpp static_asserts the layout)
-NORMALS_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("normals", "<u8"),
-                           ("encoded", "<u8"), ("relit", "<u8"), ("scratch_off", "<i8"), ("tile_off", "<i8"), ("kx", "<f8"), ("ky", "<f8"), ("step", "<i4"),
-                           ("pad", "<i4")])
-# mdpt_shadows_pair of include/mdpt.h (csrc/mdpt_post.cpp static_asserts the layout)
-SHADOWS_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("gh", "<i4"), ("gw", "<i4"),
-                           ("ao", "<u8"), ("vis", "<u8"), ("relit", "<u8"), ("scratch_off", "<i8"), ("tile_off", "<i8"), ("gtile_off", "<i8"), ("kx", "<f8"),
-                           ("ky", "<f8"), ("step", "<i4"), ("pad", "<i4")])
+# (NORMALS_RECORD and SHADOWS_RECORD, mdpt_normals_pair and mdpt_shadows_pair of include/mdpt.h, stand with the other record tables in
+# postprocess/_common.py; csrc/mdpt_post_photo.cpp static_asserts the layouts)
 
 
 def light_sweep(n: int, elevation_deg: float = 35.0) -> np.ndarray:

@@ -101,8 +101,9 @@ def test_scratch_bytes_equals_the_direct_call():
 
 
 def test_record_tables_have_the_layout_of_their_structs():
-    """item sizes and field offsets of mdpt_tile, mdpt_depth_pair, mdpt_guided_pair and mdpt_texture (the static_asserts of csrc/mdpt_post.cpp)"""
-    from muggled_dpt_amd.postprocess._common import GUIDED_RECORD, PAIR_RECORD, TEXTURE_RECORD, TILE_RECORD, record_table
+    """item sizes and field offsets of the seven record structs of include/mdpt.h (the MDPT_SAME_RECORD asserts of csrc/mdpt_post_*.cpp)"""
+    from muggled_dpt_amd.postprocess._common import (GUIDED_RECORD, NORMALS_RECORD, PAIR_RECORD, REFOCUS_RECORD, SHADOWS_RECORD, TEXTURE_RECORD, TILE_RECORD,
+                                                     record_table)
 
     class Map:
         def __init__(self, ptr, h, w):
@@ -117,6 +118,11 @@ def test_record_tables_have_the_layout_of_their_structs():
         "pair": (PAIR_RECORD, 40, {"pred": 0, "ph": 8, "pw": 12, "truth": 16, "valid": 24, "H": 32, "W": 36}),
         "guided": (GUIDED_RECORD, 56, {"map": 0, "h": 8, "w": 12, "photo": 16, "pitch": 24, "H": 32, "W": 36, "out": 40, "scratch_off": 48}),
         "texture": (TEXTURE_RECORD, 16, {"bgr": 0, "h": 8, "w": 12}),
+        "refocus": (REFOCUS_RECORD, 64, {"map": 0, "h": 8, "w": 12, "photo": 16, "pitch": 24, "H": 32, "W": 36, "out": 40, "scratch_off": 48, "tile_off": 56}),
+        "normals": (NORMALS_RECORD, 104, {"map": 0, "h": 8, "w": 12, "photo": 16, "pitch": 24, "H": 32, "W": 36, "normals": 40, "encoded": 48, "relit": 56,
+                                          "scratch_off": 64, "tile_off": 72, "kx": 80, "ky": 88, "step": 96, "pad": 100}),
+        "shadows": (SHADOWS_RECORD, 120, {"map": 0, "h": 8, "w": 12, "photo": 16, "pitch": 24, "H": 32, "W": 36, "gh": 40, "gw": 44, "ao": 48, "vis": 56, "relit": 64,
+                                          "scratch_off": 72, "tile_off": 80, "gtile_off": 88, "kx": 96, "ky": 104, "step": 112, "pad": 116}),
     }
     for name, (dtype, size, offsets) in expected.items():
         lead = tuple(dtype.names[:3])
