@@ -861,6 +861,50 @@ int mdpt_post_shadows(const mdpt_shadows_pair* records_host, const void* records
                       int32_t shininess_log2, int32_t shadow_reach, double shadow_bias, double shadow_thickness, int32_t ao_reach, double ao_radius,
                       double ao_bias, double ao_strength, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Depth segmentation on the device (additive to ABI v6; not in the reference): the depth-connected surfaces of a map as a label plane, a table of
+ * the regions, and "the region under this point" as a mask and a BGRA cutout of the photo. The entry points are named mdpt_segment_*, not
+ * mdpt_post_*: the table of the mdpt_post_* entry points and their refusals is recorded (tests/post_refusal_cases.py and its golden file), and these
+ * have a record of their own (tests/test_segment_cpu.py). Any number of images per call, each independent of the others.
+ * An image is an mdpt_segment_image record: the h x w map (dtype), its int32 [h,w] label output, scratch_off (bytes from `scratch`, a multiple of 8; the
+ * image needs mdpt_segment_scratch_bytes of its record alone from there; regions must not overlap), region_off = the rows of the region tables of
+ * the images before it (image i has R_i = (h w) / min_area rows, an exact bound), tile_off = the sum over the images before it of ceil(h / 32)
+ * ceil(w / 32) (MDPT_SEGMENT_TILE = 32) and pixel_off = the sum of their h w. The table is passed twice: records_host (read by the checks) and
+ * records_dev, its copy in device memory, 8-byte aligned (read by the kernels).
+ *   validity ...... a node is valid iff its value v (widened to fp32) is finite and, in space MDPT_ALIGN_DEPTH, v > 0. lo, hi = the min / max of the
+ *                   image's valid nodes as fp64 (a zero takes the sign +; no valid node: 0, 0) -> range[2 i], range[2 i + 1].
+ *   links ......... two valid neighbours p, q are linked iff, in fp64 on the exact fp32 values, |v_p - v_q| <= step (hi - lo) (MDPT_ALIGN_INVERSE)
+ *                   or <= step min(v_p, v_q) (MDPT_ALIGN_DEPTH); neighbours: the 4 along the axes (connectivity 4) or those and the 4 diagonals (8).
+ *   components .... the connected sets of valid nodes under the links; a component's root is its lowest linear index y w + x. Components of fewer
+ *                   than min_area nodes are dropped; the K kept ones are numbered 0 .. K - 1 in the order of their roots -> counts[i] = K.
+ *   labels ........ a node's region, -1 for a node that is not valid or whose component was dropped.
+ *   per region .... (row region_off + r) area int32; bbox int32 x 4 = x0, y0, x1, y1 inclusive; first int32 = the root; vrange fp32 x 2 = the least and
+ *                   the greatest value; sum_q int64 = the sum of floor((v - lo) / (hi - lo) 2^24 + 0.5) in fp64 (0 where hi == lo).
+ * Ten launches whatever n is: min / max partials, state, a union-find per 32 x 32 tile in LDS, a lock-free merge of the pairs across tile edges
+ * (atomic min, larger root under smaller), flatten + areas, flags, scan, scatter, relabel + statistics, finish. Integer atomics only, every output
+ * bit-deterministic, nothing read back, no synchronisation.
+ * mdpt_segment_colors: labels -> uint8 BGR [h w, 3] per image at colors + 3 pixel_off, a fixed integer hash of the label, -1 black. One launch.
+ * mdpt_segment_cutout: a photo is an mdpt_segment_photo record - the int32 [h,w] labels, the uint8 BGR photo of H x W pixels whose rows lie `pitch`
+ * bytes apart, its BGRA [H,W,4] (4-byte aligned) and mask [H,W] outputs, region_off as above and regions = R_i. picks_dev = int32 [num_picks, 2] in
+ * device memory, {image, value}: value is a node's linear index (by_label = 0: the region under it is selected; a -1 node selects nothing) or a
+ * region (by_label != 0); anything out of range selects nothing. selected = uint8, one per region row of the call, ZERO on entry, marked by the
+ * first launch. Photo pixel (Y, X) belongs to node ((Y h) / H, (X w) / W), integer division; mask = 255 where that node's region is selected,
+ * flipped by invert; BGRA = (BGR AND mask, mask). Two launches (one without picks) whatever n is.
+ * Checks (MDPT_E_INVALID, nothing launched, the message names the argument): null pointers, n outside 1 .. 65535, sizes <= 0 or h w >= 2^31, step
+ * negative or not finite, connectivity not 4 or 8, min_area < 1, a bad dtype or space, wrong region_off / tile_off / pixel_off, misaligned pointers,
+ * a photo pitch < 3 W, num_picks < 0 or picks without picks_dev, a scratch region or `selected` too small, misaligned or overlapping.
+ * Known limits: a surface at a grazing angle has large steps between neighbours and breaks into slivers; a gentle ramp (the ground) connects what
+ * stands on it to the background; regions below min_area are dropped, not merged into a neighbour. */
+#define MDPT_SEGMENT_TILE 32
+typedef struct mdpt_segment_image { const void* map; int32_t h, w; void* labels; int64_t scratch_off, region_off, tile_off, pixel_off; } mdpt_segment_image;
+typedef struct mdpt_segment_photo { const void* labels; int32_t h, w; const void* photo; int64_t pitch; int32_t H, W; void* bgra; void* mask; int64_t region_off; int32_t regions, pad; } mdpt_segment_photo;
+int mdpt_segment_scratch_bytes(const mdpt_segment_image* records_host, int32_t n, size_t* bytes);
+int mdpt_segment_depth(const mdpt_segment_image* records_host, const void* records_dev, int32_t n, int32_t dtype, int32_t space, double step,
+                       int32_t connectivity, int32_t min_area, void* scratch, size_t scratch_bytes, void* counts, void* area, void* bbox, void* first,
+                       void* vrange, void* sum_q, void* range, void* stream);
+int mdpt_segment_colors(const mdpt_segment_image* records_host, const void* records_dev, int32_t n, void* colors, void* stream);
+int mdpt_segment_cutout(const mdpt_segment_photo* records_host, const void* records_dev, int32_t n, const void* picks_dev, int32_t num_picks,
+                        int32_t by_label, void* selected, size_t selected_bytes, int32_t invert, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

@@ -500,6 +500,40 @@ struct ShadowsJob {
 };
 int mdpt_launch_post_shadows(const ShadowsJob& job, hipStream_t stream);
 
+// depth segmentation (post_segment.inc; an image = mdpt_segment_image of include/mdpt.h): the h x w map (the table's dtype), its int32 [h,w] label plane
+// (the parents of the union-find until the relabel launch), where the image's scratch starts, the rows of the region tables, the 32 x 32 tiles and the
+// nodes of the images before it. Device table, indexed by image. An image's scratch: SEGMENT_HEADER_BYTES ({min, max} partials of the map as ordered
+// keys, then SegmentState), an int32 plane (a root's area, then its new id), a byte plane of link bits, the kept roots of every 256-node block.
+struct SegmentImage { const void* map; int h, w; int* labels; long long scratch_off, region_off, tile_off, pixel_off; };
+#define SEGMENT_TILE 32      // nodes of one union-find workgroup along each axis (one thread each)
+#define SEGMENT_PARTS 64     // workgroups that share the min / max of one map
+#define SEGMENT_HEADER_BYTES 1024
+inline size_t segment_image_tiles(size_t h, size_t w) { return ((h + SEGMENT_TILE - 1) / SEGMENT_TILE) * ((w + SEGMENT_TILE - 1) / SEGMENT_TILE); }
+inline size_t segment_image_scratch_bytes(size_t h, size_t w) {
+    const size_t n = h * w;
+    return (SEGMENT_HEADER_BYTES + 4 * n + ((n + 7) & ~(size_t)7) + (n + 255) / 256 * 4 + 7) & ~(size_t)7;
+}
+inline size_t segment_image_regions(size_t h, size_t w, size_t min_area) { return (h * w) / min_area; }  // (min_area >= 1: at most h w)
+// one call: the region tables (rows region_off .. of image i) - area int32, bbox int32 x 4 {x0, y0, x1, y1}, first int32, vrange fp32 x 2 {vmin, vmax},
+// sum_q int64 - counts int32 [P] and range fp64 [P, 2] = {lo, hi}. Ten launches whatever P is. Integer atomics only, bit-deterministic.
+struct SegmentJob {
+    const SegmentImage* images;
+    int P, dt, depth_space, conn8, min_area, pad;
+    double step;
+    char* scratch;
+    int* counts; int* area; int* bbox; int* first; float* vrange; long long* sum_q; double* range;
+    size_t max_pixels, max_regions, total_tiles;
+};
+int mdpt_launch_segment(const SegmentJob& job, hipStream_t stream);
+// label -> BGR through a fixed integer hash (-1: black): colors = uint8 [nodes of the call, 3] in image order
+int mdpt_launch_segment_colors(const SegmentImage* images, int P, size_t max_pixels, unsigned char* colors, hipStream_t stream);
+// pick-to-cutout (a photo = mdpt_segment_photo of include/mdpt.h): the int32 [h,w] labels, the uint8 BGR photo of H x W pixels whose rows lie `pitch`
+// bytes apart, its BGRA [H,W,4] and mask [H,W] outputs, where the image's rows of `selected` start and how many it has. picks = int32 [num_picks, 2]
+// {image, node (by_label == 0) or region (by_label != 0)} on the device; selected = uint8, one per region row, zero on entry. Two launches.
+struct SegmentPhoto { const int* labels; int h, w; const unsigned char* photo; long long pitch; int H, W; unsigned char* bgra; unsigned char* mask; long long region_off; int regions, pad; };
+int mdpt_launch_segment_cutout(const SegmentPhoto* photos, int P, const int* picks, int num_picks, int by_label, unsigned char* selected, int invert,
+                               size_t max_groups, hipStream_t stream);
+
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);
 

@@ -1157,6 +1157,18 @@ class DPTModel(nn.Module):
         preds = self._maps_for_photos(images_bgr, guided, max_side_length, use_square_sizing, batch_size)
         return shade_images(preds, list(images_bgr), light_dirs, ambient, diffuse, specular, shininess_log2, space=space, **controls)
 
+    def inference_segments(self, images_bgr, space: str | None = None, step: float | None = None, connectivity: int = 4, min_area: int = 16,
+                           max_side_length: int | None = None, use_square_sizing: bool = True, batch_size: int = 32):
+        """The depth-connected surfaces of every photo's own predicted depth -> segment.DepthSegments at the model's resolution (not in the reference):
+        one inference_images call, then one segment.segment_depth call; nothing is read back. images_bgr as inference_images takes them. step (None:
+        segment_depth's default) / connectivity / min_area are segment_depth's; space None: "depth" for a metric model (config is_metric), "inverse"
+        for every other. segment.region_cutouts takes the result and the photos. Limits: see segment's docstring."""
+        from .segment import SEGMENT_STEP, segment_depth
+        if space is None:
+            space = "depth" if self.config.get("is_metric", False) else "inverse"
+        preds = self.inference_images(images_bgr, max_side_length, use_square_sizing, batch_size)
+        return segment_depth(preds, space=space, step=SEGMENT_STEP if step is None else step, connectivity=connectivity, min_area=min_area)
+
     def render_views(self, image_bgr: np.ndarray, view_proj=None, out_wh=(1280, 720), max_side_length: int | None = None,
                      use_square_sizing: bool = True, fov_deg: float | None = None, min_depth: float | None = None, max_depth: float | None = None,
                      edge_threshold: float | None = None, target_num_faces=None, mode: str = "triangles", cull: str = "back", point_size: float = 2.0,

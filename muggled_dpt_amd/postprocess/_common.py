@@ -26,6 +26,11 @@ NORMALS_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo",
 SHADOWS_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("gh", "<i4"), ("gw", "<i4"),
                            ("ao", "<u8"), ("vis", "<u8"), ("relit", "<u8"), ("scratch_off", "<i8"), ("tile_off", "<i8"), ("gtile_off", "<i8"), ("kx", "<f8"),
                            ("ky", "<f8"), ("step", "<i4"), ("pad", "<i4")])  # mdpt_shadows_pair
+# (mdpt_segment_image and mdpt_segment_photo, for muggled_dpt_amd/segment.py; csrc/mdpt_segment.cpp asserts the layouts)
+SEGMENT_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("labels", "<u8"), ("scratch_off", "<i8"), ("region_off", "<i8"), ("tile_off", "<i8"),
+                           ("pixel_off", "<i8")])
+SEGMENT_PHOTO_RECORD = np.dtype([("labels", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("bgra", "<u8"),
+                                 ("mask", "<u8"), ("region_off", "<i8"), ("regions", "<i4"), ("pad", "<i4")])
 
 
 def _need_cuda(tensors, what: str, expected: str = "expected a CUDA tensor") -> None:

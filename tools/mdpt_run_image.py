@@ -32,6 +32,11 @@ For one image or several, --normals saves every photo's encoded surface normal m
 photo as the guide first (and takes the normals over one photo pixel). --shade X Y Z [--shade_sweep N] does the same with cast shadows and ambient
 occlusion (relight.shade_images; --shade_reach K: the grid nodes a shadow march walks, 0 .. 32, 0 = no shadows; --shade_ao STRENGTH: the occlusion's
 strength, 0 = none): <name>_shaded###.png.
+For one image or several, --segments STEP saves every map's depth-connected surfaces (segment.segment_depth, one call for the whole list; STEP = the largest
+step between linked neighbours, as a share of the map's range or, for a metric model, of the nearer depth, e.g. 0.02; --segments_min_area N drops smaller
+regions, default 16; --segments_conn 4|8): <name>_labels.npy (int32, the model's map size, -1 = no region) and <name>_regions.json (area, bbox, first, vmin,
+vmax, mean per region) in the current directory. --pick X Y (repeatable; normalised) also saves the regions under those points of every photo as
+<name>_pick_mask.npy (uint8) and <name>_pick_cutout.npy (BGRA) at the photo's size (segment.region_cutouts).
 --stable [ALPHA] takes the images, in order, as the frames of ONE clip (they share a size): DPTModel.inference_video aligns every frame's map to the
 frame before it and filters the clip over time (muggled_dpt_amd.video; ALPHA = the filter's weight, default 0.3), video_display shows it with a
 carried range: <name>_stable.npy (fp32, the model's map size) and <name>_stable.png (the photo's size) into --output (a directory; default: the
@@ -104,6 +109,12 @@ def main():
     ap.add_argument("--shade_sweep", type=int, default=None, metavar="N", help="shade: N frames for a ring of lights at the elevation of (X, Y, Z)")
     ap.add_argument("--shade_reach", type=int, default=32, metavar="K", help="shade: grid nodes a shadow march walks (0 .. 32; 0: no shadows)")
     ap.add_argument("--shade_ao", type=float, default=1.0, metavar="STRENGTH", help="shade: strength of the ambient occlusion (0: none)")
+    ap.add_argument("--segments", type=float, default=None, metavar="STEP", help="save every map's depth-connected surfaces, <name>_labels.npy and "
+                    "<name>_regions.json: the largest step between linked neighbours (share of the range; of the nearer depth for a metric model), e.g. 0.02")
+    ap.add_argument("--segments_min_area", type=int, default=16, metavar="N", help="segments: drop regions of fewer than N nodes")
+    ap.add_argument("--segments_conn", type=int, default=4, choices=(4, 8), help="segments: neighbours along the axes, or the diagonals too")
+    ap.add_argument("--pick", type=float, nargs=2, action="append", default=None, metavar=("X", "Y"), help="segments: save the region under this point of "
+                    "every photo (normalised; repeatable) as <name>_pick_mask.npy and <name>_pick_cutout.npy")
     ap.add_argument("--truth", default=None, metavar="DIR", help="measured depth per image, DIR/<name>.npy (fp32, any size; zero or NaN: no measurement): "
                     "fit the prediction to it, save <name>_true.npy (true depth at the truth's size) and <name>_metrics.json")
     ap.add_argument("--truth_method", default="lstsq", choices=("lstsq", "median"), help="truth: least squares, or median and mean absolute deviation")
@@ -172,6 +183,7 @@ def main():
     save_guided(args, args.image_path or ["synthetic.npy"], [img], [depth])
     save_refocus(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
     save_relight(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
+    save_segments(args, bool(cfg.get("is_metric", False)), args.image_path or ["synthetic.npy"], [img], [depth])
 
 
 def crop_argument(args):
@@ -321,6 +333,30 @@ def save_refocus(args, is_metric, paths, images, depths):
         print("saved", out, f"({bgr.shape[1]}x{bgr.shape[0]}, {where}, aperture {args.refocus[1]:g}, radius <= {args.refocus_radius})")
 
 
+def save_segments(args, is_metric, paths, images, depths):
+    """--segments / --pick: one segment.segment_depth call over all maps, the labels and the region table per image; with --pick one region_cutouts call"""
+    if args.segments is None:
+        if args.pick:
+            raise SystemExit("--pick needs --segments STEP")
+        return
+    import json
+    from muggled_dpt_amd.segment import region_cutouts, segment_depth
+    seg = segment_depth(depths, space="depth" if is_metric else "inverse", step=args.segments, connectivity=args.segments_conn, min_area=args.segments_min_area)
+    for path, labels, rows in zip(paths, seg.labels, seg.region_views()):
+        stem = os.path.splitext(os.path.basename(path))[0]
+        np.save(stem + "_labels.npy", labels.cpu().numpy())
+        table = {name: rows[name].cpu().numpy().tolist() for name in ("area", "bbox", "first", "vmin", "vmax", "mean")}
+        with open(stem + "_regions.json", "w") as fh:
+            json.dump(dict(count=rows["count"], **table), fh)
+        print("saved", stem + "_labels.npy", stem + "_regions.json", f"({rows['count']} regions of {labels.shape[1]}x{labels.shape[0]} nodes)")
+    if args.pick:
+        for path, (cutout, mask) in zip(paths, region_cutouts(seg, images, points=[[tuple(p) for p in args.pick]] * len(images))):
+            stem = os.path.splitext(os.path.basename(path))[0]
+            np.save(stem + "_pick_mask.npy", mask.cpu().numpy())
+            np.save(stem + "_pick_cutout.npy", cutout.cpu().numpy())
+            print("saved", stem + "_pick_mask.npy", stem + "_pick_cutout.npy")
+
+
 def save_relight(args, is_metric, paths, images, depths):
     """--normals / --relight: one relight.depth_normals and / or one relight.relight_images call over all images (after one guided_upsample_images call with
     --relight_guided), PNGs per photo"""
@@ -425,6 +461,7 @@ def run_images(model, args, t0, is_metric=False):
     save_guided(args, args.image_path, images, depths)
     save_refocus(args, is_metric, args.image_path, images, depths)
     save_relight(args, is_metric, args.image_path, images, depths)
+    save_segments(args, is_metric, args.image_path, images, depths)
 
 
 def run_clip(model, args):
