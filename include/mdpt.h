@@ -939,7 +939,7 @@ int mdpt_debug_side_stream_info(mdpt_handle* h, int32_t* candidates, int32_t* re
 int mdpt_debug_read(mdpt_handle* h, const char* name, void* out_f32, size_t out_floats, void* workspace, size_t workspace_bytes,
                     void* stream);
 
-/* The handle-less kernel hooks below (mdpt_debug_gemm / _attention / _conv3) take their 16-bit operands as bf16 (0, default) or fp16 (1):
+/* The handle-less kernel hooks below (mdpt_debug_gemm / _attention / _conv3 / _gemm_form / _ksplit_finish) take their 16-bit operands as bf16 (0, default) or fp16 (1):
  * process-wide switch, tests only. */
 int mdpt_debug_set_operand_format(int32_t fp16);
 
@@ -960,6 +960,39 @@ int mdpt_debug_conv3(const void* in_bf16, const void* w_packed_bf16, const void*
                      int32_t Wu, void* out_f32, void* out_bf16, int32_t relu_bf16, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                      int32_t path, int32_t tile, int32_t iters, void* stream, void* dbg_times, const void* in_lo_bf16_or_null,
                      const void* w_lo_bf16_or_null, void* out_lo_bf16_or_null);  /* lo planes: the bf16x3 (fp32-class) mode */
+/* test hook: ONE launch of the GEMM family in any of its operand / epilogue forms on caller-provided device buffers. The record mirrors the
+ * launcher's internal parameter block field for field (csrc/mdpt_kernels.h GemmParams has the meaning of each; the fp8 fields and the SwinV2
+ * QKV epilogue are left out): 16-bit operand and output planes in the format of mdpt_debug_set_operand_format, fp32 everything else, null =
+ * absent. amode: 0 dense rows, 1 token rows (tok_*), 2 3x3 taps over NHWC (Hi .. cstride; the hook supplies the zero page). ekind: 0 generic
+ * (bias .. wscale, out_*), 1 QKV (q_hi .. qscale), 2 patch + pos (pos, tok_np, npad, out_f32), 3 depth-to-space (d2s_*, Ho, Wo, out_hi / out_lo),
+ * 4 depth head (head_*; N = 32). tile: 0 = the launcher's rule, 1 128x128, 2 256x256, 4 256x128, 5 8-phase 256x256, 6 64x64. ksplit > 1: K in
+ * ranges, partial planes at ks_part (ks_all: every range). Nothing is allocated besides the hook's own 256-byte zero page; sizes are the caller's.
+ * The launcher's own argument checks apply: a combination it refuses returns a positive HIP error code and launches nothing. */
+typedef struct mdpt_gemm_form {
+    const void* a_hi; const void* a_lo; const void* w_hi; const void* w_lo;
+    int32_t M, N, K, lda, ldw, npass;
+    int32_t amode, ekind, tile, act;
+    int32_t tok_np, tok_stride;
+    int32_t Hi, Wi, Cin, Ho, Wo, cstride;
+    const void* bias; const void* gamma; const void* resid;
+    int32_t ldr, bias_img_stride, bias_img_rows;
+    void* out_f32; void* out_hi; void* out_lo;
+    int32_t ldc, relu_bf16, acc_init;
+    const void* wscale;
+    void* q_hi; void* q_lo; void* k_hi; void* k_lo; void* vt_hi; void* vt_lo;
+    int32_t F, heads, npad, npadv;
+    float qscale;
+    const void* pos;
+    int32_t d2s_k, d2s_cout;
+    const void* head_w; const void* head_b; void* head_out;
+    int32_t head_sigmoid, head_out_dtype;
+    int32_t ksplit, ks_all;
+    void* ks_part;
+} mdpt_gemm_form;
+int mdpt_debug_gemm_form(const mdpt_gemm_form* form, void* stream);
+/* ... and the finishing kernel behind a ks_all launch of the same record: out_f32 / out_hi / out_lo [M, N] (row stride ldc) = the sum of the ksplit
+ * partial planes at ks_part in the order z = 0, 1, ... (+ bias); relu_bf16 applies a ReLU to the operand planes only. */
+int mdpt_debug_ksplit_finish(const mdpt_gemm_form* form, void* stream);
 
 /* Per-launch HIP-event profiler (bench.py's roofline leg): events are recorded on the launch stream around every
  * kernel launch while enabled. mdpt_profile_report() waits for the recorded events and writes a JSON summary

@@ -214,6 +214,46 @@ int mdpt_debug_conv3(const void* in_bf16, const void* w_packed_bf16, const void*
     return 0;
 }
 
+// ---- test hook: one launch of mdpt_launch_gemm in any operand / epilogue form (include/mdpt.h mdpt_gemm_form mirrors GemmParams field for field;
+//      the fp8 fields and MDPT_E_SWQKV are left out). The launcher's own checks decide what is refused; the hook only supplies the zero page.
+int mdpt_debug_gemm_form(const mdpt_gemm_form* f, void* stream) {
+    if (!f || !f->a_hi || !f->w_hi) return fail(MDPT_E_INVALID, "null argument");
+    if (f->ekind == MDPT_E_SWQKV) return fail(MDPT_E_UNSUPPORTED, "mdpt_debug_gemm_form: the SwinV2 QKV epilogue is not part of this hook");
+    static op_t* zero_page = nullptr;  // test hook only: allocated once, never freed
+    if (!zero_page) {
+        if (hipMalloc((void**)&zero_page, 256) != hipSuccess || hipMemset(zero_page, 0, 256) != hipSuccess) return fail(MDPT_E_STATE, "zero page allocation failed");
+    }
+    GemmParams g;
+    memset(&g, 0, sizeof(g));
+    g.A_hi = (const op_t*)f->a_hi; g.A_lo = (const op_t*)f->a_lo; g.W_hi = (const op_t*)f->w_hi; g.W_lo = (const op_t*)f->w_lo;
+    g.M = f->M; g.N = f->N; g.K = f->K; g.lda = f->lda; g.ldw = f->ldw; g.npass = f->npass;
+    g.zero_page = zero_page;
+    g.amode = f->amode; g.ekind = f->ekind; g.tile = f->tile; g.act = f->act;
+    g.tok_np = f->tok_np; g.tok_stride = f->tok_stride;
+    g.Hi = f->Hi; g.Wi = f->Wi; g.Cin = f->Cin; g.Ho = f->Ho; g.Wo = f->Wo; g.cstride = f->cstride;
+    g.bias = (const float*)f->bias; g.gamma = (const float*)f->gamma; g.resid = (const float*)f->resid; g.ldr = f->ldr;
+    g.bias_img_stride = f->bias_img_stride; g.bias_img_rows = f->bias_img_rows;
+    g.out_f32 = (float*)f->out_f32; g.out_hi = (op_t*)f->out_hi; g.out_lo = (op_t*)f->out_lo; g.ldc = f->ldc;
+    g.relu_bf16 = f->relu_bf16; g.acc_init = f->acc_init; g.wscale = (const float*)f->wscale;
+    g.q_hi = (op_t*)f->q_hi; g.q_lo = (op_t*)f->q_lo; g.k_hi = (op_t*)f->k_hi; g.k_lo = (op_t*)f->k_lo; g.vt_hi = (op_t*)f->vt_hi; g.vt_lo = (op_t*)f->vt_lo;
+    g.F = f->F; g.heads = f->heads; g.npad = f->npad; g.npadv = f->npadv; g.qscale = f->qscale;
+    g.pos = (const float*)f->pos;
+    g.d2s_k = f->d2s_k; g.d2s_cout = f->d2s_cout;
+    g.head_w = (const float*)f->head_w; g.head_b = (const float*)f->head_b; g.head_sigmoid = f->head_sigmoid; g.head_out = f->head_out;
+    g.head_out_dtype = f->head_out_dtype;
+    g.ksplit = f->ksplit; g.ks_part = (float*)f->ks_part; g.ks_all = f->ks_all;
+    CHK(OPLG(mdpt_launch_gemm, g, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- test hook: the finishing kernel behind a ks_all launch of the same record
+int mdpt_debug_ksplit_finish(const mdpt_gemm_form* f, void* stream) {
+    if (!f || !f->ks_part || (!f->out_f32 && !f->out_hi)) return fail(MDPT_E_INVALID, "null argument");
+    CHK(OPLG(mdpt_launch_ksplit_finish, (const float*)f->ks_part, (size_t)f->M * f->ldc, f->ksplit, (const float*)f->bias, (float*)f->out_f32, (op_t*)f->out_hi,
+             (op_t*)f->out_lo, f->relu_bf16, f->M, f->N, f->ldc, (hipStream_t)stream, 0, 0));
+    return 0;
+}
+
 // ---- test hook: the fused attention kernel on caller-provided head-major operands (bf16 mode, head dim 64, no bias):
 //      Q, K [B, heads, npad, 64] (Q pre-scaled by 1/8), Vt [B, heads, 64, npadv] (pad columns zero) -> out [B * npad, heads * 64]
 int mdpt_debug_attention(const void* q_bf16, const void* k_bf16, const void* vt_bf16, void* out_bf16, int32_t B, int32_t heads, int32_t N,

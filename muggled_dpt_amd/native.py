@@ -187,6 +187,29 @@ _SZ = ctypes.c_size_t
 _I = ctypes.c_int32
 _D = ctypes.c_double
 _VP4 = ctypes.POINTER(ctypes.c_void_p)
+
+A_DENSE, A_TOKENS, A_CONV3 = 0, 1, 2  # MDPT_A_* / MDPT_E_* / MDPT_TILE_* of csrc/mdpt_kernels.h, as mdpt_gemm_form takes them
+E_GENERIC, E_QKV, E_PATCH, E_D2S, E_HEAD = 0, 1, 2, 3, 4
+TILE_AUTO, TILE_128x128, TILE_256x256, TILE_256x128, TILE_PP256, TILE_64x64 = 0, 1, 2, 4, 5, 6
+
+
+class MdptGemmForm(ctypes.Structure):
+    """mdpt_gemm_form of include/mdpt.h (test hook mdpt_debug_gemm_form): same fields, same order."""
+    _fields_ = (
+        [(n, _VP) for n in ("a_hi", "a_lo", "w_hi", "w_lo")]
+        + [(n, _I) for n in ("M", "N", "K", "lda", "ldw", "npass", "amode", "ekind", "tile", "act", "tok_np", "tok_stride",
+                             "Hi", "Wi", "Cin", "Ho", "Wo", "cstride")]
+        + [(n, _VP) for n in ("bias", "gamma", "resid")]
+        + [(n, _I) for n in ("ldr", "bias_img_stride", "bias_img_rows")]
+        + [(n, _VP) for n in ("out_f32", "out_hi", "out_lo")]
+        + [(n, _I) for n in ("ldc", "relu_bf16", "acc_init")]
+        + [(n, _VP) for n in ("wscale", "q_hi", "q_lo", "k_hi", "k_lo", "vt_hi", "vt_lo")]
+        + [(n, _I) for n in ("F", "heads", "npad", "npadv")]
+        + [("qscale", ctypes.c_float), ("pos", _VP), ("d2s_k", _I), ("d2s_cout", _I)]
+        + [(n, _VP) for n in ("head_w", "head_b", "head_out")]
+        + [(n, _I) for n in ("head_sigmoid", "head_out_dtype", "ksplit", "ks_all")]
+        + [("ks_part", _VP)]
+    )
 SYMBOLS = {
     "mdpt_abi_version": (ctypes.c_int, []),
     "mdpt_last_error": (ctypes.c_char_p, []),
@@ -282,6 +305,8 @@ SYMBOLS = {
     "mdpt_debug_gemm": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
     "mdpt_debug_attention": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     "mdpt_debug_conv3": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "mdpt_debug_gemm_form": (ctypes.c_int, [ctypes.POINTER(MdptGemmForm), _VP]),
+    "mdpt_debug_ksplit_finish": (ctypes.c_int, [ctypes.POINTER(MdptGemmForm), _VP]),
     "mdpt_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "mdpt_profile_report": (ctypes.c_int, [ctypes.c_char_p, _SZ]),
     "mdpt_debug_set_stop": (ctypes.c_int, [_VP, _I, _I]),
