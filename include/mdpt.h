@@ -939,7 +939,7 @@ int mdpt_debug_side_stream_info(mdpt_handle* h, int32_t* candidates, int32_t* re
 int mdpt_debug_read(mdpt_handle* h, const char* name, void* out_f32, size_t out_floats, void* workspace, size_t workspace_bytes,
                     void* stream);
 
-/* The handle-less kernel hooks below (mdpt_debug_gemm / _attention / _conv3 / _gemm_form / _ksplit_finish) take their 16-bit operands as bf16 (0, default) or fp16 (1):
+/* The handle-less kernel hooks below (mdpt_debug_gemm / _attention / _conv3 / _gemm_form / _ksplit_finish / _attention_form / _attn_weights_form) take their 16-bit operands as bf16 (0, default) or fp16 (1):
  * process-wide switch, tests only. */
 int mdpt_debug_set_operand_format(int32_t fp16);
 
@@ -952,6 +952,31 @@ int mdpt_debug_gemm(const void* a_bf16, const void* w_bf16, void* out_f32, void*
  * columns; out [B * npad, heads * 64]. */
 int mdpt_debug_attention(const void* q_bf16, const void* k_bf16, const void* vt_bf16, void* out_bf16, int32_t B, int32_t heads, int32_t N,
                          int32_t npad, int32_t npadv, int32_t iters, void* stream);
+/* test hook: ONE launch of the fused attention in any of its forms on caller-provided device buffers. The record mirrors the launcher's internal
+ * parameter block field for field (csrc/mdpt_kernels.h AttnParams has the meaning of each; tail_last, which the launcher sets itself, is left
+ * out): 16-bit planes in the format of mdpt_debug_set_operand_format, null = absent. x3: the three-pass form on hi + lo planes. bias_lut / tq / tk:
+ * the additive table, s[q][k] += lut[h][tq[q] - tk[k]]. rowmap != null: SwinV2 window attention (head_dim 32, B = images * win_nw, region ids or null,
+ * bias_run4 / bias_row / bias_ww, swin_ls, out_ld). allow_split_kv: the latency form where the launcher's rule takes it. Nothing is allocated; sizes
+ * are the caller's. The launcher's own argument checks apply: a combination it refuses returns a positive HIP error code and launches nothing. */
+typedef struct mdpt_attn_form {
+    const void* q_hi; const void* q_lo; const void* k_hi; const void* k_lo;
+    const void* vt_hi; const void* vt_lo;
+    void* out_hi; void* out_lo;
+    int32_t B, heads, N, npad, npadv, F;
+    int32_t x3;
+    const float* bias_lut; int32_t bias_elen; const int32_t* tq; const int32_t* tk;
+    int32_t head_dim;
+    int32_t win_nw; const int32_t* rowmap; const int32_t* region; int32_t region_ld;
+    int32_t bias_run4;
+    int32_t bias_row;
+    int32_t bias_ww;
+    const float* swin_ls;
+    int32_t out_ld;
+    int32_t allow_split_kv;
+} mdpt_attn_form;
+int mdpt_debug_attention_form(const mdpt_attn_form* form, void* stream);
+/* ... and the diagnostic weights dump of the same record: out_f32 [B, heads, N, N] = the softmax probabilities (natural units) */
+int mdpt_debug_attn_weights_form(const mdpt_attn_form* form, void* out_f32, void* stream);
 /* test/bench hook: one 3x3 stride-1 conv Cin -> Cout (256 = the decoder's fusion width, every epilogue form; 128 = the head's first conv,
  * bias only) on caller-provided operands, through the implicit-GEMM
  * kernels (path 0, tile = MDPT_TILE_*) or the halo-staged kernel (path 1). Replaces one nn.Conv2d(…, 3, padding=1) of the reference's

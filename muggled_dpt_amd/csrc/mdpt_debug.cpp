@@ -267,6 +267,36 @@ int mdpt_debug_attention(const void* q_bf16, const void* k_bf16, const void* vt_
     return 0;
 }
 
+// ---- test hook: one launch of mdpt_launch_attention in any of its forms (include/mdpt.h mdpt_attn_form mirrors AttnParams field for field; the
+//      launcher sets tail_last itself). The launcher's own checks decide what is refused.
+static AttnParams attn_form_params(const mdpt_attn_form* f) {
+    AttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q_hi = (const op_t*)f->q_hi; a.q_lo = (const op_t*)f->q_lo; a.k_hi = (const op_t*)f->k_hi; a.k_lo = (const op_t*)f->k_lo;
+    a.vt_hi = (const op_t*)f->vt_hi; a.vt_lo = (const op_t*)f->vt_lo; a.out_hi = (op_t*)f->out_hi; a.out_lo = (op_t*)f->out_lo;
+    a.B = f->B; a.heads = f->heads; a.N = f->N; a.npad = f->npad; a.npadv = f->npadv; a.F = f->F; a.x3 = f->x3;
+    a.bias_lut = f->bias_lut; a.bias_elen = f->bias_elen; a.tq = f->tq; a.tk = f->tk;
+    a.head_dim = f->head_dim;
+    a.win_nw = f->win_nw; a.rowmap = f->rowmap; a.region = f->region; a.region_ld = f->region_ld;
+    a.bias_run4 = f->bias_run4; a.bias_row = f->bias_row; a.bias_ww = f->bias_ww;
+    a.swin_ls = f->swin_ls; a.out_ld = f->out_ld; a.allow_split_kv = f->allow_split_kv;
+    return a;
+}
+
+int mdpt_debug_attention_form(const mdpt_attn_form* f, void* stream) {
+    if (!f || !f->q_hi || !f->k_hi || !f->vt_hi || !f->out_hi) return fail(MDPT_E_INVALID, "null argument");
+    if (f->x3 && (!f->q_lo || !f->k_lo || !f->vt_lo || !f->out_lo)) return fail(MDPT_E_INVALID, "null argument: x3 takes the lo planes");
+    CHK(OPLG(mdpt_launch_attention, attn_form_params(f), (hipStream_t)stream));
+    return 0;
+}
+
+// ---- test hook: the diagnostic weights dump (mdpt_launch_attn_weights) of the same record
+int mdpt_debug_attn_weights_form(const mdpt_attn_form* f, void* out_f32, void* stream) {
+    if (!f || !f->q_hi || !f->k_hi || !out_f32) return fail(MDPT_E_INVALID, "null argument");
+    CHK(OPLG(mdpt_launch_attn_weights, attn_form_params(f), (float*)out_f32, (hipStream_t)stream));
+    return 0;
+}
+
 // ---- RCCL all-gather wrapper (resolved lazily so the library itself has no link-time dependency on RCCL)
 int mdpt_allgather(void* comm, const void* send_dev, void* recv_dev, size_t count_per_rank, int32_t dtype, void* stream) {
     typedef int (*allgather_fn)(const void*, void*, size_t, int, void*, void*);

@@ -210,6 +210,19 @@ class MdptGemmForm(ctypes.Structure):
         + [(n, _I) for n in ("head_sigmoid", "head_out_dtype", "ksplit", "ks_all")]
         + [("ks_part", _VP)]
     )
+
+
+class MdptAttnForm(ctypes.Structure):
+    """mdpt_attn_form of include/mdpt.h (test hooks mdpt_debug_attention_form / mdpt_debug_attn_weights_form): same fields, same order."""
+    _fields_ = (
+        [(n, _VP) for n in ("q_hi", "q_lo", "k_hi", "k_lo", "vt_hi", "vt_lo", "out_hi", "out_lo")]
+        + [(n, _I) for n in ("B", "heads", "N", "npad", "npadv", "F", "x3")]
+        + [("bias_lut", _VP), ("bias_elen", _I), ("tq", _VP), ("tk", _VP), ("head_dim", _I), ("win_nw", _I), ("rowmap", _VP), ("region", _VP)]
+        + [(n, _I) for n in ("region_ld", "bias_run4", "bias_row", "bias_ww")]
+        + [("swin_ls", _VP), ("out_ld", _I), ("allow_split_kv", _I)]
+    )
+
+
 SYMBOLS = {
     "mdpt_abi_version": (ctypes.c_int, []),
     "mdpt_last_error": (ctypes.c_char_p, []),
@@ -307,6 +320,8 @@ SYMBOLS = {
     "mdpt_debug_conv3": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "mdpt_debug_gemm_form": (ctypes.c_int, [ctypes.POINTER(MdptGemmForm), _VP]),
     "mdpt_debug_ksplit_finish": (ctypes.c_int, [ctypes.POINTER(MdptGemmForm), _VP]),
+    "mdpt_debug_attention_form": (ctypes.c_int, [ctypes.POINTER(MdptAttnForm), _VP]),
+    "mdpt_debug_attn_weights_form": (ctypes.c_int, [ctypes.POINTER(MdptAttnForm), _VP, _VP]),
     "mdpt_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "mdpt_profile_report": (ctypes.c_int, [ctypes.c_char_p, _SZ]),
     "mdpt_debug_set_stop": (ctypes.c_int, [_VP, _I, _I]),
