@@ -905,6 +905,53 @@ int mdpt_segment_colors(const mdpt_segment_image* records_host, const void* reco
 int mdpt_segment_cutout(const mdpt_segment_photo* records_host, const void* records_dev, int32_t n, const void* picks_dev, int32_t num_picks,
                         int32_t by_label, void* selected, size_t selected_bytes, int32_t invert, void* stream);
 
+/* Locally varying true-depth alignment on the device (additive to ABI v6; not in the reference): depth completion from a relative-depth map and a
+ * measured depth map that is partly valid and at its own resolution (a LiDAR sweep, a structure-from-motion point set, a cheap sensor). Where
+ * mdpt_post_align_* fit one (A, B) per image, these fit one per cell of a grid over the truth, smooth them, and apply the coefficient FIELD, so that a
+ * drift of the prediction's error across the frame does not stay in the result. Named mdpt_localfit_*, not mdpt_post_*, for the reason
+ * mdpt_segment_* are (the recorded table of the mdpt_post_* entry points); their record is tests/test_local_align_cpu.py. Any number of pairs per
+ * call, each independent of the others, sizes and grids may all differ.
+ * A pair is an mdpt_localfit_pair record: the seven fields of an mdpt_depth_pair record - pred ph x pw of pred_dtype, truth fp32 H x W, valid uint8 H x W or
+ * NULL - the grid gh x gw (1 <= gh <= H, 1 <= gw <= W, both <= MDPT_LOCALFIT_MAX_GRID = 256), cell_off = the sum of gh gw over the pairs before it
+ * (its rows of the moment and coefficient tables), scratch_off (bytes from `scratch`, a multiple of 8; the pair needs mdpt_localfit_scratch_bytes
+ * of its record alone from there; regions must not overlap) and out (apply only). The table is passed twice: records_host (read by the checks) and
+ * records_dev, its copy in device memory, 8-byte aligned (read by the kernels). All arithmetic fp64, nothing contracted, results rounded once.
+ *   samples ....... exactly those of mdpt_post_align_fit with MDPT_ALIGN_LSTSQ: the same validity rule and truth range [tmin, tmax], v = the
+ *                   prediction at the centre of the truth pixel by the same resampler, t = 1 / truth (MDPT_ALIGN_INVERSE) or truth (MDPT_ALIGN_DEPTH).
+ *   cell moments .. the sample at truth pixel (Y, X) belongs to cell (Y gh / H, X gw / W), integer division (mdpt_post_guided_upsample's rule). Per
+ *                   cell M = {n, Sv, St, Svv, Svt, Stt} -> moments_f64 [cells of the call, 6]. A cell's pixels are taken in row-major order inside
+ *                   the cell, in chunks of MDPT_LOCALFIT_CHUNK = 2048: a workgroup reduces one chunk (thread t its pixels t, t + 256, ... in order,
+ *                   then a fixed tree) and the next launch adds a cell's chunks in chunk order. The split depends on the pair's own H, W, gh, gw only.
+ *   global fit .... G = the cells' M added in row-major cell order -> sums_f64 [P, 6]; (A0, B0) from G by mdpt_post_align_fit's solve rule, its
+ *                   degenerate rule included -> fit_f64 [P, 2].
+ *   window fit .... node (j, i): the M of the cells with |dj| <= radius and |di| <= radius, clipped to the grid, one running sum with dj outer and di
+ *                   inner, both ascending. A window without a sample takes (A0, B0). Otherwise, where prior > 0 and n_G > 0, prior (G_k / n_G) is
+ *                   added term by term (prior pseudo-samples distributed as the image's own), and the sums are solved by the same rule; a degenerate
+ *                   window (n < 2, var <= 0, A not finite or <= 0) takes (A0, B0). prior = 0: the pure local fit; prior large: the global fit.
+ *   coefficients .. C[j, i] = the window fits summed over the same clipped window in the same order, divided by its cell count (the guided
+ *                   filter's second averaging) -> coeffs_f64 [cells of the call, 2].
+ *   apply ......... per pixel (Y, X) of the record's H x W (the OUTPUT size here; truth and valid are not read and may be NULL; the grid need not fit
+ *                   inside it) (A, B) = C resampled at the pixel's centre, u = (X + 0.5) gw / W - 0.5 clamped to the grid, fp64 weights, rows first,
+ *                   A and B separately; v = the prediction at the pixel's centre; q = A v + B; from there as mdpt_post_align_apply: 1 / q with +inf
+ *                   where q <= 0 in inverse space, q in depth space, clamped to [dmin, dmax] where finite, rounded to fp32 once -> out. NaN stays NaN.
+ * mdpt_localfit_fit: FIVE launches whatever n is (chunk partials, cells, global fit, window fits, coefficient means); mdpt_localfit_apply: ONE. No
+ * atomics, nothing read back, no synchronisation, bit-deterministic. The window sums are direct: (2 radius + 1)^2 additions a node.
+ * Checks (MDPT_E_INVALID, nothing launched, the message names the argument): null pointers, n outside 1 .. 65535, sizes <= 0 or H W >= 2^31, a grid
+ * larger than the truth or over the cap, radius outside 0 .. MDPT_LOCALFIT_MAX_RADIUS = 64, prior negative or not finite, tmin > tmax, dmin > dmax,
+ * a bad dtype or space, a wrong cell_off, misaligned pointers, a scratch region outside the scratch, misaligned or overlapping.
+ * Not done here: edge-aware (photo-guided) propagation of the coefficients, robust reweighting of outliers, a median variant, per-node confidence,
+ * temporal coherence. */
+#define MDPT_LOCALFIT_MAX_GRID 256
+#define MDPT_LOCALFIT_MAX_RADIUS 64
+#define MDPT_LOCALFIT_CHUNK 2048
+typedef struct mdpt_localfit_pair { const void* pred; int32_t ph, pw; const void* truth; const void* valid; int32_t H, W, gh, gw; int64_t cell_off, scratch_off; void* out; } mdpt_localfit_pair;
+int mdpt_localfit_scratch_bytes(const mdpt_localfit_pair* records_host, int32_t n, size_t* bytes);
+int mdpt_localfit_fit(const mdpt_localfit_pair* records_host, const void* records_dev, int32_t n, int32_t pred_dtype, int32_t space, int32_t radius,
+                      double prior, double tmin, double tmax, void* moments_f64, void* fit_f64, void* sums_f64, void* coeffs_f64, void* scratch,
+                      size_t scratch_bytes, void* stream);
+int mdpt_localfit_apply(const mdpt_localfit_pair* records_host, const void* records_dev, int32_t n, int32_t pred_dtype, int32_t space,
+                        const void* coeffs_f64, double dmin, double dmax, void* stream);
+
 /* Stage boundaries of the LAST mdpt_forward on `workspace`, converted to reference layouts (debug / parity taps):
  * which = 0..3 encoder taps [B,N,F]; 4..7 reassembly maps (BCHW); 8 fused map [B,C,8gh,8gw]. */
 int mdpt_export_tap(mdpt_handle* h, int32_t which, void* out_f32, void* workspace, size_t workspace_bytes, void* stream);

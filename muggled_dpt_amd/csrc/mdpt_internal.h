@@ -6,6 +6,7 @@
 //   mdpt_post_geometry.cpp  ... mesh, render, hole filling; mdpt_post_fit.cpp  ... tiles, true-depth alignment, guided upsampling, video;
 //   mdpt_post_photo.cpp     ... refocus, normals, shadows; mdpt_post_checks.h  the argument checks and layout asserts these four share, each once
 //   mdpt_segment.cpp    the mdpt_segment_* entry points (depth segmentation), on the same checks
+//   mdpt_localfit.cpp   the mdpt_localfit_* entry points (locally varying true-depth alignment), on the same checks
 //   mdpt_debug.cpp      test / measurement hooks and the RCCL wrapper
 //
 // libmdpt: C ABI (include/mdpt.h) + host-side orchestration of the DPT forward path on one MI355X.

@@ -534,6 +534,32 @@ struct SegmentPhoto { const int* labels; int h, w; const unsigned char* photo; l
 int mdpt_launch_segment_cutout(const SegmentPhoto* photos, int P, const int* picks, int num_picks, int by_label, unsigned char* selected, int invert,
                                size_t max_groups, hipStream_t stream);
 
+// locally varying true-depth alignment (post_localfit.inc; a pair = mdpt_localfit_pair of include/mdpt.h): an AlignPair (the same seven fields first, so
+// that the sample rule of post_align.inc reads it), the gh x gw grid, the cells of the pairs before it (rows of the moment and coefficient tables),
+// where the pair's scratch starts and, for the apply launch, its fp32 H x W output. Device table, indexed by pair. A pair's scratch: the partial
+// moments [cells][chunks of its largest cell][6], then the window fits [cells][2], fp64.
+struct LocalFitPair { const void* pred; int ph, pw; const float* truth; const unsigned char* valid; int H, W, gh, gw; long long cell_off, scratch_off; float* out; };
+#define LOCALFIT_MAX_GRID 256   // cells along an axis, at most
+#define LOCALFIT_MAX_RADIUS 64  // window radius in cells, at most
+// the chunks (MDPT_TILE_FIT_CHUNK pixels, row-major inside the cell) of the largest cell: a cell spans at most ceil(H / gh) x ceil(W / gw) pixels
+__host__ __device__ inline size_t localfit_cell_chunks(size_t H, size_t W, size_t gh, size_t gw) { return tile_fit_chunks(((H + gh - 1) / gh) * ((W + gw - 1) / gw)); }
+inline size_t localfit_pair_scratch_bytes(size_t H, size_t W, size_t gh, size_t gw) {
+    return (gh * gw * localfit_cell_chunks(H, W, gh, gw) * 6 + gh * gw * 2) * sizeof(double);
+}
+// fit: five launches whatever P is (cell partials, cells, global fit, window fits, coefficient means) -> moments [cells of the call, 6], fit [P, 2],
+// sums [P, 6], coeffs [cells of the call, 2]; max_blocks / max_cells: the largest cells x chunks / cells of a pair. apply: one launch.
+struct LocalFitJob {
+    const LocalFitPair* pairs;
+    int P, dt, inverse, radius;
+    double prior, tmin, tmax;
+    char* scratch;
+    double* moments; double* fit; double* sums; double* coeffs;
+    size_t max_blocks, max_cells;
+};
+int mdpt_launch_localfit_fit(const LocalFitJob& job, hipStream_t stream);
+int mdpt_launch_localfit_apply(const LocalFitPair* pairs, int P, size_t max_pixels, int dt, int inverse, const double* coeffs, double dmin, double dmax,
+                               hipStream_t stream);
+
 // stream_probe.hip: does `candidate` run kernels beside `waiter_stream`? (*seen != 0 after synchronising with waiter_stream)
 int mdpt_launch_queue_probe(unsigned* flag, unsigned* seen, hipStream_t waiter_stream, hipStream_t candidate, hipEvent_t ready);
 

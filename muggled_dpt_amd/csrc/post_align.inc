@@ -257,8 +257,17 @@ __global__ __launch_bounds__(64) void align_metrics_solve_kernel(const AlignPair
     o[10] = 100.0 * sqrt(fmax(s[5] / m - me * me, 0.0));
 }
 
-// true depth: out pixel (Y, X) of pair p's H x W output (at out + offs[p]) = the prediction at the pixel's centre, q = A v + B, d = 1 / q in inverse
-// space (q <= 0: +inf), q in depth space; then clamped to [dmin, dmax] where those are finite, rounded to fp32 once. NaN stays NaN.
+// q = A v + B -> true depth (align_apply_kernel and the local fit's apply): d = 1 / q in inverse space (q <= 0: +inf), q in depth space; then clamped
+// to [dmin, dmax] where those are finite, rounded to fp32 once. NaN stays NaN.
+__device__ __forceinline__ float align_depth_of(double q, int inverse, double dmin, double dmax) {
+#pragma clang fp contract(off)
+    double d = inverse ? (q <= 0.0 ? (double)INFINITY : 1.0 / q) : q;
+    if (isfinite(dmin) && d < dmin) d = dmin;
+    if (isfinite(dmax) && d > dmax) d = dmax;
+    return (float)d;
+}
+
+// true depth: out pixel (Y, X) of pair p's H x W output (at out + offs[p]) = the prediction at the pixel's centre, q = A v + B -> align_depth_of
 __global__ __launch_bounds__(256) void align_apply_kernel(const AlignPair* __restrict__ pairs, int dt, int inverse, const double* __restrict__ fit,
                                                           const long long* __restrict__ offs, double dmin, double dmax, float* __restrict__ out) {
 #pragma clang fp contract(off)
@@ -267,11 +276,7 @@ __global__ __launch_bounds__(256) void align_apply_kernel(const AlignPair* __res
     const double A = fit ? fit[2 * (size_t)blockIdx.y] : 1.0, B = fit ? fit[2 * (size_t)blockIdx.y + 1] : 0.0;
     float* o = out + offs[blockIdx.y];
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
-        const double q = A * align_pred_at(p, dt, e) + B;
-        double d = inverse ? (q <= 0.0 ? (double)INFINITY : 1.0 / q) : q;
-        if (isfinite(dmin) && d < dmin) d = dmin;
-        if (isfinite(dmax) && d > dmax) d = dmax;
-        o[e] = (float)d;
+        o[e] = align_depth_of(A * align_pred_at(p, dt, e) + B, inverse, dmin, dmax);
     }
 }
 

@@ -104,9 +104,11 @@ __device__ __forceinline__ unsigned block_rank(int k, unsigned& total) {
 // [c CHUNK, (c + 1) CHUNK) of the record's n - each thread its MDPT_TILE_FIT_CHUNK / 256 = 8 strided samples in order, sample(e, a) adding sample e
 // to the thread's K sums, then block_sum_f64's fixed tree - into row[c K ..], `row` being the record's parts[max_chunks][K]. A chunk past n does
 // nothing (uniform over the block, before any barrier: the grid's x extent is that of the largest record). chunk_order_sum adds the chunks up.
+// chunk_reduce_at: the same for a workgroup whose chunk c is not its blockIdx.x (the local fit's grid folds cell and chunk into x); `o` = where the
+// chunk's K sums go.
 template <int K, typename Sample>
-__device__ __forceinline__ void chunk_reduce(size_t n, double* __restrict__ row, Sample&& sample) {
-    const size_t base = (size_t)blockIdx.x * MDPT_TILE_FIT_CHUNK;
+__device__ __forceinline__ void chunk_reduce_at(size_t chunk, size_t n, double* __restrict__ o, Sample&& sample) {
+    const size_t base = chunk * MDPT_TILE_FIT_CHUNK;
     if (base >= n) return;
     double a[K];
 #pragma unroll
@@ -117,10 +119,12 @@ __device__ __forceinline__ void chunk_reduce(size_t n, double* __restrict__ row,
         sample(e, a);
     }
     block_sum_f64<K>(a);
-    if (threadIdx.x == 0) {
-        double* o = row + (size_t)blockIdx.x * K;
+    if (threadIdx.x == 0)
         for (int k = 0; k < K; ++k) o[k] = a[k];
-    }
+}
+template <int K, typename Sample>
+__device__ __forceinline__ void chunk_reduce(size_t n, double* __restrict__ row, Sample&& sample) {
+    chunk_reduce_at<K>((size_t)blockIdx.x, n, row + (size_t)blockIdx.x * K, sample);
 }
 
 // lane k < K of the block adds partial sum k of `chunks` chunks in chunk order -> s[k] (shared); the block is synchronised on return

@@ -20,3 +20,4 @@
 #include "post_normals.inc"  // surface normals and relighting: edge-aware differences of the unprojected map over an LDS tile, V lights a pass
 #include "post_shadows.inc"  // cast shadows and ambient occlusion for the relighting: marches over an LDS tile of a working grid, folded into the shading
 #include "post_segment.inc"  // depth segmentation: union-find over LDS tiles, lock-free merge across tiles, region tables, pick-to-cutout
+#include "post_localfit.inc" // locally varying true-depth alignment: moments per grid cell, window fits, a coefficient field applied per pixel

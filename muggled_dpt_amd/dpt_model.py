@@ -1083,6 +1083,23 @@ class DPTModel(nn.Module):
         metrics = depth_metrics(preds, truths, fit, valid, space, truth_range, staged=staged)
         return fit, metrics, true_depth(preds, fit, staged[3], space)
 
+    def inference_completed(self, images_bgr, truths, valid=None, grid_hw=None, radius: int | None = None, prior: float | None = None, truth_range=(None, None),
+                            clamp=(None, None), max_side_length: int | None = None, use_square_sizing: bool = True, batch_size: int = 32, return_fit: bool = False):
+        """Photos with sparse measured depth maps (a LiDAR sweep, structure-from-motion points, a cheap sensor) -> dense true-depth maps that follow the
+        measurements locally, a list of fp32 [1,H_i,W_i] at each truth's own size (depth completion; not in the reference): one inference_images call, then
+        local_align.fit_true_depth_local and true_depth_local, all on the device with nothing read back. truths / valid / truth_range as evaluate_depth takes them;
+        grid_hw / radius / prior are fit_true_depth_local's (None: its defaults, user-facing choices and not measured optima). A metric model (config is_metric)
+        is fitted in depth space, every other model in inverse-depth space, as evaluate_depth chooses. return_fit: -> (maps, LocalDepthFit).
+        postprocess.depth_metrics(maps, truths, fit=None, space="depth") scores the result. Limits: see local_align's docstring."""
+        from .local_align import LOCAL_GRID_HW, LOCAL_PRIOR, LOCAL_RADIUS, fit_true_depth_local, true_depth_local
+        space = "depth" if self.config.get("is_metric", False) else "inverse"
+        preds = self.inference_images(images_bgr, max_side_length, use_square_sizing, batch_size)
+        fit = fit_true_depth_local(preds, truths, valid, space=space, grid_hw=LOCAL_GRID_HW if grid_hw is None else grid_hw,
+                                   radius=LOCAL_RADIUS if radius is None else radius, prior=LOCAL_PRIOR if prior is None else prior, truth_range=truth_range)
+        hws = [tuple(int(v) for v in (t.shape[-2:])) for t in truths]
+        maps = true_depth_local(preds, fit, hws, space, clamp)
+        return (maps, fit) if return_fit else maps
+
     def inference_guided(self, images_bgr, radius: int = 8, eps: float = 1e-4, max_side_length: int | None = None, use_square_sizing: bool = True,
                          batch_size: int = 32) -> list[Tensor]:
         """Depth of every photo at the PHOTO's own size with the photo as the guide of the enlargement -> a list of fp32 [1,H_i,W_i] maps in input

@@ -21,7 +21,7 @@ LIB_PATH = os.path.join(CSRC, "libmdpt.so")
 # -DMDPT_OP_F16, fp16; the launcher symbols carry the format as a suffix and the host side (mdpt_internal.h: OPL) picks per handle
 OPERAND_SOURCES = ("gemm.hip", "conv3h.hip", "attention.hip", "elementwise.hip", "swin.hip", "head.hip")
 PLAIN_SOURCES = ("postprocess.hip", "stream_probe.hip", "mdpt_api.cpp", "mdpt_post.cpp", "mdpt_post_geometry.cpp", "mdpt_post_fit.cpp", "mdpt_post_photo.cpp",
-                 "mdpt_segment.cpp", "mdpt_inventory.cpp", "mdpt_stages.cpp", "mdpt_debug.cpp", "mdpt_prof.cpp")
+                 "mdpt_segment.cpp", "mdpt_localfit.cpp", "mdpt_inventory.cpp", "mdpt_stages.cpp", "mdpt_debug.cpp", "mdpt_prof.cpp")
 SOURCES = OPERAND_SOURCES + PLAIN_SOURCES
 # everything a source may #include: every header and .inc of csrc/ (read from the directory, so that a new one cannot be forgotten; sorted:
 # source_hash() covers the names) and the public header. _stale() and source_hash() go over SOURCES + HEADERS
@@ -59,6 +59,7 @@ REFOCUS_MAX_RADIUS, REFOCUS_TILE = 32, 32  # MDPT_REFOCUS_*: the largest blur ra
 REFOCUS_INVERSE, REFOCUS_DEPTH = ALIGN_INVERSE, ALIGN_DEPTH  # its spaces are the MDPT_ALIGN_* ones
 NORMALS_MAX_STEP, NORMALS_TILE, NORMALS_MAX_LIGHTS = 16, 32, 64  # MDPT_NORMALS_*: the largest difference step of mdpt_post_normals, its tile side, the lights a call takes
 SEGMENT_TILE = 32  # MDPT_SEGMENT_TILE: the side of the union-find tiles of mdpt_segment_depth (its spaces are the MDPT_ALIGN_* ones)
+LOCALFIT_MAX_GRID, LOCALFIT_MAX_RADIUS, LOCALFIT_CHUNK = 256, 64, 2048  # MDPT_LOCALFIT_*: the cells an axis and the window radius mdpt_localfit_fit takes at most, the pixels of a cell's chunk
 SHADOWS_MAX_REACH, SHADOWS_AO_DIRECTIONS = 32, 8  # MDPT_SHADOWS_*: the grid nodes a shadow march / an occlusion direction of mdpt_post_shadows walks at most, its directions
 
 
@@ -310,6 +311,9 @@ SYMBOLS = {
     "mdpt_segment_depth": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _D, _I, _I, _VP, _SZ, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mdpt_segment_colors": (ctypes.c_int, [_VP, _VP, _I, _VP, _VP]),
     "mdpt_segment_cutout": (ctypes.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _SZ, _I, _VP]),
+    "mdpt_localfit_scratch_bytes": (ctypes.c_int, [_VP, _I, ctypes.POINTER(_SZ)]),
+    "mdpt_localfit_fit": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _I, _D, _D, _D, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "mdpt_localfit_apply": (ctypes.c_int, [_VP, _VP, _I, _I, _I, _VP, _D, _D, _VP]),
     "mdpt_export_tap": (ctypes.c_int, [_VP, _I, _VP, _VP, _SZ, _VP]),
     "mdpt_set_gemm_tile": (ctypes.c_int, [_VP, _I]),
     "mdpt_set_batch_split": (ctypes.c_int, [_VP, _I]),

@@ -31,6 +31,9 @@ SEGMENT_RECORD = np.dtype([("map", "<u8"), ("h", "<i4"), ("w", "<i4"), ("labels"
                            ("pixel_off", "<i8")])
 SEGMENT_PHOTO_RECORD = np.dtype([("labels", "<u8"), ("h", "<i4"), ("w", "<i4"), ("photo", "<u8"), ("pitch", "<i8"), ("H", "<i4"), ("W", "<i4"), ("bgra", "<u8"),
                                  ("mask", "<u8"), ("region_off", "<i8"), ("regions", "<i4"), ("pad", "<i4")])
+# (mdpt_localfit_pair, for muggled_dpt_amd/local_align.py; csrc/mdpt_localfit.cpp asserts the layout)
+LOCALFIT_RECORD = np.dtype([("pred", "<u8"), ("ph", "<i4"), ("pw", "<i4"), ("truth", "<u8"), ("valid", "<u8"), ("H", "<i4"), ("W", "<i4"), ("gh", "<i4"), ("gw", "<i4"),
+                            ("cell_off", "<i8"), ("scratch_off", "<i8"), ("out", "<u8")])
 
 
 def _need_cuda(tensors, what: str, expected: str = "expected a CUDA tensor") -> None:

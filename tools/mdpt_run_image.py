@@ -37,6 +37,9 @@ step between linked neighbours, as a share of the map's range or, for a metric m
 regions, default 16; --segments_conn 4|8): <name>_labels.npy (int32, the model's map size, -1 = no region) and <name>_regions.json (area, bbox, first, vmin,
 vmax, mean per region) in the current directory. --pick X Y (repeatable; normalised) also saves the regions under those points of every photo as
 <name>_pick_mask.npy (uint8) and <name>_pick_cutout.npy (BGRA) at the photo's size (segment.region_cutouts).
+With --truth DIR, --truth_local GH GW also completes every measured map (local_align.fit_true_depth_local over a GH x GW grid, true_depth_local; --truth_local_radius R
+cells, default 1; --truth_local_prior K pseudo-samples, default 4): <name>_completed.npy (true depth at the truth's size, following the measurements locally) and
+the completed map's metrics next to the global fit's in <name>_metrics.json (keys local_*).
 --stable [ALPHA] takes the images, in order, as the frames of ONE clip (they share a size): DPTModel.inference_video aligns every frame's map to the
 frame before it and filters the clip over time (muggled_dpt_amd.video; ALPHA = the filter's weight, default 0.3), video_display shows it with a
 carried range: <name>_stable.npy (fp32, the model's map size) and <name>_stable.png (the photo's size) into --output (a directory; default: the
@@ -118,6 +121,10 @@ def main():
     ap.add_argument("--truth", default=None, metavar="DIR", help="measured depth per image, DIR/<name>.npy (fp32, any size; zero or NaN: no measurement): "
                     "fit the prediction to it, save <name>_true.npy (true depth at the truth's size) and <name>_metrics.json")
     ap.add_argument("--truth_method", default="lstsq", choices=("lstsq", "median"), help="truth: least squares, or median and mean absolute deviation")
+    ap.add_argument("--truth_local", type=int, nargs=2, default=None, metavar=("GH", "GW"), help="truth: also fit (A, B) per cell of a GH x GW grid over the "
+                    "truth and save <name>_completed.npy (depth completion), its metrics beside the global fit's")
+    ap.add_argument("--truth_local_radius", type=int, default=1, metavar="R", help="truth_local: window radius in cells")
+    ap.add_argument("--truth_local_prior", type=float, default=4.0, metavar="K", help="truth_local: pseudo-samples that pull a window towards the global fit")
     ap.add_argument("--truth_range", type=float, nargs=2, default=None, metavar=("MIN", "MAX"), help="truth: use measurements within MIN..MAX only")
     ap.add_argument("--render", default=None, metavar="DIR", help="render every image's depth mesh from moving viewpoints (the 3D viewer's view) and "
                     "save <name>_view###.png (RGBA) into DIR; the mesh follows --mesh_faces / --mesh_fov / --mesh_points")
@@ -282,8 +289,11 @@ def save_tiled(model, args, paths, images):
 
 def save_true_depth(args, is_metric, paths, depths):
     """--truth: one fit_true_depth, one depth_metrics and one true_depth call over all images (what DPTModel.evaluate_depth runs after its
-    inference), the fit and the metrics read back once for the .json files"""
+    inference), the fit and the metrics read back once for the .json files; --truth_local: fit_true_depth_local and true_depth_local as well (what
+    DPTModel.inference_completed runs), the completed maps scored as they are (depth_metrics with fit=None in depth space)"""
     if not args.truth:
+        if args.truth_local is not None:
+            raise SystemExit("--truth_local needs --truth DIR")
         return
     import json
     from muggled_dpt_amd import postprocess as pp
@@ -294,10 +304,22 @@ def save_true_depth(args, is_metric, paths, depths):
     fit = pp.fit_true_depth(depths, truths, None, space, args.truth_method, rng)
     metrics = pp.depth_metrics(depths, truths, fit, None, space, rng)
     maps = pp.true_depth(depths, fit, [t.shape for t in truths], space)
+    completed = local_metrics = None
+    if args.truth_local is not None:
+        from muggled_dpt_amd import local_align
+        local = local_align.fit_true_depth_local(depths, truths, None, space=space, grid_hw=tuple(args.truth_local), radius=args.truth_local_radius,
+                                                 prior=args.truth_local_prior, truth_range=rng)
+        completed = local_align.true_depth_local(depths, local, [t.shape for t in truths], space)
+        local_metrics = pp.depth_metrics(completed, truths, None, None, "depth", rng).cpu().tolist()
     fit, metrics = fit.cpu().tolist(), metrics.cpu().tolist()
     for k, stem in enumerate(stems):
         np.save(stem + "_true.npy", maps[k][0].cpu().numpy())
         report = {"A": fit[k][0], "B": fit[k][1], "space": space, "method": args.truth_method, **dict(zip(pp.DEPTH_METRIC_NAMES, metrics[k]))}
+        if completed is not None:
+            np.save(stem + "_completed.npy", completed[k][0].cpu().numpy())
+            report.update({"local_grid": list(args.truth_local), "local_radius": args.truth_local_radius, "local_prior": args.truth_local_prior,
+                           **{"local_" + name: value for name, value in zip(pp.DEPTH_METRIC_NAMES, local_metrics[k])}})
+            print("saved", stem + "_completed.npy", f"(AbsRel {local_metrics[k][2]:.4g}, delta1 {local_metrics[k][7]:.4g})")
         with open(stem + "_metrics.json", "w") as fh:
             json.dump(report, fh, indent=1)
         print("saved", stem + "_true.npy", stem + "_metrics.json", f"(A {fit[k][0]:.6g}, B {fit[k][1]:.6g}, AbsRel {metrics[k][2]:.4g}, delta1 {metrics[k][7]:.4g})")
